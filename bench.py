@@ -1,7 +1,14 @@
 """Benchmark: batched Wolves-and-Bushes env-steps/s on MI355X (BASELINE.json `metric`).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config default|wide31|c5|torus]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run does what the line's headline figure needs and nothing else: set up, warm up, time
+exactly --steps steps, write the last step's outputs if --dump-outputs is given, print the
+line.  --full adds everything measured beside it: the diagnostic launches (per-step launches,
+one-handle and single-launch timings), the other configs' lines under `configs`, and the CPU
+baselines (--no-diag, --no-extra and --no-cpu drop one of them from a --full run).
 
 A step = one fused pass over all B envs of a rank: move, wolves, bushes, kill/eat/starve,
 reward/done, auto-reset and the full observation render, with the inputs (actions,
@@ -12,7 +19,10 @@ the gym `env.step` surface) is timed beside it (`rollout.per_step_launch`; `--ro
 makes it the line).  Each rank
 owns env ids [rank*B, (rank+1)*B) — independent shards, no collective on the data path
 (weak scaling).  Timing: barrier + synchronize on both sides of exactly K steps, max over
-ranks; value = N*B*K / that time.  Rank 0 prints one JSON line.
+ranks; value = N*B*K / that time; ms_per_step = that time / K.  The K steps are whole launches
+and, where K is no multiple of the launch's length, one shorter launch; at most GRAPH_STEPS of
+them are captured in one graph, which a longer window replays (plan_window).  Rank 0 prints one
+JSON line.
 
 Steady state: whatever --warmup asks, at least 2 * max_turns steps run untimed after the
 reset, so the timed window holds the auto-reset mix of the workload (random policy: ~2.4 % of
@@ -59,11 +69,56 @@ CONFIGS = {
 # boundaries: each costs the launch gap, step 0's state loads and the last step's tail)
 C5_SEGMENT = 64
 DEFAULT_ROLLOUT = 64
-# the timed window's floor, whatever --steps asks: at least this many launches of the line's
-# kernel in the captured graph, and graph replays until at least this many seconds are timed
-# (a one-launch window, 0.4 ms, is at the mercy of one launch's jitter)
+# the floor of the windows timed beside the line (--full: time_launches), which take no --steps:
+# at least this many launches of the kernel in the captured graph, and graph replays until at
+# least this many seconds are timed (a one-launch window, 0.4 ms, is at the mercy of one
+# launch's jitter).  The line's own window is exactly --steps steps (plan_window).
 MIN_TIMED_LAUNCHES = 32
 MIN_TIMED_SECONDS = 0.2
+# the line's window: at most this many steps in one captured graph (and in the actions buffer,
+# 64 KiB per step at B = 65536); a longer window replays the graph
+GRAPH_STEPS = 2048
+# --dump-outputs: bytes written at most, all arrays together (float32)
+DUMP_BYTES = 48 << 20
+
+
+def plan_window(steps, steps_per_launch, max_graph_steps=0):
+    """The timed window of exactly `steps` steps as (g, q, r, cap): q replays of a graph of g
+    steps, then one replay of a graph of the r < g steps left over (r == 0: none).  g is at most
+    `cap` steps: `max_graph_steps`, else GRAPH_STEPS or MIN_TIMED_LAUNCHES launches if that is
+    more, in whole launches.  The actions buffer holds `cap` steps after the warm-up."""
+    per = max(1, int(steps_per_launch))
+    cap = window_steps(int(max_graph_steps), per, 1) if max_graph_steps else window_steps(GRAPH_STEPS, per)
+    steps = int(steps)
+    if steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    g = min(steps, cap)
+    q = steps // g
+    return g, q, steps - q * g, cap
+
+
+def dump_outputs(path, outputs, B, rank=0, world=1):
+    """--dump-outputs: write `outputs` {name: (one tensor per env shard, env axis)}, B envs in
+    all, as path/<name>.npy in float32 (a rank of an N-GPU run: <name>_rank<r>.npy).  Where
+    everything together is more than this rank's share of DUMP_BYTES, every array holds the same
+    fixed, seeded sample of the envs (sorted env ids), so two runs with the same arguments write
+    the same entries."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    per_env = sum(sum(t.numel() for t in ts) // B for ts, _ in outputs.values())
+    n = min(B, max(1, DUMP_BYTES // world // (4 * max(1, per_env))))
+    idx = np.arange(B) if n == B else np.sort(np.random.RandomState(0x5EED).choice(B, n, replace=False))
+    for name, (ts, axis) in outputs.items():
+        parts, base = [], 0
+        for t in ts:
+            nb = t.shape[axis]
+            loc = torch.as_tensor(idx[(idx >= base) & (idx < base + nb)] - base, device=t.device)
+            parts.append(t.index_select(axis, loc).to(torch.float32).cpu())
+            base += nb
+        np.save(os.path.join(path, name + suffix + ".npy"), torch.cat(parts, axis).numpy())
 
 
 def window_steps(requested, steps_per_launch, min_launches=MIN_TIMED_LAUNCHES):
@@ -507,11 +562,13 @@ def run_torus(args, dev, rank, world):
     N, R = env.N, env.R
     W = max(args.warmup, 2 * int(env.game_options["max_turns"]))
     W = -(-W // T) * T
-    K = window_steps(args.steps, T)
+    # the window (plan_window): `reps` replays of a graph of G turns, then the `tail` turns left
+    # over; K turns of actions after the warm-up
+    G, reps, tail, K = plan_window(args.steps, T)
     gen = torch.Generator(device=dev)
     gen.manual_seed(1234 + rank)
     actions = torus_actions(W + K, B, NO, NW, NB, dev, gen)
-    obs = torch.empty((T, B, N, R), dtype=torch.uint8, device=dev)
+    obs = torch.zeros((T, B, N, R), dtype=torch.uint8, device=dev)  # (zeros: the records' padding bytes)
     rew = torch.empty((T, B, N), dtype=torch.float32, device=dev)
     done = torch.empty((T, B, N), dtype=torch.uint8, device=dev)
     wr = torch.empty((T, B), dtype=torch.uint8, device=dev)
@@ -521,40 +578,38 @@ def run_torus(args, dev, rank, world):
 
     def run(t0, n, stream):
         s = ctypes.c_void_p(stream.cuda_stream)
-        for t in range(t0, t0 + n, T):
-            _lib.check2(L.wab2_rollout(h, a0 + t * B * N, T, o0, r0, d0, w0, s), "wab2_rollout")
+        for t in range(t0, t0 + n, T):  # (the last launch shorter where n is no multiple of T)
+            _lib.check2(L.wab2_rollout(h, a0 + t * B * N, min(T, t0 + n - t), o0, r0, d0, w0, s), "wab2_rollout")
 
     stream = torch.cuda.current_stream(dev)
     env.reset_environment()
     run(0, W, stream)
     torch.cuda.synchronize(dev)
-    graph = None
+    parts = [n for n in (G, tail) if n > 0]
+    graphs = []
     if args.mode == "graph":
-        graph = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream(dev)
-        side.wait_stream(stream)
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(graph, stream=side):
-                run(W, K, torch.cuda.current_stream(dev))
-        stream.wait_stream(side)
-        torch.cuda.synchronize(dev)
+        for n in parts:
+            g = torch.cuda.CUDAGraph()
+            side.wait_stream(stream)
+            with torch.cuda.stream(side):
+                with torch.cuda.graph(g, stream=side):
+                    run(W, n, torch.cuda.current_stream(dev))
+            stream.wait_stream(side)
+            torch.cuda.synchronize(dev)
+            graphs.append(g)
         env.reset_environment()  # the capture did not execute the turns: rewind
         run(0, W, stream)
         torch.cuda.synchronize(dev)
 
-    def replay_once():
-        if graph is not None:
-            graph.replay()
+    def replay(j):
+        if graphs:
+            graphs[j].replay()
         else:
-            run(W, K, stream)
-    c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    c0.record(stream)
-    replay_once()
-    c1.record(stream)
+            run(W, parts[j], stream)
+    for j in range(len(parts)):  # untimed: a graph's first launch carries its upload
+        replay(j)
     torch.cuda.synchronize(dev)
-    reps = window_replays(c0.elapsed_time(c1) * 1e-3)
-    if world > 1:
-        reps = int(max_over_ranks(reps))
     cb = env.counters()
     if world > 1:
         dist.barrier()
@@ -564,7 +619,9 @@ def run_torus(args, dev, rank, world):
     with CLOCK:
         ev0.record(stream)
         for _ in range(reps):
-            replay_once()
+            replay(0)
+        if tail:
+            replay(1)
         ev1.record(stream)
         torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t_wall
@@ -574,7 +631,11 @@ def run_torus(args, dev, rank, world):
         dist.barrier()
     elapsed = max_over_ranks(stream_ms * 1e-3)
     ca = env.counters()
-    steps = K * reps
+    steps = G * reps + tail  # (= --steps)
+    if args.dump_outputs:  # the last launch's records, reward, done and world resets
+        tt = (tail or G) % T or T
+        dump_outputs(args.dump_outputs, {"obs": ([obs[:tt]], 1), "reward": ([rew[:tt]], 1), "done": ([done[:tt]], 1),
+                                         "world_reset": ([wr[:tt]], 1)}, B, rank, world)
     kern_ms = stream_ms / steps  # per turn (launch / T)
     alg = torus_alg_bytes(NO, NW, NB, T)
     # the per-step surface beside it: one wab2_step launch per turn, records into a 32-slot ring
@@ -620,9 +681,9 @@ def run_torus(args, dev, rank, world):
                                 "alg_bytes_per_env_step": round(ps_alg, 3),
                                 "frac": round(ps_alg * B / (ps_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
             "timed_window": {"turns": ca["turns"] - cb["turns"], "resets": ca["resets"] - cb["resets"],
-                             "graph_steps": K, "graph_replays": reps, "launches": steps // T,
-                             "stream_ms": round(stream_ms, 3), "wall_ms": round(wall * 1e3, 3),
-                             "floor": {"min_launches": MIN_TIMED_LAUNCHES, "min_seconds": MIN_TIMED_SECONDS}},
+                             "graph_steps": G, "graph_replays": reps, "tail_steps": tail,
+                             "launches": reps * -(-G // T) + -(-tail // T),
+                             "stream_ms": round(stream_ms, 3), "wall_ms": round(wall * 1e3, 3)},
             "warmup_effective": W,
             "devices": sorted({r["pci"] for r in per_rank}),
             "sclk_mhz": line_sclk,
@@ -833,6 +894,13 @@ def main():
                     help="per-step launches: N > 0 writes step t's obs, reward and done into slot t %% N of "
                          "[N, B] buffers (the stores then reach HBM, as a rollout's do) instead of one "
                          "[B] buffer rewritten every step (which a 256 MB Infinity Cache can absorb)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the line: the diagnostic launches, the other "
+                         "configs' lines (configs key) and the CPU baselines; a plain run times the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed launch returned (the last step's "
+                         "buffers of a per-step run) as DIR/<name>.npy, float32; above %d MiB in all, a fixed "
+                         "seeded sample of the envs (ranks of an N-GPU run: <name>_rank<r>.npy)" % (DUMP_BYTES >> 20))
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--stream-shards", type=int, default=2,
@@ -857,6 +925,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if not args.full:  # a plain run: the line only
+        args.no_diag = args.no_extra = args.no_cpu = True
     if args.policy == "mlp" and args.config != "c5":
         raise SystemExit("bench.py: --policy mlp needs --config c5 (the policy reads the features)")
     if args.rollout < 0:
@@ -915,19 +987,19 @@ def main():
         desc = desc % seg
         per_launch_steps = seg if c5_roll else 1
         W = max(seg, -(-W // seg) * seg)
-        if args.policy == "mlp":
-            # closed loop: ~16 graph nodes per step (the policy's kernels and the env launch), so
-            # the captured graph holds 2-4 segments and replays make up the timed window
-            K = min(window_steps(K, seg, 2), 4 * seg)
-        else:
-            K = window_steps(K, seg, MIN_TIMED_LAUNCHES if c5_roll else MIN_TIMED_LAUNCHES * seg)
+        # closed loop: ~16 graph nodes per step (the policy's kernels and the env launch), so
+        # the captured graph holds at most 4 segments and replays make up the timed window
+        plan = plan_window(K, seg, 4 * seg if args.policy == "mlp" else 0)
     elif rollout:
         per_launch_steps = args.rollout
         W = -(-W // args.rollout) * args.rollout
-        K = window_steps(K, args.rollout)
+        plan = plan_window(K, args.rollout)
     else:
         per_launch_steps = 1
-        K = window_steps(K, 1)
+        plan = plan_window(K, 1)
+    # the window: `reps` replays of a graph of G steps and one of a graph of the `tail` steps left
+    # over; K: the steps of actions after the warm-up (the diagnostic launches index them too)
+    G, reps, tail, K = plan
     env.reset()
     gen = torch.Generator(device=dev)
     gen.manual_seed(1234 + rank)
@@ -953,14 +1025,15 @@ def main():
     shard_streams = [torch.cuda.Stream(dev) for _ in range(S - 1)]
 
     def shard_chains(t0, n, T, stream, launch):
-        """launch(k, t, hip_stream) for every T-step launch t in [t0, t0 + n) of every shard k,
-        shard 0 on `stream`, the others on their own streams forked from it and joined back"""
+        """launch(k, t, hip_stream, steps) for every T-step launch t in [t0, t0 + n) of every shard
+        k (the last one shorter where n is no multiple of T), shard 0 on `stream`, the others on
+        their own streams forked from it and joined back"""
         subs = [stream] + shard_streams
         for st in shard_streams:
             st.wait_stream(stream)
         for t in range(t0, t0 + n, T):
             for k, st in enumerate(subs):
-                launch(k, t, ctypes.c_void_p(st.cuda_stream))
+                launch(k, t, ctypes.c_void_p(st.cuda_stream), min(T, t0 + n - t))
         for st in shard_streams:
             stream.wait_stream(st)
     if c5:
@@ -969,7 +1042,7 @@ def main():
         feats = torch.zeros((T, B, F), dtype=torch.float32, device=dev)
         seg_rew = torch.zeros((T, B), dtype=torch.float32, device=dev)
         seg_done = torch.zeros((T, B), dtype=torch.uint8, device=dev)
-        seg_ret = torch.empty((T, B), dtype=torch.float32, device=dev)
+        seg_ret = torch.zeros((T, B), dtype=torch.float32, device=dev)
         f0, r0, d0, ret0 = feats.data_ptr(), seg_rew.data_ptr(), seg_done.data_ptr(), seg_ret.data_ptr()
         fused = not args.c5_unfused
         # the wrapped env of actor_critic.py returns features only: the fused call renders the
@@ -1014,15 +1087,15 @@ def main():
                                    "wab_discounted_returns_exact")
                 return
             if c5_roll and S > 1:  # the shards' segments on their streams
-                shard_chains(t0, n, T, stream, lambda k, t, sk: _lib.check(L.wab_rollout_features(
-                    shard_envs[k]._h, shard_actions[k].data_ptr() + t * Bs, T, ctypes.addressof(c5_shard[k][0]),
+                shard_chains(t0, n, T, stream, lambda k, t, sk, tt: _lib.check(L.wab_rollout_features(
+                    shard_envs[k]._h, shard_actions[k].data_ptr() + t * Bs, tt, ctypes.addressof(c5_shard[k][0]),
                     c5_shard[k][1].data_ptr(), c5_shard[k][2].data_ptr(), c5_shard[k][3].data_ptr(), 0.99, None,
                     c5_shard[k][4].data_ptr(), sk), "wab_rollout_features"))
                 return
             if c5_roll:  # one launch per segment: T fused steps and the segment's returns
                 for t in range(t0, t0 + n, T):
-                    _lib.check(L.wab_rollout_features(h, a0 + t * B, T, rseq_addr, r0, d0, f0, 0.99, None, ret0, s),
-                               "wab_rollout_features")
+                    _lib.check(L.wab_rollout_features(h, a0 + t * B, min(T, t0 + n - t), rseq_addr, r0, d0, f0,
+                                                      0.99, None, ret0, s), "wab_rollout_features")
                 return
             for t in range(t0, t0 + n):
                 i = t % T
@@ -1030,6 +1103,18 @@ def main():
                 if i == T - 1:
                     _lib.check(L.wab_discounted_returns_exact(h, r0, d0, T, B, 0.99, None, ret0, s),
                                "wab_discounted_returns_exact")
+
+        def last_outputs(n):
+            """--dump-outputs: the last launch's buffers, the window's last graph holding n steps
+            (per-step launches: the segment buffers as they stand after the last step)"""
+            if not c5_roll:
+                return {"features": ([feats], 1), "reward": ([seg_rew], 1), "done": ([seg_done], 1),
+                        "returns": ([seg_ret], 1)}
+            tt = n % T or T
+            sh = c5_shard if S > 1 else [(None, seg_rew, seg_done, feats, seg_ret, seg_scal)]
+            return {"features": ([c[3][:tt] for c in sh], 1), "scalars": ([c[5][:, :tt] for c in sh], 2),
+                    "reward": ([c[1][:tt] for c in sh], 1), "done": ([c[2][:tt] for c in sh], 1),
+                    "returns": ([c[4][:tt] for c in sh], 1)}
     elif rollout:
         T = args.rollout
         if S == 1:
@@ -1044,11 +1129,18 @@ def main():
             shard_bufs.append((e._h, shard_actions[k].data_ptr(), o, pl, sc, rw, dn))
 
         def run(t0, n, stream):
-            def launch(k, t, sk):
+            def launch(k, t, sk, tt):
                 hk, ak, o, pl, sc, rw, dn = shard_bufs[k]
-                _lib.check(L.wab_rollout(hk, ak + t * Bs, T, ctypes.addressof(o), rw.data_ptr(), dn.data_ptr(), sk),
+                _lib.check(L.wab_rollout(hk, ak + t * Bs, tt, ctypes.addressof(o), rw.data_ptr(), dn.data_ptr(), sk),
                            "wab_rollout")
             shard_chains(t0, n, T, stream, launch)
+
+        def last_outputs(n):
+            """--dump-outputs: the last launch's rollout buffers (its steps' obs, reward, done), the
+            window's last graph holding n steps"""
+            tt = n % T or T
+            return {"planes": ([b[3][:tt] for b in shard_bufs], 1), "scalars": ([b[4][:, :tt] for b in shard_bufs], 2),
+                    "reward": ([b[5][:tt] for b in shard_bufs], 1), "done": ([b[6][:tt] for b in shard_bufs], 1)}
     elif args.obs_ring > 0:
         N = args.obs_ring
         ring_planes = torch.empty((N, B, 3, env.W, env.S), dtype=torch.uint8, device=dev)
@@ -1067,6 +1159,12 @@ def main():
                 rc = L.wab_step(h, a0 + t * B, slot_addr[i], ring_rew[i].data_ptr(), ring_done[i].data_ptr(), None, s)
                 if rc:
                     _lib.check(rc, "wab_step")
+
+        def last_outputs(n):
+            """--dump-outputs: the ring slot the window's last step wrote"""
+            i = (W + n - 1) % N
+            return {"planes": ([ring_planes[i]], 0), "scalars": ([ring_scal[:, i]], 1),
+                    "reward": ([ring_rew[i]], 0), "done": ([ring_done[i]], 0)}
     else:
         def run(t0, n, stream):
             s = ctypes.c_void_p(stream.cuda_stream)
@@ -1075,21 +1173,31 @@ def main():
                 if rc:
                     _lib.check(rc, "wab_step")
 
+        def last_outputs(n):
+            """--dump-outputs: the env's obs, reward and done buffers after the window's last step"""
+            return {"planes": ([env._obs["planes"]], 0), "scalars": ([env._obs["scalars"]], 1),
+                    "reward": ([env.reward], 0), "done": ([env.done], 0)}
+
     stream = torch.cuda.current_stream(dev)
     run(0, W, stream)
     torch.cuda.synchronize(dev)
     print("bench.py: %d warm-up steps done" % W, file=sys.stderr, flush=True)
-    graph = None
+    # the window's graphs: G steps (replayed `reps` times) and the `tail` steps left over, both
+    # from the first step after the warm-up
+    parts = [n for n in (G, tail) if n > 0]
+    graphs = []
     if args.mode == "graph":
-        graph = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream(dev)
-        side.wait_stream(stream)
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(graph, stream=side):
-                run(W, K, torch.cuda.current_stream(dev))
-        stream.wait_stream(side)
-        torch.cuda.synchronize(dev)
-        print("bench.py: %d steps captured" % K, file=sys.stderr, flush=True)
+        for n in parts:
+            g = torch.cuda.CUDAGraph()
+            side.wait_stream(stream)
+            with torch.cuda.stream(side):
+                with torch.cuda.graph(g, stream=side):
+                    run(W, n, torch.cuda.current_stream(dev))
+            stream.wait_stream(side)
+            torch.cuda.synchronize(dev)
+            graphs.append(g)
+        print("bench.py: %s steps captured" % " + ".join(str(n) for n in parts), file=sys.stderr, flush=True)
         # the capture itself did not execute the steps; rewind state by a fresh reset
         env.reset()
         if S > 1:
@@ -1098,23 +1206,18 @@ def main():
         run(0, W, stream)
         torch.cuda.synchronize(dev)
 
-    def replay_once():
-        if graph is not None:
-            graph.replay()
+    def replay(j):
+        if graphs:
+            graphs[j].replay()
         else:
-            run(W, K, stream)
+            run(W, parts[j], stream)
 
-    # calibration (untimed): one replay of the window's K steps sizes the replay count
-    c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    c0.record(stream)
-    replay_once()
-    c1.record(stream)
+    # untimed: one replay of each graph (a graph's first launch carries its upload)
+    for j in range(len(parts)):
+        replay(j)
     torch.cuda.synchronize(dev)
-    reps = window_replays(c0.elapsed_time(c1) * 1e-3)
-    if world > 1:  # every rank times the same number of steps
-        reps = int(max_over_ranks(reps))
 
-    timed_envs = shard_envs if (rollout or c5_roll) else [env]
+    timed_envs =shard_envs if (rollout or c5_roll) else [env]
 
     def workload_counters():
         out = {}
@@ -1131,7 +1234,9 @@ def main():
     with CLOCK:  # (a host thread reading sysfs: nothing on the device's path)
         ev0.record(stream)
         for _ in range(reps):
-            replay_once()
+            replay(0)
+        if tail:
+            replay(1)
         ev1.record(stream)
         torch.cuda.synchronize(dev)
     wall_rank = time.perf_counter() - t0
@@ -1143,15 +1248,16 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = max_over_ranks(elapsed_rank)
-    K_req, K = K, K * reps  # steps in the graph; steps timed
+    K_req, K = K, G * reps + tail  # steps of actions after the warm-up; steps timed (= --steps)
     c_after = workload_counters()
+    if args.dump_outputs:  # (before the diagnostic launches below, which write the env's buffers)
+        dump_outputs(args.dump_outputs, last_outputs(tail or G), B, rank, world)
     window = {"env_steps": c_after["steps"] - c_before["steps"],
               "resets": c_after["resets"] - c_before["resets"],
-              "graph_steps": K_req, "graph_replays": reps,
-              "launches": K // per_launch_steps,
+              "graph_steps": G, "graph_replays": reps, "tail_steps": tail,
+              "launches": reps * -(-G // per_launch_steps) + -(-tail // per_launch_steps),
               "stream_ms": round(stream_ms, 3), "wall_ms": round(wall_rank * 1e3, 3)}
     window["resets_per_env_step"] = round(window["resets"] / max(1, window["env_steps"]), 5)
-    window["floor"] = {"min_launches": MIN_TIMED_LAUNCHES, "min_seconds": MIN_TIMED_SECONDS}
 
     # kernel duration: the HIP events around the timed region on the launch stream give the
     # average per launch (back-to-back graph launches: kernel time plus the launch gap, the

@@ -9,7 +9,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 bash tools/gpu_steps.sh "$out" tests smoke bench bench:wide31 bench:c5 bench:torus mlp ring
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29517 bench.py --gpus 2 --share-gpu --steps 20 > "$out/bench_n2_share.log" 2>&1 \
+  --master-port 29517 bench.py --full --gpus 2 --share-gpu --steps 20 > "$out/bench_n2_share.log" 2>&1 \
   || { tail -30 "$out/bench_n2_share.log"; exit 1; }
 tail -c 800 "$out/bench_n2_share.log"
 for m in 200 1600; do

@@ -3,9 +3,9 @@
 # that the first failure ends the call:  tools/gpu_steps.sh OUT_DIR STEP [STEP ...]
 #   tests         the whole -m gpu suite (one process)
 #   tests:EXPR    the -m gpu tests matching -k EXPR
-#   bench         bench.py default line (the driver's command, --steps 20)
-#   bench:CONFIG  bench.py --config CONFIG
-#   mlp           bench.py --config c5 --policy mlp (closed loop)
+#   bench         bench.py --full default line (--steps 20: the line, its diagnostics, configs and CPU baselines)
+#   bench:CONFIG  bench.py --full --config CONFIG
+#   mlp           bench.py --full --config c5 --policy mlp (closed loop)
 #   ring          the per-step launch into a 32-slot obs ring (default and wide31)
 #   stamps:ARGS   tools/phase_stamps.py --no-build ARGS (comma-separated)
 #   prof:CONFIG   rocprofv3 --kernel-trace --stats of bench.py --config CONFIG
@@ -24,14 +24,14 @@ for s in "$@"; do
       tail -3 "$out/$tag.log" ;;
     bench)
       cfg=${arg:-default}
-      timeout -k 10 400 python bench.py --config "$cfg" $( [ -z "$arg" ] && echo --steps 20 ) > "$out/bench_$cfg.log" 2>&1 || { tail -30 "$out/bench_$cfg.log"; exit 1; }
+      timeout -k 10 400 python bench.py --full --config "$cfg" $( [ -z "$arg" ] && echo --steps 20 ) > "$out/bench_$cfg.log" 2>&1 || { tail -30 "$out/bench_$cfg.log"; exit 1; }
       tail -c 600 "$out/bench_$cfg.log" ;;
     mlp)
-      timeout -k 10 400 python bench.py --config c5 --policy mlp --no-cpu > "$out/bench_c5_mlp.log" 2>&1 || { tail -30 "$out/bench_c5_mlp.log"; exit 1; }
+      timeout -k 10 400 python bench.py --full --config c5 --policy mlp --no-cpu > "$out/bench_c5_mlp.log" 2>&1 || { tail -30 "$out/bench_c5_mlp.log"; exit 1; }
       tail -c 600 "$out/bench_c5_mlp.log" ;;
     ring)
       for cfg in default wide31; do
-        timeout -k 10 300 python bench.py --config $cfg --rollout 0 --obs-ring 32 --no-cpu > "$out/bench_${cfg}_ring.log" 2>&1 || { tail -30 "$out/bench_${cfg}_ring.log"; exit 1; }
+        timeout -k 10 300 python bench.py --full --config $cfg --rollout 0 --obs-ring 32 --no-cpu > "$out/bench_${cfg}_ring.log" 2>&1 || { tail -30 "$out/bench_${cfg}_ring.log"; exit 1; }
         tail -c 300 "$out/bench_${cfg}_ring.log"
       done ;;
     stamps)
@@ -39,7 +39,7 @@ for s in "$@"; do
       cat "$out/stamps_${arg//[ ,-]/_}.log" ;;
     prof)
       cfg=${arg:-default}
-      timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof_$cfg" -o run -- python3 bench.py --config "$cfg" --no-cpu > "$out/prof_$cfg.log" 2>&1 || { tail -30 "$out/prof_$cfg.log"; exit 1; }
+      timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof_$cfg" -o run -- python3 bench.py --full --config "$cfg" --no-cpu > "$out/prof_$cfg.log" 2>&1 || { tail -30 "$out/prof_$cfg.log"; exit 1; }
       find "$out/prof_$cfg" -name '*kernel_stats.csv' | head -1 | xargs -I{} cp {} "$out/prof_$cfg/kernel_stats.csv"
       head -5 "$out/prof_$cfg/kernel_stats.csv" ;;
     smoke)
