@@ -5,6 +5,12 @@ eliminated; not a runnable build) and counts VALU / SALU / LDS / VMEM instructio
 default-geometry kernel wab_step_small<8, 11, false, false>, plus the store-only remainder (k = 9).
 Loops count once, so this ranks the straight-line cost of each wave's step, the part a
 PMC run cannot split by wave.  Usage: python tools/isa_count.py [extra hipcc flags]
+
+--roll-store [extra hipcc flags]: the rollout instance wab_step_small<8, 11, false, true>, waves
+W0 and W2: static counts of each obs store region, from a region's first stream read
+(ds_read_u16) to its last 16-byte global store.  A region is `general` (per-unit masked, the
+partial-group path: it clears with ds_write_b16) or `whole` (store_units_whole11: ds_write_b128
+clears); 11-12 stores = a step's store_units_nt, 5-6 = the last step's store_units_of.
 """
 import os
 import re
@@ -14,6 +20,64 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(REPO, "wab_gym_amd", "csrc", "wab_step_small.hip")
 KERNEL = os.environ.get("ISA_KERNEL", "_ZN3wab14wab_step_smallILi8ELi11ELb0ELb0EEEvNS_6ParamsE")
+
+
+ROLL_KERNEL = "_ZN3wab14wab_step_smallILi8ELi11ELb0ELb1EEEvNS_6ParamsE"
+
+
+def listing(flags, kernel):
+    out = "/tmp/isa_count.s"
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-DWAB_DIAGNOSTIC_BUILD",
+                           "--cuda-device-only", "-S", SRC, "-o", out] + flags, stderr=subprocess.DEVNULL)
+    s = open(out).read()
+    a = s.index(kernel + ":")
+    ops = []
+    for line in s[a:s.index(".Lfunc_end", a)].splitlines():
+        m = re.match(r"\s+([a-z_0-9]+)(.*)", line)
+        if m:
+            ops.append((m.group(1), m.group(2)))
+    return ops
+
+
+def store_regions(ops):
+    """[first ds_read_u16 .. last global_store_dwordx4] spans: a new span starts at a stream
+    read that follows a store (every path issues its reads before its first store)."""
+    spans, start, last_store = [], None, None
+    for i, (op, _) in enumerate(ops):
+        if op == "ds_read_u16":
+            if start is None or last_store is not None:
+                if start is not None:
+                    spans.append((start, last_store))
+                start, last_store = i, None
+        elif op in ("global_store_dwordx4", "flat_store_dwordx4") and start is not None:
+            last_store = i
+        elif op == "s_barrier" and start is not None:
+            if last_store is not None:
+                spans.append((start, last_store))
+            start, last_store = None, None
+    if start is not None and last_store is not None:
+        spans.append((start, last_store))
+    rows = []
+    for a, b in spans:
+        c = {"kind": "general", "stores": 0, "valu": 0, "salu": 0, "branch": 0, "exec_branch": 0, "waitcnt": 0, "lds": 0}
+        for op, rest in ops[a:b + 1]:
+            if op.startswith("v_"):
+                c["valu"] += 1
+            elif op.startswith("ds_"):
+                c["lds"] += 1
+                if op == "ds_write_b128":
+                    c["kind"] = "whole"
+            elif op.endswith("store_dwordx4"):
+                c["stores"] += 1
+            elif op.startswith("s_cbranch"):
+                c["branch"] += 1
+                c["exec_branch"] += op.startswith("s_cbranch_exec")
+            elif op == "s_waitcnt":
+                c["waitcnt"] += 1
+            elif op.startswith("s_") and op not in ("s_nop", "s_barrier"):
+                c["salu"] += 1
+        rows.append(c)
+    return rows
 
 
 def counts(flags):
@@ -42,5 +106,10 @@ def counts(flags):
 
 if __name__ == "__main__":
     extra = sys.argv[1:]
+    if extra and extra[0] == "--roll-store":
+        for k in (0, 2):
+            for c in store_regions(listing(["-DWAB_ONLY_WAVE=%d" % k] + extra[1:], ROLL_KERNEL)):
+                print("W%d %s" % (k, c))
+        sys.exit(0)
     for k, name in ((0, "W0 bushes"), (1, "W1 draws"), (2, "W2 wolves"), (3, "W3 ring"), (9, "stores only")):
         print("%-12s %s" % (name, counts(["-DWAB_ONLY_WAVE=%d" % k] + extra)))

@@ -405,10 +405,82 @@ __device__ __forceinline__ void render_s(const Params& p, const Lds& s, int lane
 // each unit after its read so the stream can be rendered into again.  (Measured and not
 // adopted: the store instructions aligned to absolute 128-byte lines, plain stores, the units
 // in smaller read/clear/store batches; the obs stores split over W0, W2 and W3.)
-template <int NT, int NK>
-__device__ __forceinline__ void store_units_nt(const Params& p, uint8_t* planes, uint32_t* stream, int idx) {
+//
+// A whole group (64 envs) of the G = 11 geometry has 64 * 363 / 16 = 1452 units, a constant:
+// which of a wave's units exist is then known at compile time, all but the last index (wave
+// W0 of store_units_nt<128, 12>: k <= 10 for every lane, k = 11 for lanes < 44; W2, lanes 64..
+// 127: k <= 10 only).  store_units_whole11 is that case as straight-line code (the general
+// path below tests `u < full` per lane and unit, which compiles to one exec-masked branch
+// region per unit in each of its three loops): thread I0 + lane stores units I0 + lane + NT *
+// k, k in [K0, K1); all reads first, then the clears, then the expansions and stores, of which
+// only the last index's is masked.  The wave's units of one k are 128 contiguous bytes of the
+// stream: it clears its share with 16-byte writes (lane = 8 * k' + chunk), after its reads
+// (LDS operations of one wave retire in order).  A lane whose chunk lies past the wave's
+// share writes the share's last chunk once more instead of being masked; the share ends at
+// the stream's 2904 bytes rounded up to 2912, inside stream_words.  The store addresses are
+// a scalar base, advanced by whole 4 KiB, plus the lane's 32-bit offset and an immediate.
+#ifndef WAB_STORE_WHOLE  // (tuning A/B: 0 = whole groups take the general path too)
+#define WAB_STORE_WHOLE 1
+#endif
+constexpr uint32_t kUnits11 = 64u * 363u / 16u;
+template <int NT, int K0, int K1, int I0>
+__device__ __forceinline__ void store_units_whole11(uint8_t* out, uint32_t* stream, int lane) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  typedef u32x4 __attribute__((may_alias)) u32x4_any;  // (the clears overwrite what s16 reads)
+  static_assert(I0 % 64 == 0 && NT % 64 == 0, "a wave's units of one k are contiguous");
+  static_assert((uint32_t)(I0 + NT * K0) < kUnits11, "the wave has a unit");
+  const uint16_t* s16 = reinterpret_cast<const uint16_t*>(stream) + I0;
+  uint32_t v[K1 - K0];
+  uint32_t share_end = 0u;  // (bytes; a constant once unrolled)
+#pragma unroll
+  for (int k = K0; k < K1; ++k) {
+    const uint32_t u0 = (uint32_t)(I0 + NT * k);
+    if (u0 + 63u < kUnits11) v[k - K0] = (uint32_t)s16[lane + NT * k];
+    else if (u0 < kUnits11) v[k - K0] = (uint32_t)s16[min((uint32_t)lane, kUnits11 - 1u - u0) + NT * k];  // (tail lanes: unused)
+    else v[k - K0] = 0u;
+    if (u0 < kUnits11) share_end = min((u0 + 64u) * 2u, (kUnits11 * 2u + 15u) & ~15u);
+  }
+#pragma unroll
+  for (int i = 0; i < (K1 - K0 + 7) / 8; ++i) {
+    const uint32_t k = (uint32_t)(K0 + 8 * i) + ((uint32_t)lane >> 3);
+    const uint32_t byte = ((uint32_t)I0 + (uint32_t)NT * k) * 2u + 16u * ((uint32_t)lane & 7u);
+    *reinterpret_cast<u32x4_any*>(reinterpret_cast<uint8_t*>(stream) + min(byte, share_end - 16u)) = u32x4{0u, 0u, 0u, 0u};
+  }
+  if (!out) return;  // (wab_rollout_features without planes: the stream is only cleared)
+  typedef uint8_t __attribute__((address_space(1))) g_u8;  // (global, so the stores keep their scalar-base form)
+  typedef u32x4 __attribute__((address_space(1))) g_u32x4;
+  g_u8* base = (g_u8*)out;
+  uint32_t base_off = 0u;
+#pragma unroll
+  for (int k = K0; k < K1; ++k) {
+    const uint32_t u0 = (uint32_t)(I0 + NT * k);
+    if (u0 >= kUnits11) continue;
+    const uint32_t adv = ((uint32_t)(NT * k) * 16u - base_off) & ~4095u;
+    if (adv) {
+      base += adv;
+      base_off += adv;
+      asm("" : "+s"(base));  // (kept scalar: not re-associated into 64-bit per-lane adds)
+    }
+    if (u0 + 63u >= kUnits11 && u0 + (uint32_t)lane >= kUnits11) continue;  // the one masked unit
+    u32x4 q;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) q[b] = (((v[k - K0] >> (4 * b)) & 0xFu) * 0x00204081u) & 0x01010101u;
+    g_u32x4* dst = (g_u32x4*)base + (uint32_t)(I0 + lane + NT * k - (int)(base_off / 16u));
+    if (WAB_ROLL_OBS_NT) __builtin_nontemporal_store(q, dst);
+    else *dst = q;
+  }
+}
+
+// (G != 11, runtime geometry: the unit count is a scalar; those instances stay on the general path.)
+template <int G, int NT, int NK, int I0>
+__device__ __forceinline__ void store_units_nt(const Params& p, uint8_t* planes, uint32_t* stream, int lane) {
   const int64_t g0 = (int64_t)blockIdx.x * 64;
   const uint32_t OB = (uint32_t)p.OB;
+  if (WAB_STORE_WHOLE && G == 11 && p.B - g0 >= 64) {  // (uniform)
+    store_units_whole11<NT, 0, NK, I0>(planes ? planes + (size_t)g0 * OB : nullptr, stream, lane);
+    return;
+  }
+  const int idx = I0 + lane;
   const uint32_t full = ((uint32_t)min((int64_t)64, p.B - g0) * OB) >> 4;
   uint8_t* out = planes + (size_t)g0 * OB;
   uint16_t* s16 = reinterpret_cast<uint16_t*>(stream);
@@ -439,7 +511,9 @@ __device__ __forceinline__ void store_units_nt(const Params& p, uint8_t* planes,
 
 // Multi-step launches store step t's obs during step t + 1 (streams alternate), by W0 and W2 in
 // their slack before B2 (W1 and W3 never store).  Diagnostic build -DWAB_ROLL_FLOOR=1: every
-// step's work skipped, its obs stores kept (the store pattern's own floor; results wrong by design)
+// step's work skipped, its obs stores kept: W0 and W2 make the product's store_units_nt call
+// between the step's two barriers, the last step's store_units_of stays (the store pattern's
+// own floor; results wrong by design)
 #ifndef WAB_ROLL_FLOOR
 #define WAB_ROLL_FLOOR 0
 #endif
@@ -879,7 +953,7 @@ __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const
   count_steps(p);
   const unsigned long long jm = __ballot(job);
   if (lane == 0 && jm) atomicAdd(&p.block_resets[blockIdx.x], (unsigned long long)__popcll(jm));  // (no-return: a load here would wait for the stores)
-  if (ROLL && carry->prev_stream) store_units_nt<128, 12>(p, carry->prev_planes, carry->prev_stream, lane);
+  if (ROLL && carry->prev_stream) store_units_nt<G, 128, 12, 0>(p, carry->prev_planes, carry->prev_stream, lane);
   SMALL_STAMP(4);
   lds_barrier();  // B2: S rendered (done envs too when their terminal obs is asked for)
   if (!ROLL && p.t_planes) {  // (terminal obs: per-step launches only)
@@ -1197,7 +1271,7 @@ __device__ __forceinline__ unsigned long long wolves_wave(const Params& p, const
   }
   if (wolf_of) atomicAdd(&p.counters[CTR_WOLF_OVERFLOW], wolf_of);
   const unsigned long long jm = __ballot(job);
-  if (ROLL && carry->prev_stream) store_units_nt<128, 12>(p, carry->prev_planes, carry->prev_stream, 64 + lane);
+  if (ROLL && carry->prev_stream) store_units_nt<G, 128, 12, 64>(p, carry->prev_planes, carry->prev_stream, lane);
   SMALL_STAMP(19);
   lds_barrier();  // B2
   if (!ROLL && p.t_planes) lds_barrier();  // B3
@@ -1346,10 +1420,17 @@ __device__ __forceinline__ unsigned long long ring_wave(const Params& p, const S
 // Multi-step launches: units [K0, K1) of the six per thread of a finished step's stream (p its
 // step's slice), each cleared after its read (the last step's obs, stored at its end).  No
 // partial tail: a multi-step launch needs B * OB % 16 == 0 (wab_rollout).
-template <int K0, int K1>
-__device__ __forceinline__ void store_units_of(const Params& p, uint32_t* stream, int tid) {
+// A whole G = 11 group takes store_units_whole11 (wave WAVE's threads: k <= 4 unmasked, k = 5
+// for threads < 172).
+template <int G, int K0, int K1, int WAVE>
+__device__ __forceinline__ void store_units_of(const Params& p, uint32_t* stream, int lane) {
   const int64_t g0 = (int64_t)blockIdx.x * 64;
   const uint32_t OB = (uint32_t)p.OB;
+  if (WAB_STORE_WHOLE && G == 11 && p.B - g0 >= 64) {  // (uniform)
+    store_units_whole11<256, K0, K1, 64 * WAVE>(p.planes + (size_t)g0 * OB, stream, lane);
+    return;
+  }
+  const int tid = 64 * WAVE + lane;
   const uint32_t full = ((uint32_t)min((int64_t)64, p.B - g0) * OB) >> 4;
   uint8_t* out = p.planes + (size_t)g0 * OB;
   uint16_t* s16 = reinterpret_cast<uint16_t*>(stream);
@@ -1622,6 +1703,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
       c.prev_stream = t > 0 ? lds + ((t & 1) ? L0.stream : L0.stream2) : nullptr;           \
       if (WAB_ROLL_FLOOR) {  /* diagnostic floor: the stores alone (results wrong by design) */ \
         lds_barrier();                                                                       \
+        if constexpr (kWave == 0 || kWave == 2) {  /* the product's call, W0 and W2 */        \
+          if (c.prev_stream) store_units_nt<G, 128, 12, 32 * kWave>(p, c.prev_planes, c.prev_stream, lane); \
+        }                                                                                    \
         lds_barrier();                                                                       \
       } else {                                                                               \
         __VA_ARGS__;                                                                         \
@@ -1629,12 +1713,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
       if (FEAT) step_features<true>(p, L, lds, wave, lane, t);  /* this step's rows */     \
       if (t == T - 1 && p.planes) {                                                          \
         lds_barrier();                                                                       \
-        store_units_of<0, 6>(p, lds + L.stream, threadIdx.x);                                \
+        store_units_of<G, 0, 6, kWave>(p, lds + L.stream, lane);                               \
       }                                                                                      \
       lds_barrier();                                                                         \
       ROLL_LOOP_STAMP(38, t == T / 2);  /* past the middle step's end barrier */             \
     }
     if (wave == 0) {
+      constexpr int kWave = 0;
       CarryW0 c;
       WAB_ROLL_STEP({
         role_prio<true>(3, t, p.features != nullptr);
@@ -1642,12 +1727,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
         role_prio<true>(0, t, p.features != nullptr);
       })
     } else if (wave == 1) {
+      constexpr int kWave = 1;
       CarryPtr<CarryHdr> c;
       WAB_ROLL_STEP(draws_wave<G, true>(p, L, lds, lane, &c.c, t, t == T - 1))
     } else if (wave == 2) {
+      constexpr int kWave = 2;
       CarryW2<SLOTS> c;
       WAB_ROLL_STEP((wolves_wave<SLOTS, G, true>(p, L, lds, lane, &c, t, t == T - 1)))
     } else {
+      constexpr int kWave = 3;
       CarryPtr<CarryHdr> c;
       WAB_ROLL_STEP((ring_wave<SLOTS, G, true>(p, L, lds, lane, &c.c, t, t == T - 1)))
     }
