@@ -34,6 +34,8 @@
  *                            + gym.spaces.flatten                    actor_critic.py:188
  *   wab_discounted_returns<- finish_episode's return loop             actor_critic.py:139-143
  *   wab_discounted_returns_exact <- the same on the env's own rewards   actor_critic.py:139-145
+ *   wab_snapshot_save / wab_snapshot_restore <- (no counterpart: the reference has no
+ *                            checkpoint, resume or rewind of an env)
  */
 #ifndef WAB_H_
 #define WAB_H_
@@ -45,7 +47,7 @@
 extern "C" {
 #endif
 
-#define WAB_ABI_VERSION 5
+#define WAB_ABI_VERSION 6
 #define WAB_MAX_WOLF_SLOTS 32 /* largest per-env live-wolf slot count (wab_config.wolf_slots) */
 #define WAB_MAX_VIEW 63       /* largest odd width/height accepted */
 
@@ -295,7 +297,8 @@ int wab_render_envs(wab_handle* h, const wab_obs* obs, int64_t first, int64_t co
  * bush exists (wab_env.py:664).  mask (device u8 [B], nullable) limits the envs written.
  * The handle keeps a path of ostrich tiles for this: call it after EVERY wab_reset and
  * wab_step of the envs it observes (turn t's entry is written at turn t); a missing entry
- * counts in wab_counters.ego_missing.  Not valid after wab_rollout. */
+ * counts in wab_counters.ego_missing.  Not valid after wab_rollout, nor after
+ * wab_snapshot_restore (a snapshot does not hold the path). */
 int wab_egocentric(wab_handle* h, const uint8_t* mask, uint8_t* proximity, void* stream);
 
 /* Discounted returns of actor_critic.finish_episode (actor_critic.py:139-143) over a
@@ -314,6 +317,60 @@ int wab_discounted_returns(const float* reward, const uint8_t* done, int32_t T, 
 int wab_discounted_returns_exact(const wab_handle* h, const float* reward, const uint8_t* done, int32_t T,
                                  int64_t B, double gamma, const float* bootstrap, float* returns,
                                  void* stream);
+
+/* ---- snapshots: save and restore env state ---------------------------------------- */
+
+/* A snapshot is one fixed-size record per env, env-major: env k of a snapshot is bytes
+ * [k * R, (k + 1) * R) of `records`, R = wab_snapshot_bytes (a multiple of 16; 480 for the
+ * defaults), so any env range is one contiguous slice.  A record holds everything an episode
+ * needs to continue: the env's header (tile, turn, role / status / counts, episode), its food
+ * (f64), wolf_slots wolf tiles, eaten_capacity eaten-log entries (tiles u32, then berries left
+ * u8) and the bush bitmap of the view (bit i * height + j, after the eat).  It is canonical:
+ * wolf slots, log entries and bitmap bits that are not live are 0, and the layout does not
+ * depend on which step kernel runs the handle (wab_step_kernel), so equal states give equal
+ * bytes and a snapshot moves between handles of any plane_stride.  Every draw is keyed by
+ * (seed, global env id, episode, ...): a record restored into the slot with the same global id
+ * continues bit for bit, in the same handle or another one, of any batch size.
+ * Not in a snapshot: wab_counters (cumulative, left as they are), the caller's observation
+ * buffers (the current observation is taken before the step's eat and spawn, so it cannot be
+ * derived from a record: a caller that rewinds keeps its own copy), and the path of
+ * wab_egocentric, which is not valid after a restore, as it is not after wab_rollout. */
+#define WAB_SNAPSHOT_MAGIC 0x53424157u /* the bytes 'W' 'A' 'B' 'S' */
+#define WAB_SNAPSHOT_VERSION 1u
+typedef struct wab_snapshot_info {   /* host POD, describes a block of records */
+  uint32_t magic, version;           /* WAB_SNAPSHOT_MAGIC, WAB_SNAPSHOT_VERSION */
+  uint64_t config_hash;              /* wab_snapshot_hash of the saving handle's options */
+  uint64_t seed;
+  int64_t env_id_first, count;       /* global ids [first, first + count) */
+  int64_t record_bytes;
+} wab_snapshot_info;
+
+/* R for these options (host only, no device needed); < 0 on options wab_create refuses. */
+int wab_snapshot_bytes(const wab_config* cfg);
+
+/* Hash of what decides how a state continues: every rule field, width, height, autoreset, the
+ * resolved wolf_slots and eaten_capacity and the threshold table (NULL hashes as the table
+ * wab_bush_thresholds gives).  Not plane_stride.  Host only; 0 on options wab_create refuses. */
+uint64_t wab_snapshot_hash(const wab_config* cfg);
+
+/* Write the records of envs [first, first + count) of the handle (indices into the handle) to
+ * `records` (device, 16-byte aligned, count * R bytes) and describe them in `info`
+ * (env_id_first = the handle's env_id_base + first).  One stream-ordered launch: no allocation,
+ * no synchronisation.  WAB_E_STATE before the first wab_reset, WAB_E_INVALID for a range outside
+ * [0, B). */
+int wab_snapshot_save(wab_handle* h, int64_t first, int64_t count, void* records, wab_snapshot_info* info,
+                      void* stream);
+
+/* Env i of the handle, of global id g, takes record g - info->env_id_first when g lies in the
+ * snapshot's id range and mask (device u8 [B], or NULL) is NULL or mask[i] != 0; every other env
+ * is left untouched.  `records` is the snapshot's first record (device, 16-byte aligned).  One
+ * stream-ordered launch; every range is checked on the host first.  WAB_E_INVALID (the message
+ * names the check) when magic, version, config_hash, seed or record_bytes differ from the
+ * handle's, or the two id ranges do not intersect.  A handle that was never reset accepts only a
+ * restore of all its envs with mask = NULL, which then counts as its first wab_reset; any other
+ * restore into it is WAB_E_STATE. */
+int wab_snapshot_restore(wab_handle* h, const wab_snapshot_info* info, const void* records,
+                         const uint8_t* mask, void* stream);
 
 /* Test hook: the bush value (berries, generate_n_bush_values wab_env.py:631-635) the step
  * kernels give the 53-bit draws U[n] under h's threshold table, computed by the kernels' own

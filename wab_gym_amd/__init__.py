@@ -22,6 +22,10 @@ def __getattr__(name):
         from . import egocentric
 
         return getattr(egocentric, name)
+    if name == "EnvSnapshot":
+        from .snapshot import EnvSnapshot
+
+        return EnvSnapshot
     if name == "EpisodeMonitor":
         from .monitor import EpisodeMonitor
 
@@ -33,4 +37,5 @@ def __getattr__(name):
     raise AttributeError(name)
 
 
-__all__ = ["BatchedWolvesAndBushesEnv", "default_game_options", "make_config", "bush_thresholds"]
+__all__ = ["BatchedWolvesAndBushesEnv", "EnvSnapshot", "default_game_options", "make_config",
+           "bush_thresholds"]

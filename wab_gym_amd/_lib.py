@@ -19,6 +19,7 @@ EXPORTED = [
     "wab_superbasic_dim", "wab_featurize_superbasic", "wab_render", "wab_egocentric",
     "wab_debug_bush_values", "wab_step_features", "wab_discounted_returns_exact",
     "wab_bush_thresholds", "wab_rollout_features", "wab_render_envs", "wab_set_obs_placement",
+    "wab_snapshot_bytes", "wab_snapshot_hash", "wab_snapshot_save", "wab_snapshot_restore",
     # include/wab_torus.h: the Environment 2.0 torus world
     "wab2_abi_version", "wab2_last_error", "wab2_record_size", "wab2_create", "wab2_destroy",
     "wab2_batch", "wab2_reset", "wab2_step", "wab2_rollout", "wab2_get_state", "wab2_get_counters",
@@ -28,7 +29,8 @@ EXPORTED = [
 ABI2_VERSION = 1
 OBS_SAME_BUFFER, OBS_FRESH_BUFFER = 0, 1  # wab_set_obs_placement
 
-ABI_VERSION = 5
+ABI_VERSION = 6
+SNAPSHOT_MAGIC, SNAPSHOT_VERSION = 0x53424157, 1  # 'WABS' (wab_snapshot_info)
 
 
 class WabObs(ctypes.Structure):
@@ -42,6 +44,13 @@ class WabCounters(ctypes.Structure):
                 ("resets", ctypes.c_uint64), ("ego_missing", ctypes.c_uint64),
                 ("handoff_timeouts", ctypes.c_uint64), ("wolf_overflow_reset", ctypes.c_uint64),
                 ("rollout_launches", ctypes.c_uint64), ("rollout_step_calls", ctypes.c_uint64)]
+
+
+class WabSnapshotInfo(ctypes.Structure):
+    _fields_ = [("magic", ctypes.c_uint32), ("version", ctypes.c_uint32),
+                ("config_hash", ctypes.c_uint64), ("seed", ctypes.c_uint64),
+                ("env_id_first", ctypes.c_int64), ("count", ctypes.c_int64),
+                ("record_bytes", ctypes.c_int64)]
 
 
 class WabError(RuntimeError):
@@ -97,6 +106,11 @@ def load():
     L.wab_step_kernel.argtypes = [P]
     L.wab_step_kernel.restype = ctypes.c_char_p
     L.wab_set_obs_placement.argtypes = [P, I32]
+    L.wab_snapshot_bytes.argtypes = [P]
+    L.wab_snapshot_hash.argtypes = [P]
+    L.wab_snapshot_hash.restype = U64
+    L.wab_snapshot_save.argtypes = [P, I64, I64, P, P, P]
+    L.wab_snapshot_restore.argtypes = [P, P, P, P, P]
     L.wab2_abi_version.restype = ctypes.c_int
     L.wab2_last_error.restype = ctypes.c_char_p
     L.wab2_record_size.argtypes = [P]
@@ -114,7 +128,7 @@ def load():
     L.wab2_get_obs.argtypes = [P, I32, P, P]
     L.wab2_take_action.argtypes = [P, I32, P, P, P, P, P]
     for name in EXPORTED:
-        if name not in ("wab_abi_version", "wab_last_error", "wab_batch", "wab_step_kernel",
+        if name not in ("wab_abi_version", "wab_last_error", "wab_batch", "wab_step_kernel", "wab_snapshot_hash",
                         "wab2_abi_version", "wab2_last_error", "wab2_batch"):
             getattr(L, name).restype = ctypes.c_int
     if L.wab_abi_version() != ABI_VERSION:

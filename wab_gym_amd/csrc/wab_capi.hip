@@ -36,6 +36,8 @@ template <int VEC, int NE>
 __global__ void wab_returns_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done, int32_t T,
                                    int64_t B, double gamma, const float* __restrict__ bootstrap,
                                    float* __restrict__ out, RewardTable tab);
+__global__ void wab_snapshot_pack(SnapParams p);
+__global__ void wab_snapshot_unpack(SnapParams p);
 }
 
 using wab::Params;
@@ -62,6 +64,7 @@ struct wab_handle {
   size_t wide_roll_lds_bytes = 0;  // ... of its multi-step build (wab_rollout_wide)
   int32_t obs_placement = WAB_OBS_SAME_BUFFER;  // wab_set_obs_placement: which wide per-step build
   uint64_t rollout_launches = 0, rollout_step_calls = 0;  // wab_counters' host tallies
+  uint64_t snapshot_hash = 0;  // wab_snapshot_hash of the options the handle was created with
 };
 
 namespace {
@@ -81,6 +84,84 @@ int fail(int code, const std::string& msg) {
   } while (0)
 
 int n_actions_of(const wab_config* c) { return (c->gatherer_only || c->lookout_only) ? 5 : 6; }
+
+// wab_config's "0 = default" fields as wab_create resolves them
+int resolved_wolf_slots(const wab_config* c) { return c->wolf_slots == 0 ? 8 : c->wolf_slots; }
+int resolved_eaten_capacity(const wab_config* c) {
+  return c->eaten_capacity > 0 ? c->eaten_capacity
+                               : (c->max_turns < 1 ? 1 : (c->max_turns > 255 ? 255 : c->max_turns));
+}
+
+// wab_snapshot_hash: FNV-1a over the options that decide how a state continues, as 64-bit words
+// (doubles by their bits): every rule field, width, height, autoreset, the resolved wolf_slots and
+// eaten_capacity, the threshold table.  Not plane_stride: it only shapes the observation.
+struct Fnv {
+  uint64_t h = 0xcbf29ce484222325ull;
+  void word(uint64_t v) {
+    for (int i = 0; i < 8; ++i) {
+      h ^= (v >> (8 * i)) & 0xFFu;
+      h *= 0x100000001b3ull;
+    }
+  }
+  void real(double d) {
+    uint64_t v;
+    std::memcpy(&v, &d, 8);
+    word(v);
+  }
+  void integer(int64_t v) { word((uint64_t)v); }
+};
+
+uint64_t snapshot_hash_of(const wab_config* c, const uint64_t* table) {
+  Fnv f;
+  f.real(c->reward_per_turn);
+  f.real(c->reward_for_being_killed);
+  f.real(c->reward_for_starving);
+  f.real(c->reward_for_finishing);
+  f.real(c->reward_for_eating);
+  f.integer(c->gatherer_only != 0);
+  f.integer(c->lookout_only != 0);
+  f.integer(c->restrict_view != 0);
+  f.integer(c->starting_role);
+  f.integer(c->starting_role_random != 0);
+  f.integer(c->starting_food_random != 0);
+  f.real(c->starting_food);
+  f.integer(c->max_turns);
+  f.integer(c->height);
+  f.integer(c->width);
+  f.integer(c->max_berries_per_bush);
+  f.real(c->bush_power);
+  f.integer(c->turns_to_fill_food);
+  f.integer(c->turns_to_empty_food);
+  f.integer(c->wolf_spawn_margin);
+  f.real(c->chance_wolf_on_square);
+  f.real(c->wolf_chance_to_despawn);
+  f.integer(c->wolves != 0);
+  f.integer(c->wolves_can_move != 0);
+  f.integer(c->god_mode != 0);
+  f.integer(c->autoreset != 0);
+  f.integer(resolved_wolf_slots(c));
+  f.integer(resolved_eaten_capacity(c));
+  for (int k = 0; k < c->max_berries_per_bush; ++k) f.word(table[k]);
+  return f.h;
+}
+
+// the geometry a record depends on; false (with the message set) for options wab_create refuses
+bool snapshot_dims(const wab_config* c, int* slots, int* cap, int* whw) {
+  if (!c) return fail(WAB_E_INVALID, "wab_snapshot: NULL config"), false;
+  if (c->width % 2 == 0 || c->height % 2 == 0)
+    return fail(WAB_E_INVALID, "width and height must be odd numbers"), false;
+  if (c->width < 1 || c->height < 1 || c->width > WAB_MAX_VIEW || c->height > WAB_MAX_VIEW)
+    return fail(WAB_E_INVALID, "width/height out of range [1, 63]"), false;
+  *slots = resolved_wolf_slots(c);
+  if (*slots != 8 && *slots != 16 && *slots != 32)
+    return fail(WAB_E_INVALID, "wolf_slots must be 8, 16 or 32"), false;
+  *cap = resolved_eaten_capacity(c);
+  if (*cap > 255) return fail(WAB_E_INVALID, "eaten_capacity must be <= 255"), false;
+  if (c->max_berries_per_bush < 0 || c->max_berries_per_bush > 255)
+    return fail(WAB_E_INVALID, "max_berries_per_bush must be in [0, 255]"), false;
+  *whw = (c->width * c->height + 31) / 32;
+  return true;
+}
 
 // masks wab_env.py:109-139 as 11-bit row masks (bit j <=> mask[i][j] == 1)
 const char* kLookout[11] = {"11100000111", "11000000011", "10000000001", "00000000000",
@@ -413,12 +494,11 @@ int wab_create(const wab_config* c, int64_t batch, uint64_t seed, int64_t env_id
   if (c->wolf_spawn_margin < 0 || c->width / 2 + c->wolf_spawn_margin > 120 ||
       c->height / 2 + c->wolf_spawn_margin > 120)
     return fail(WAB_E_INVALID, "wolf_spawn_margin out of range");
-  const int slots = c->wolf_slots == 0 ? 8 : c->wolf_slots;
+  const int slots = resolved_wolf_slots(c);
   if (slots != 8 && slots != 16 && slots != 32) return fail(WAB_E_INVALID, "wolf_slots must be 8, 16 or 32");
   const int S = c->plane_stride > 0 ? c->plane_stride : c->height;
   if (S < c->height || S > 64) return fail(WAB_E_INVALID, "plane_stride must be in [height, 64]");
-  const int cap = c->eaten_capacity > 0 ? c->eaten_capacity
-                                        : (c->max_turns < 1 ? 1 : (c->max_turns > 255 ? 255 : c->max_turns));
+  const int cap = resolved_eaten_capacity(c);
   if (cap > 255) return fail(WAB_E_INVALID, "eaten_capacity must be <= 255");
   if (batch < 0) return fail(WAB_E_INVALID, "batch must be >= 0");
 
@@ -534,6 +614,7 @@ int wab_create(const wab_config* c, int64_t batch, uint64_t seed, int64_t env_id
       for (int i = 0; i < 11; ++i)
         for (int j = 0; j < 11; ++j)
           if ((p.mask_rows[r][i] >> j) & 1u) p.view121[r][(i * 11 + j) >> 5] |= 1u << ((i * 11 + j) & 31);
+  h->snapshot_hash = snapshot_hash_of(c, thr_host);
   p.seed = seed;
   p.env_base = env_id_base;
   p.B = batch;
@@ -1141,6 +1222,130 @@ int wab_discounted_returns_exact(const wab_handle* h, const float* reward, const
   if (T == 0 || B == 0) return WAB_OK;
   DeviceGuard guard(h->device);
   return launch_returns(reward, done, T, B, gamma, bootstrap, returns, h->rewards, stream);
+}
+
+namespace {
+// SnapParams of envs [env0, env0 + n) of h against `records` (the record of env0), and the LDS of
+// the launch: 64 envs per pass, halved until the pass fits 40 KB, a quarter of a CU's 160 KB, so
+// that the four workgroups a CU gets at B = 65536 are resident together.  Measured at 31x31 (592-byte
+// records, 46 KB for 64 envs, three workgroups per CU and a second round for the fourth): save
+// 27.6 -> 19.2 us, restore 19.3 -> 15.5 us with passes of 32 envs (CHANGELOG.md).
+wab::SnapParams snapshot_params(const wab_handle* h, int64_t env0, int64_t n, const void* records,
+                                const uint8_t* mask, size_t* lds) {
+  const Params& p = h->p;
+  wab::SnapParams sp;
+  std::memset(&sp, 0, sizeof(sp));
+  sp.W = p.W; sp.H = p.H; sp.WH = p.WH; sp.WHW = p.WHW;
+  sp.slots = h->slots;
+  sp.cap = p.eaten_cap;
+  sp.wide = h->step_kernel == KERNEL_WIDE;
+  sp.B = p.B;
+  sp.env0 = env0;
+  sp.n = n;
+  sp.records = static_cast<uint4*>(const_cast<void*>(records));
+  sp.mask = mask;
+  sp.hdr = p.hdr; sp.food = p.food; sp.wolves = p.wolves;
+  sp.eaten_xy = p.eaten_xy; sp.eaten_rem = p.eaten_rem; sp.bushmap = p.bushmap;
+  const uint32_t pitch = wab::snap_pitch(wab::snap_layout(sp.slots, sp.cap, sp.WHW).rw);
+  const auto bytes = [&](int lg) { return ((size_t)pitch + (sp.wide ? 33u : 0u)) * 4u << lg; };
+  sp.lg_envs = 6;
+  while (bytes(sp.lg_envs) > 40u * 1024u) --sp.lg_envs;  // (the largest record is 1952 bytes: >= 16 envs)
+  *lds = bytes(sp.lg_envs);
+  return sp;
+}
+}  // namespace
+
+int wab_snapshot_bytes(const wab_config* cfg) {
+  g_err.clear();
+  int slots, cap, whw;
+  if (!snapshot_dims(cfg, &slots, &cap, &whw)) return WAB_E_INVALID;
+  return (int)wab::snap_layout(slots, cap, whw).rw * 4;
+}
+
+uint64_t wab_snapshot_hash(const wab_config* cfg) {
+  g_err.clear();
+  int slots, cap, whw;
+  if (!snapshot_dims(cfg, &slots, &cap, &whw)) return 0;
+  std::vector<uint64_t> own;
+  const uint64_t* table = cfg->bush_thresholds;
+  if (cfg->max_berries_per_bush > 0 && !table) {
+    own.resize((size_t)cfg->max_berries_per_bush);
+    if (wab_bush_thresholds(cfg->bush_power, cfg->max_berries_per_bush, own.data()) != WAB_OK) return 0;
+    table = own.data();
+  }
+  return snapshot_hash_of(cfg, table);
+}
+
+int wab_snapshot_save(wab_handle* h, int64_t first, int64_t count, void* records, wab_snapshot_info* info,
+                      void* stream) {
+  g_err.clear();
+  if (!h || !info) return fail(WAB_E_INVALID, "wab_snapshot_save: NULL argument");
+  if (!h->reset_done) return fail(WAB_E_STATE, "wab_snapshot_save: no env has a state before the first wab_reset");
+  const int64_t B = h->p.B;
+  if (first < 0 || count < 0 || first > B || count > B - first)
+    return fail(WAB_E_INVALID, "wab_snapshot_save: [first, first + count) must lie in [0, B)");
+  if (count > 0 && (!records || !aligned16(records)))
+    return fail(WAB_E_INVALID, "wab_snapshot_save: records must be a 16-byte aligned device pointer");
+  size_t lds = 0;
+  const wab::SnapParams sp = snapshot_params(h, first, count, records, nullptr, &lds);
+  info->magic = WAB_SNAPSHOT_MAGIC;
+  info->version = WAB_SNAPSHOT_VERSION;
+  info->config_hash = h->snapshot_hash;
+  info->seed = h->p.seed;
+  info->env_id_first = h->p.env_base + first;
+  info->count = count;
+  info->record_bytes = (int64_t)wab::snap_layout(sp.slots, sp.cap, sp.WHW).rw * 4;
+  if (count == 0) return WAB_OK;
+  DeviceGuard guard(h->device);
+  const dim3 grid((unsigned)((count + wab::kEnvsPerBlock - 1) / wab::kEnvsPerBlock));
+  hipLaunchKernelGGL(wab::wab_snapshot_pack, grid, dim3(256), lds, (hipStream_t)stream, sp);
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+int wab_snapshot_restore(wab_handle* h, const wab_snapshot_info* info, const void* records, const uint8_t* mask,
+                         void* stream) {
+  g_err.clear();
+  if (!h || !info) return fail(WAB_E_INVALID, "wab_snapshot_restore: NULL argument");
+  const Params& p = h->p;
+  const int64_t R = (int64_t)wab::snap_layout(h->slots, p.eaten_cap, p.WHW).rw * 4;
+  if (info->magic != WAB_SNAPSHOT_MAGIC) return fail(WAB_E_INVALID, "wab_snapshot_restore: magic is not 'WABS'");
+  if (info->version != WAB_SNAPSHOT_VERSION)
+    return fail(WAB_E_INVALID, "wab_snapshot_restore: snapshot version " + std::to_string(info->version) +
+                                   ", this library reads version 1");
+  if (info->config_hash != h->snapshot_hash)
+    return fail(WAB_E_INVALID, "wab_snapshot_restore: config_hash differs (the snapshot is of other game options, "
+                               "wolf_slots or eaten_capacity; see wab_snapshot_hash)");
+  if (info->seed != p.seed) return fail(WAB_E_INVALID, "wab_snapshot_restore: seed differs from the handle's");
+  if (info->record_bytes != R)
+    return fail(WAB_E_INVALID, "wab_snapshot_restore: record_bytes " + std::to_string(info->record_bytes) +
+                                   " != " + std::to_string(R) + " of this handle");
+  // global ids [lo, hi): the snapshot's range cut to the handle's (all on the host: the kernel
+  // indexes records [lo - first, hi - first) only)
+  const int64_t s_first = info->env_id_first, s_count = info->count;
+  if (s_count < 0 || (s_first > 0 && s_count > INT64_MAX - s_first))
+    return fail(WAB_E_INVALID, "wab_snapshot_restore: bad id range in the snapshot");
+  const int64_t lo = std::max(s_first, p.env_base);
+  const int64_t hi = std::min(s_first + s_count, p.env_base + p.B);
+  if (lo >= hi)
+    return fail(WAB_E_INVALID, "wab_snapshot_restore: the snapshot's env ids [" + std::to_string(s_first) + ", " +
+                                   std::to_string(s_first + s_count) + ") do not intersect the handle's [" +
+                                   std::to_string(p.env_base) + ", " + std::to_string(p.env_base + p.B) + ")");
+  if (!h->reset_done && (mask || lo != p.env_base || hi != p.env_base + p.B))
+    return fail(WAB_E_STATE, "wab_snapshot_restore: a handle that was never reset takes only a restore of "
+                             "all its envs (mask = NULL)");
+  if (!records || !aligned16(records))
+    return fail(WAB_E_INVALID, "wab_snapshot_restore: records must be a 16-byte aligned device pointer");
+  size_t lds = 0;
+  const wab::SnapParams sp = snapshot_params(h, lo - p.env_base, hi - lo,
+                                             static_cast<const uint8_t*>(records) + (size_t)(lo - s_first) * (size_t)R,
+                                             mask, &lds);
+  DeviceGuard guard(h->device);
+  const dim3 grid((unsigned)((hi - lo + wab::kEnvsPerBlock - 1) / wab::kEnvsPerBlock));
+  hipLaunchKernelGGL(wab::wab_snapshot_unpack, grid, dim3(256), lds, (hipStream_t)stream, sp);
+  HIP_TRY(hipGetLastError());
+  h->reset_done = true;  // (a full restore is a never-reset handle's first reset)
+  return WAB_OK;
 }
 
 int wab_debug_bush_values(wab_handle* h, const uint64_t* U, int32_t* out, int64_t n, void* stream) {

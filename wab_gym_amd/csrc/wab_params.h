@@ -332,6 +332,49 @@ struct FeatParams {
   float* out;                // [B][F]
 };
 
+// Snapshot records (wab_snapshot.hip, wab_snapshot_save / wab_snapshot_restore): one env's
+// state as consecutive dwords, the same whichever step kernel runs the handle:
+//   [0,4) hdr  [4,6) food  [wolf, +slots) wolf tiles  [exy, +cap) eaten tiles
+//   [erem, +ceil(cap/4)) berries left, one byte per entry  [bm, +WHW) bush bitmap, bit i*H + j
+// then zeros up to rw (a multiple of 4: records are 16-byte units).
+struct SnapLayout {
+  uint32_t wolf, exy, erem, bm, end, rw;
+};
+
+__host__ __device__ inline SnapLayout snap_layout(int slots, int cap, int WHW) {
+  SnapLayout L;
+  L.wolf = 6u;
+  L.exy = L.wolf + (uint32_t)slots;
+  L.erem = L.exy + (uint32_t)cap;
+  L.bm = L.erem + ((uint32_t)cap + 3u) / 4u;
+  L.end = L.bm + (uint32_t)WHW;
+  L.rw = lds_align4(L.end);
+  return L;
+}
+
+// LDS dwords per env of the record transposition: rw rounded up to an odd number of 16-byte
+// units, so that the lane-per-env dword accesses of the state side spread over 16 banks (a
+// 4-way conflict) and the 16-byte accesses of the record side stay aligned
+__host__ __device__ inline uint32_t snap_pitch(uint32_t rw) { return ((rw / 4u) & 1u) ? rw : rw + 4u; }
+
+struct SnapParams {
+  int32_t W, H, WH, WHW;
+  int32_t slots, cap;
+  int32_t wide;        // the handle's bushmap layout: 1 = [B][32] row dwords (wab_step_wide.hip,
+                       // bit j of row i), 0 = [WHW][B] words (bit i*H + j)
+  int32_t lg_envs;     // log2 of the envs per LDS pass (6, or less when 64 records exceed the LDS)
+  int64_t B;           // the handle's batch: the pitch of the state arrays' rows
+  int64_t env0, n;     // envs [env0, env0 + n) of the handle ...
+  uint4* records;      // ... are records[0 .. n) (16-byte aligned, rw dwords each)
+  const uint8_t* mask; // unpack only, nullable: [B], envs with mask[i] == 0 are left untouched
+  uint4* hdr;
+  double* food;
+  uint32_t* wolves;
+  uint32_t* eaten_xy;
+  uint8_t* eaten_rem;
+  uint32_t* bushmap;
+};
+
 // The rewards one step of an env can return (wab_env.py:299-340: 0 + r_x, or 0 + r_eat + r_x
 // for r_x in per turn / finishing / starving / killed) as (float32 bits, exact double) pairs:
 // the double a float32 device reward came from (wab_discounted_returns_exact).  n = 0: none.

@@ -77,6 +77,14 @@ class BatchedWolvesAndBushesEnvEgoCentric(BatchedWolvesAndBushesEnv):
     def rollout(self, actions):
         raise NotImplementedError("the egocentric observation is computed per step; use step()")
 
+    def snapshot(self, envs=None):
+        raise NotImplementedError("a snapshot does not hold the episode's path, which the egocentric "
+                                  "observation is computed from (wab_egocentric, include/wab.h)")
+
+    def restore(self, snap, mask=None):
+        raise NotImplementedError("a snapshot does not hold the episode's path, which the egocentric "
+                                  "observation is computed from (wab_egocentric, include/wab.h)")
+
 
 class BatchedWolvesAndBushesEnvEgocentricJustBushes(BatchedWolvesAndBushesEnvEgoCentric):
     """Observation = the 5 bush proximities only; action_space Discrete(5) (wab_env.py:963-964)."""

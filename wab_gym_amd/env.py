@@ -392,6 +392,99 @@ class BatchedWolvesAndBushesEnv:
         return {"features": features, "scalars": scal.permute(1, 0, 2), "reward": rew, "done": done,
                 "returns": ret, "planes": planes}
 
+    # ------------------------------------------------------------------ snapshots
+    def snapshot(self, envs=None):
+        """The state of every env, or of envs=(first, count), as an EnvSnapshot (snapshot.py):
+        the device records of wab_snapshot_save plus those envs' rows of the gym surface (obs,
+        reward, done, terminal obs).  restore() of it, into this env or into another one of the
+        same options and seed that holds the same global env ids, continues bit for bit.  Not
+        part of it: counters(), and anything a wrapper keeps."""
+        from .snapshot import EnvSnapshot
+
+        t = self._torch
+        if not self._reset_once:
+            raise RuntimeError("call reset() before snapshot(): no env has a state yet")
+        first, count = (0, self.num_envs) if envs is None else (int(envs[0]), int(envs[1]))
+        if first < 0 or count < 0 or first + count > self.num_envs:
+            raise ValueError("envs=(first, count) must lie in [0, %d)" % self.num_envs)
+        L = _lib.load()
+        R = int(L.wab_snapshot_bytes(ctypes.addressof(self.cfg)))
+        if R < 0:
+            _lib.check(R, "wab_snapshot_bytes")
+        records = t.empty((count, R), dtype=t.uint8, device=self.device)
+        info = _lib.WabSnapshotInfo()
+        _lib.check(L.wab_snapshot_save(self._h, first, count, records.data_ptr(), ctypes.addressof(info),
+                                       self._stream()), "wab_snapshot_save")
+        rows = slice(first, first + count)
+        term = self._term
+        return EnvSnapshot(
+            info.magic, info.version, info.config_hash, info.seed, info.env_id_first, info.count,
+            info.record_bytes, records, self._obs["planes"][rows].clone(), self._obs["scalars"][:, rows].clone(),
+            self.reward[rows].clone(), self.done[rows].clone(), self.W, self.H, self.S,
+            planes_valid=self._planes_valid,
+            term_planes=None if term is None else term["planes"][rows].clone(),
+            term_scalars=None if term is None else term["scalars"][:, rows].clone())
+
+    def restore(self, snap, mask=None):
+        """Put the envs of `snap` (an EnvSnapshot) back into the state it holds and return the obs
+        tuple, as reset() does.  An env of this batch takes the record of its own global id
+        (env_id_base + index) when the snapshot holds that id and mask is None or mask[i] is true;
+        every other env is untouched.  The device state and the restored envs' rows of the gym
+        surface (obs, reward, done, terminal obs) are restored; counters() are not.  The snapshot
+        may come from an env of another batch size, env_id_base or plane_stride (the H columns
+        are copied, the padding is zeroed); other options, another seed or disjoint ids raise
+        ValueError.  A never-reset env takes only a restore of all its envs (mask=None), which is
+        then its first reset."""
+        t = self._torch
+        m = None
+        if mask is not None:
+            if not self._reset_once:
+                raise RuntimeError("a never-reset env takes only a restore of every env (mask=None)")
+            m = t.as_tensor(mask, device=self.device).to(t.uint8).contiguous()
+            if m.shape != (self.num_envs,):
+                raise ValueError("mask must have shape [num_envs]")
+        lo = max(snap.env_id_first, self.env_id_base)
+        hi = min(snap.env_id_first + snap.count, self.env_id_base + self.num_envs)
+        partial = m is not None or hi - lo != self.num_envs
+        if partial and self._reset_once and not self._planes_valid:
+            raise RuntimeError("the env's obs planes are stale (step_features/rollout_features with "
+                               "store_planes=False); restore every env, or step()/reset() first")
+        snap = snap.to(self.device)
+        records = snap.records.contiguous()
+        info = snap.info()
+        _lib.check(_lib.load().wab_snapshot_restore(self._h, ctypes.addressof(info), records.data_ptr(),
+                                                    None if m is None else m.data_ptr(), self._stream()),
+                   "wab_snapshot_restore")
+        self._reset_mask_keepalive = m
+        # the restored envs' rows of the surface (the checks above passed: same W and H, lo < hi)
+        dst, src = slice(lo - self.env_id_base, hi - self.env_id_base), slice(lo - snap.env_id_first,
+                                                                              hi - snap.env_id_first)
+        sel = None if m is None else m[dst].bool()
+
+        def put(own, saved, env_axis):
+            view = own[dst] if env_axis == 0 else own[:, dst]
+            if sel is None:
+                view.copy_(saved)
+            else:
+                s = sel.view([-1] + [1] * (view.dim() - 1)) if env_axis == 0 else sel
+                view.copy_(t.where(s, saved, view))
+
+        def put_planes(own, saved):
+            p = t.zeros((hi - lo, 3, self.W, self.S), dtype=t.uint8, device=self.device)
+            p[..., :self.H] = saved[src][..., :self.H]
+            put(own, p, 0)
+
+        put_planes(self._obs["planes"], snap.planes)
+        put(self._obs["scalars"], snap.scalars[:, src], 1)
+        put(self.reward, snap.reward[src], 0)
+        put(self.done, snap.done[src], 0)
+        if self._term is not None and snap.term_planes is not None:
+            put_planes(self._term["planes"], snap.term_planes)
+            put(self._term["scalars"], snap.term_scalars[:, src], 1)
+        self._planes_valid = (self._planes_valid if partial else True) and snap.planes_valid
+        self._reset_once = True
+        return self._obs_tuple(self._obs)
+
     def render(self, mode="rgb_array", scale=32, draw_health=True, out=None, obs=None, envs=None):
         """render (wab_env.py:468-502) of every env's current observation (or of `obs`, a
         dict of planes [B,3,W,S] and scalars [3,B] u8 tensors) on device: u8 [B, W*scale,

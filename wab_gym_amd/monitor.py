@@ -179,7 +179,9 @@ class EpisodeMonitor:
     """`gym.wrappers.Monitor(env, directory, video_callable, force)` for a batched env: episode
     statistics of every env, video of env `video_env`'s scheduled episodes (module
     docstring).  video_callable=False records none.  Attributes of the wrapped env pass
-    through."""
+    through, except snapshot() and restore(): the running episode sums and the video recorder
+    are not part of an EnvSnapshot, so after a restore the statistics would describe episodes
+    that were never played; both raise NotImplementedError here."""
 
     def __init__(self, env, directory=None, force=False, flush_every=32, monitor_id=0, video_callable=None,
                  video_env=0, video_scale=32):
@@ -207,6 +209,14 @@ class EpisodeMonitor:
 
     def __getattr__(self, name):
         return getattr(self.env, name)
+
+    def snapshot(self, envs=None):
+        raise NotImplementedError("EpisodeMonitor does not snapshot: its episode statistics are not part "
+                                  "of an EnvSnapshot")
+
+    def restore(self, snap, mask=None):
+        raise NotImplementedError("EpisodeMonitor does not restore: its running episode sums would be "
+                                  "wrong afterwards")
 
     def reset(self, mask=None):
         obs = self.env.reset(mask)
