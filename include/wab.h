@@ -36,6 +36,7 @@
  *   wab_discounted_returns_exact <- the same on the env's own rewards   actor_critic.py:139-145
  *   wab_snapshot_save / wab_snapshot_restore <- (no counterpart: the reference has no
  *                            checkpoint, resume or rewind of an env)
+ *   wab_policy_act        <- Policy.forward + select_action's sample  actor_critic.py:76-125
  */
 #ifndef WAB_H_
 #define WAB_H_
@@ -47,7 +48,7 @@
 extern "C" {
 #endif
 
-#define WAB_ABI_VERSION 6
+#define WAB_ABI_VERSION 7
 #define WAB_MAX_WOLF_SLOTS 32 /* largest per-env live-wolf slot count (wab_config.wolf_slots) */
 #define WAB_MAX_VIEW 63       /* largest odd width/height accepted */
 
@@ -371,6 +372,51 @@ int wab_snapshot_save(wab_handle* h, int64_t first, int64_t count, void* records
  * restore into it is WAB_E_STATE. */
 int wab_snapshot_restore(wab_handle* h, const wab_snapshot_info* info, const void* records,
                          const uint8_t* mask, void* stream);
+
+/* ---- device policy: the closed loop's action in one launch --------------------------- */
+
+/* The actor-critic network of actor_critic.py:54-97 for inference: three Linear + leaky_relu
+ * (slope 0.01) layers of widths h1, h2, h3, clamp(-4, 4) after the third, a softmax action head
+ * (n_actions units) and a one-unit value head.  in_features >= 1, h1, h2, h3 in [1, 256],
+ * n_actions in [2, 8]; the reference's net is {449, 128, 150, 128, 5}.
+ * Numeric contract: every matmul operand (input features, weights, hidden activations after
+ * bias, leaky_relu and clamp) is rounded to bf16, nearest even; products accumulate in fp32;
+ * bias, activation, clamp, softmax (max-subtracted, expf, one divide) and the value are fp32.
+ * Features that are 0 or 1, as wab_step_features writes them, are exact.  The reference's
+ * + U(0, 1) / 100 input noise (actor_critic.py:189) is not reproduced.
+ * Sampling: u = U * 2^-53 with U the 53-bit keyed draw of (seed, global env id, the env's current
+ * episode, site 11, the env's current turn, tile (0, 0), k = 0), episode and turn read from the
+ * handle's own state; action = #{k < n_actions - 1 : c_k <= u}, c_k the running sum in double,
+ * k = 0, 1, ..., of the fp32 probabilities written to `probs`.  The action is an exact function
+ * of probs and u, the same for any sharding of the batch. */
+typedef struct wab_policy wab_policy;
+typedef struct wab_policy_shape {
+  int32_t in_features, h1, h2, h3, n_actions;
+} wab_policy_shape;
+/* fp32 device arrays in torch.nn.Linear's layout: weights [out][in], biases [out] (affine1,
+ * affine2, affine3, action_head, value_head of actor_critic.Policy) */
+typedef struct wab_policy_weights {
+  const float *w1, *b1, *w2, *b2, *w3, *b3, *wa, *ba, *wv, *bv;
+} wab_policy_weights;
+
+/* Allocate the packed-weight image on `device` (synchronous).  WAB_E_INVALID for a shape outside
+ * the ranges above. */
+int wab_policy_create(const wab_policy_shape* shape, int device, wab_policy** out);
+
+/* Round the weights to bf16 into the padded image the kernel reads: one stream-ordered launch, no
+ * allocation, no synchronisation (a training loop reloads after every optimizer step). */
+int wab_policy_load(wab_policy* p, const wab_policy_weights* weights, void* stream);
+
+/* One launch: probs, value and the sampled action of every env of the handle from features
+ * [B][in_features] float32 (e.g. those wab_step_features wrote; 4-byte aligned).  actions [B] int8;
+ * probs [B][n_actions] float32 or NULL; value [B] float32 or NULL.  No host synchronisation, safe
+ * to capture in a hipGraph.  WAB_E_INVALID when n_actions differs from the handle's or the policy
+ * is on another device; WAB_E_STATE before the first wab_policy_load or the first wab_reset. */
+int wab_policy_act(wab_handle* h, wab_policy* p, const float* features, int8_t* actions, float* probs,
+                   float* value, void* stream);
+
+/* Free the policy (synchronises its device). */
+int wab_policy_destroy(wab_policy* p);
 
 /* Test hook: the bush value (berries, generate_n_bush_values wab_env.py:631-635) the step
  * kernels give the 53-bit draws U[n] under h's threshold table, computed by the kernels' own

@@ -1,0 +1,127 @@
+"""The device policy's references on the CPU (wab_gym_amd/policy.py): reference_forward on a net
+small enough to follow by hand, sample_reference against the keyed RNG's definition, and E_bf16,
+what the bf16 contract costs against a stock fp32 forward on the GPU test's own inputs."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import policy_cases as pc
+from wab_gym_amd import policy
+
+
+def test_reference_forward_by_hand():
+    """A 2-2-2-2 net, A = 2.  x = (1, 0.5):
+    layer 1: z = (1 + 1 + 0.5, -1 - 1) = (2.5, -2); leaky (2.5, -2 * 0.01f); bf16 (2.5, -0.02001953125)
+             (0.02 = 1.28 * 2^-6; 1.28 * 128 = 163.84 -> 164 / 128 * 2^-6);
+    layer 2: z = (2 * 2.5, 100 * -0.02001953125) = (5, -2.001953125); leaky, bf16 (5, -0.02001953125);
+    layer 3: z = (5, -100 * 5) = (5, -500); leaky (5, -5 (just above)); clamp (4, -4): both limits;
+    heads: logits 0.25 * (4, -4) = (1, -1): probs (e^2, 1) / (1 + e^2); value 0.5 * 4 + 0.25 * -4 + 1 = 2."""
+    sd = {"affine1.weight": [[1.0, 2.0], [-1.0, -2.0]], "affine1.bias": [0.5, 0.0],
+          "affine2.weight": [[2.0, 0.0], [0.0, 100.0]], "affine2.bias": [0.0, 0.0],
+          "affine3.weight": [[1.0, 0.0], [-100.0, 0.0]], "affine3.bias": [0.0, 0.0],
+          "action_head.weight": [[0.25, 0.0], [0.0, 0.25]], "action_head.bias": [0.0, 0.0],
+          "value_head.weight": [[0.5, 0.25]], "value_head.bias": [1.0]}
+    sd = {k: torch.tensor(v, dtype=torch.float32) for k, v in sd.items()}
+    assert policy.shape_of(sd) == (2, 2, 2, 2, 2)
+    hidden = []
+    probs, value = policy.reference_forward(sd, torch.tensor([[1.0, 0.5]]), hidden=hidden)
+    assert probs.dtype == torch.float64 and value.dtype == torch.float64
+    slope = float(np.float32(0.01))
+    assert hidden[0][0].tolist() == [[2.5, -2.0]]
+    assert hidden[0][1].tolist() == [[2.5, -0.02001953125]]
+    assert hidden[1][0].tolist() == [[5.0, -2.001953125]]
+    assert hidden[1][1].tolist() == [[5.0, -0.02001953125]]
+    assert hidden[2][0].tolist() == [[5.0, -500.0]]
+    assert -500.0 * slope < -4.0          # the negative slope takes -500 below the lower clamp limit
+    assert hidden[2][1].tolist() == [[4.0, -4.0]]
+    e2 = math.exp(2.0)
+    assert probs[0].tolist() == pytest.approx([e2 / (1 + e2), 1 / (1 + e2)], abs=1e-15)
+    assert value.tolist() == [2.0]
+
+
+def test_reference_forward_rounds_inputs_and_weights_to_bf16():
+    """1/3 as a feature and as a weight are used as bf16(1/3) = 0.333984375."""
+    sd = {k: torch.zeros(s) for k, s in (("affine1.weight", (1, 1)), ("affine1.bias", (1,)),
+                                         ("affine2.weight", (1, 1)), ("affine2.bias", (1,)),
+                                         ("affine3.weight", (1, 1)), ("affine3.bias", (1,)),
+                                         ("action_head.weight", (2, 1)), ("action_head.bias", (2,)),
+                                         ("value_head.weight", (1, 1)), ("value_head.bias", (1,)))}
+    sd["affine1.weight"][0, 0] = 1.0 / 3.0
+    hidden = []
+    policy.reference_forward(sd, torch.tensor([[1.0 / 3.0]]), hidden=hidden)
+    assert hidden[0][0].item() == 0.333984375 * 0.333984375
+
+
+def test_state_dict_checks():
+    sd = dict(pc.weights("odd"))
+    del sd["value_head.bias"]
+    with pytest.raises(ValueError, match="value_head.bias"):
+        policy.shape_of(sd)
+    sd = dict(pc.weights("odd"))
+    sd["affine2.weight"] = sd["affine2.weight"][:, :-1]
+    with pytest.raises(ValueError, match="affine2.weight"):
+        policy.shape_of(sd)
+
+
+def test_sample_reference_is_the_keyed_draw_of_site_11():
+    from oracle import keyed_rng
+
+    assert policy.SITE_POLICY == 11
+    taken = [v for k, v in vars(keyed_rng).items() if k.startswith("SITE_")]
+    assert 11 not in taken and max(taken) == 10  # the first id free in the oracle's list
+    rng = np.random.RandomState(3)
+    n, A = 500, 5
+    p = rng.dirichlet(np.ones(A), size=n).astype(np.float32)
+    seed = 0xC0FFEE
+    env = rng.randint(0, 1 << 40, size=n)
+    ep = rng.randint(0, 1 << 31, size=n)
+    turn = rng.randint(0, 200, size=n)
+    u = np.array([keyed_rng.draw_u(keyed_rng.episode_key(seed, int(e), int(q)), 11, int(t), [0], [0], 0)[0]
+                  for e, q, t in zip(env, ep, turn)])
+    assert np.array_equal(policy.keyed_u(seed, env, ep, turn), u)
+    want = np.zeros(n, np.int8)
+    for i in range(n):
+        c = 0.0
+        for k in range(A - 1):
+            c += float(p[i, k])
+            want[i] += c <= u[i]
+    got = policy.sample_reference(p, seed, env, ep, turn)
+    assert got.dtype == np.int8 and np.array_equal(got, want)
+    assert len(set(got.tolist())) == A
+    # the boundaries: u below the first cumulative sum, and a cumulative sum equal to u
+    assert policy.sample_reference(np.array([[1.0, 0.0]], np.float32), seed, [5], [0], [0])[0] == 0
+    assert policy.sample_reference(np.array([[0.0, 1.0]], np.float32), seed, [5], [0], [0])[0] == 1
+    with pytest.raises(ValueError):
+        policy.sample_reference(p.astype(np.float64), seed, env, ep, turn)
+
+
+@pytest.mark.parametrize("which", ["ref", "odd"])
+def test_weights_reach_both_clamp_limits_and_negative_slopes(which):
+    sd = pc.weights(which)
+    feats = pc.ref_features(257) if which == "ref" else pc.odd_features(257)
+    hidden = []
+    policy.reference_forward(sd, feats, hidden=hidden)
+    for z, _ in hidden:
+        assert (z < 0).any() and (z > 0).any()
+    assert (hidden[2][1] == 4.0).any() and (hidden[2][1] == -4.0).any()
+    assert ((hidden[2][1] > -4.0) & (hidden[2][1] < 4.0)).any()
+
+
+def test_contract_cost_E_bf16(capsys):
+    """E_bf16 = max |reference_forward - stock fp32 torch forward with unrounded weights| over the
+    GPU test's inputs: the yardstick of tests/test_gpu_policy.py (the kernel must stay within half
+    of it).  Printed per case; DESIGN.md records the B = 257 figures."""
+    rows = []
+    for which in ("ref", "odd"):
+        sd = pc.weights(which)
+        for B in pc.BATCHES:
+            feats = pc.ref_features(B) if which == "ref" else pc.odd_features(B)
+            e_p, e_v = pc.contract_cost(sd, feats)
+            rows.append((which, B, e_p, e_v))
+            # bf16 keeps 8 bits: the cost is far above fp32 noise and far below the outputs' scale
+            assert 1e-6 < e_p < 0.1 and 1e-6 < e_v < 0.5, (which, B, e_p, e_v)
+    with capsys.disabled():
+        for r in rows:
+            print("E_bf16 net %-3s B %3d: probs %.3e value %.3e" % r)

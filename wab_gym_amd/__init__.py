@@ -26,6 +26,10 @@ def __getattr__(name):
         from .snapshot import EnvSnapshot
 
         return EnvSnapshot
+    if name == "DevicePolicy":
+        from .policy import DevicePolicy
+
+        return DevicePolicy
     if name == "EpisodeMonitor":
         from .monitor import EpisodeMonitor
 
@@ -37,5 +41,5 @@ def __getattr__(name):
     raise AttributeError(name)
 
 
-__all__ = ["BatchedWolvesAndBushesEnv", "EnvSnapshot", "default_game_options", "make_config",
-           "bush_thresholds"]
+__all__ = ["BatchedWolvesAndBushesEnv", "DevicePolicy", "EnvSnapshot", "default_game_options",
+           "make_config", "bush_thresholds"]

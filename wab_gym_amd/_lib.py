@@ -20,6 +20,7 @@ EXPORTED = [
     "wab_debug_bush_values", "wab_step_features", "wab_discounted_returns_exact",
     "wab_bush_thresholds", "wab_rollout_features", "wab_render_envs", "wab_set_obs_placement",
     "wab_snapshot_bytes", "wab_snapshot_hash", "wab_snapshot_save", "wab_snapshot_restore",
+    "wab_policy_create", "wab_policy_load", "wab_policy_act", "wab_policy_destroy",
     # include/wab_torus.h: the Environment 2.0 torus world
     "wab2_abi_version", "wab2_last_error", "wab2_record_size", "wab2_create", "wab2_destroy",
     "wab2_batch", "wab2_reset", "wab2_step", "wab2_rollout", "wab2_get_state", "wab2_get_counters",
@@ -29,7 +30,7 @@ EXPORTED = [
 ABI2_VERSION = 1
 OBS_SAME_BUFFER, OBS_FRESH_BUFFER = 0, 1  # wab_set_obs_placement
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 SNAPSHOT_MAGIC, SNAPSHOT_VERSION = 0x53424157, 1  # 'WABS' (wab_snapshot_info)
 
 
@@ -51,6 +52,14 @@ class WabSnapshotInfo(ctypes.Structure):
                 ("config_hash", ctypes.c_uint64), ("seed", ctypes.c_uint64),
                 ("env_id_first", ctypes.c_int64), ("count", ctypes.c_int64),
                 ("record_bytes", ctypes.c_int64)]
+
+
+class WabPolicyShape(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("in_features", "h1", "h2", "h3", "n_actions")]
+
+
+class WabPolicyWeights(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "wa", "ba", "wv", "bv")]
 
 
 class WabError(RuntimeError):
@@ -111,6 +120,10 @@ def load():
     L.wab_snapshot_hash.restype = U64
     L.wab_snapshot_save.argtypes = [P, I64, I64, P, P, P]
     L.wab_snapshot_restore.argtypes = [P, P, P, P, P]
+    L.wab_policy_create.argtypes = [P, ctypes.c_int, ctypes.POINTER(P)]
+    L.wab_policy_load.argtypes = [P, P, P]
+    L.wab_policy_act.argtypes = [P, P, P, P, P, P, P]
+    L.wab_policy_destroy.argtypes = [P]
     L.wab2_abi_version.restype = ctypes.c_int
     L.wab2_last_error.restype = ctypes.c_char_p
     L.wab2_record_size.argtypes = [P]

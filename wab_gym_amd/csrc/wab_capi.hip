@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -17,6 +18,7 @@
 #include "wab_params.h"
 #include "wab_device.h"
 #include "wab_feat.h"
+#include "wab_policy.h"
 
 namespace wab {
 template <int MODE, int SLOTS, bool SMALL>
@@ -38,6 +40,9 @@ __global__ void wab_returns_kernel(const float* __restrict__ reward, const uint8
                                    float* __restrict__ out, RewardTable tab);
 __global__ void wab_snapshot_pack(SnapParams p);
 __global__ void wab_snapshot_unpack(SnapParams p);
+__global__ void wab_policy_pack(PolicyPackParams p);
+template <bool TWO>
+__global__ void wab_policy_kernel(PolicyParams p);
 }
 
 using wab::Params;
@@ -65,6 +70,16 @@ struct wab_handle {
   int32_t obs_placement = WAB_OBS_SAME_BUFFER;  // wab_set_obs_placement: which wide per-step build
   uint64_t rollout_launches = 0, rollout_step_calls = 0;  // wab_counters' host tallies
   uint64_t snapshot_hash = 0;  // wab_snapshot_hash of the options the handle was created with
+};
+
+// wab_policy_*: the packed weights of one network on one device (wab_policy.h)
+struct wab_policy {
+  int device = 0;
+  wab::PolicyDims dims;
+  wab::PolicyLds lds;
+  uint16_t* w = nullptr;  // bf16 image, dims.w_total elements
+  float* b = nullptr;     // padded biases, dims.b_total floats
+  bool loaded = false;
 };
 
 namespace {
@@ -1345,6 +1360,129 @@ int wab_snapshot_restore(wab_handle* h, const wab_snapshot_info* info, const voi
   hipLaunchKernelGGL(wab::wab_snapshot_unpack, grid, dim3(256), lds, (hipStream_t)stream, sp);
   HIP_TRY(hipGetLastError());
   h->reset_done = true;  // (a full restore is a never-reset handle's first reset)
+  return WAB_OK;
+}
+
+// ---- device policy (wab_policy.hip) -------------------------------------------------------
+
+int wab_policy_create(const wab_policy_shape* shape, int device, wab_policy** out) {
+  g_err.clear();
+  if (!shape || !out) return fail(WAB_E_INVALID, "wab_policy_create: NULL argument");
+  *out = nullptr;
+  if (shape->in_features < 1) return fail(WAB_E_INVALID, "wab_policy_create: in_features must be >= 1");
+  const int32_t hs[3] = {shape->h1, shape->h2, shape->h3};
+  for (int i = 0; i < 3; ++i)
+    if (hs[i] < 1 || hs[i] > wab::kPolicyMaxWidth)
+      return fail(WAB_E_INVALID, "wab_policy_create: h" + std::to_string(i + 1) + " = " + std::to_string(hs[i]) +
+                                     " outside [1, 256]");
+  if (shape->n_actions < 2 || shape->n_actions > wab::kPolicyMaxActions)
+    return fail(WAB_E_INVALID, "wab_policy_create: n_actions must be in [2, 8]");
+  if (shape->in_features > (1 << 20)) return fail(WAB_E_INVALID, "wab_policy_create: in_features above 2^20");
+  int n_dev = 0;
+  HIP_TRY(hipGetDeviceCount(&n_dev));
+  if (device < 0 || device >= n_dev) return fail(WAB_E_INVALID, "wab_policy_create: no such device");
+  wab_policy* p = new (std::nothrow) wab_policy();
+  if (!p) return fail(WAB_E_NOMEM, "wab_policy_create: out of host memory");
+  p->device = device;
+  p->dims = wab::policy_dims(shape->in_features, shape->h1, shape->h2, shape->h3, shape->n_actions);
+  p->lds = wab::policy_lds(p->dims);
+  DeviceGuard guard(device);
+  // the kernel's dynamic LDS can exceed the 64 KB default: raised for this device at every
+  // create, to what this policy needs or more (the attribute is a maximum per device and kernel,
+  // so it is set to the device's limit, whatever other policies on the device need)
+  int lds_max = 0;
+  hipError_t e = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
+  if (e == hipSuccess && (size_t)lds_max < p->lds.total) {
+    delete p;
+    return fail(WAB_E_INVALID, "wab_policy_create: the device's LDS is smaller than the kernel needs");
+  }
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(p->dims.NT1 > 4 ? reinterpret_cast<void*>(&wab::wab_policy_kernel<true>)
+                                            : reinterpret_cast<void*>(&wab::wab_policy_kernel<false>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+  void *w = nullptr, *b = nullptr;
+  if (e == hipSuccess) e = hipMalloc(&w, (size_t)p->dims.w_total * 2u);
+  if (e == hipSuccess) e = hipMalloc(&b, (size_t)p->dims.b_total * 4u);
+  if (e != hipSuccess) {
+    if (w) (void)hipFree(w);
+    delete p;
+    return fail(e == hipErrorOutOfMemory ? WAB_E_NOMEM : WAB_E_HIP,
+                std::string("wab_policy_create: ") + hipGetErrorString(e));
+  }
+  p->w = static_cast<uint16_t*>(w);
+  p->b = static_cast<float*>(b);
+  *out = p;
+  return WAB_OK;
+}
+
+int wab_policy_destroy(wab_policy* p) {
+  if (!p) return WAB_OK;
+  {
+    DeviceGuard guard(p->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(p->w);
+    (void)hipFree(p->b);
+  }
+  delete p;
+  return WAB_OK;
+}
+
+int wab_policy_load(wab_policy* p, const wab_policy_weights* wts, void* stream) {
+  g_err.clear();
+  if (!p || !wts) return fail(WAB_E_INVALID, "wab_policy_load: NULL argument");
+  if (!wts->w1 || !wts->b1 || !wts->w2 || !wts->b2 || !wts->w3 || !wts->b3 || !wts->wa || !wts->ba || !wts->wv ||
+      !wts->bv)
+    return fail(WAB_E_INVALID, "wab_policy_load: every weight and bias pointer must be set");
+  wab::PolicyPackParams pp;
+  pp.d = p->dims;
+  pp.w1 = wts->w1; pp.b1 = wts->b1; pp.w2 = wts->w2; pp.b2 = wts->b2; pp.w3 = wts->w3; pp.b3 = wts->b3;
+  pp.wa = wts->wa; pp.ba = wts->ba; pp.wv = wts->wv; pp.bv = wts->bv;
+  pp.w = p->w;
+  pp.b = p->b;
+  DeviceGuard guard(p->device);
+  const unsigned blocks = (unsigned)std::min<uint32_t>((p->dims.w_total + 255u) / 256u, 1024u);
+  hipLaunchKernelGGL(wab::wab_policy_pack, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pp);
+  HIP_TRY(hipGetLastError());
+  p->loaded = true;
+  return WAB_OK;
+}
+
+int wab_policy_act(wab_handle* h, wab_policy* p, const float* features, int8_t* actions, float* probs,
+                   float* value, void* stream) {
+  g_err.clear();
+  if (!h || !p || !features || !actions) return fail(WAB_E_INVALID, "wab_policy_act: NULL argument");
+  if (p->device != h->device)
+    return fail(WAB_E_INVALID, "wab_policy_act: the policy is on device " + std::to_string(p->device) +
+                                   ", the handle on device " + std::to_string(h->device));
+  if (p->dims.A != h->p.n_actions)
+    return fail(WAB_E_INVALID, "wab_policy_act: the policy has " + std::to_string(p->dims.A) +
+                                   " actions, the handle's options " + std::to_string(h->p.n_actions));
+  if (!p->loaded) return fail(WAB_E_STATE, "wab_policy_act: call wab_policy_load first");
+  if (!h->reset_done) return fail(WAB_E_STATE, "wab_policy_act: call wab_reset first (no env has an episode yet)");
+  if ((reinterpret_cast<uintptr_t>(features) & 3u) != 0 || (probs && (reinterpret_cast<uintptr_t>(probs) & 3u) != 0) ||
+      (value && (reinterpret_cast<uintptr_t>(value) & 3u) != 0))
+    return fail(WAB_E_INVALID, "wab_policy_act: features, probs and value must be 4-byte aligned");
+  if (h->p.B == 0) return WAB_OK;
+  wab::PolicyParams pp;
+  pp.d = p->dims;
+  pp.lds = p->lds;
+  pp.seed = h->p.seed;
+  pp.env_base = h->p.env_base;
+  pp.B = h->p.B;
+  pp.hdr = h->p.hdr;
+  pp.features = features;
+  pp.actions = actions;
+  pp.probs = probs;
+  pp.value = value;
+  pp.w = p->w;
+  pp.b = p->b;
+  DeviceGuard guard(h->device);
+  const dim3 grid((unsigned)((h->p.B + wab::kPolicyEnvs - 1) / wab::kPolicyEnvs));
+  if (p->dims.NT1 > 4)  // h1 > 128: two layer-1 tiles per wave
+    hipLaunchKernelGGL(wab::wab_policy_kernel<true>, grid, dim3(256), p->lds.total, (hipStream_t)stream, pp);
+  else
+    hipLaunchKernelGGL(wab::wab_policy_kernel<false>, grid, dim3(256), p->lds.total, (hipStream_t)stream, pp);
+  HIP_TRY(hipGetLastError());
   return WAB_OK;
 }
 

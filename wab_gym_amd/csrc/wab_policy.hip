@@ -1,0 +1,320 @@
+// wab_policy.hip — the actor-critic policy of actor_critic.py:54-97 for inference, with the
+// action sampled in the same launch (wab_policy_act), and the weight pack kernel
+// (wab_policy_load).  gfx950.
+//
+// Network: three Linear + leaky_relu(0.01) layers, clamp(-4, 4) after the third, a softmax
+// action head and a one-unit value head; F >= 1 inputs, widths h1, h2, h3 in 1..256, A = 2..8
+// actions, all runtime (zero padding to the MFMA tile).
+//
+// Numeric contract (wab_gym_amd/policy.py reference_forward states the same in torch):
+//   * every matmul operand is bf16, rounded to nearest even: the input features, the weights
+//     (once, by the pack kernel) and the hidden activations after bias, leaky_relu and clamp;
+//   * products are accumulated in fp32 by v_mfma_f32_32x32x16_bf16 (the order of the sum is the
+//     instruction's; k-steps of 16 in ascending order);
+//   * bias add, leaky_relu (x >= 0 ? x : 0.01f * x), clamp, the softmax (max-subtracted, expf,
+//     the sum over k = 0, 1, ... in order, one divide 1 / sum, p_k = e_k * that) and the value
+//     are fp32; features that are 0 or 1 (wab_step_features) are exact in bf16;
+//   * the reference's + U(0, 1) / 100 input noise (actor_critic.py:189) is not reproduced.
+// Sampling: u = U * 2^-53, U the 53-bit keyed draw of (seed, global env id, the env's current
+// episode, site 11, the env's current turn, x = 0, y = 0, k = 0), episode and turn read from the
+// handle's state; action = #{k < A - 1 : c_k <= u}, c_k the running sum in double, k = 0, 1, ...,
+// of the fp32 probabilities written out: an exact function of probs and u.
+//
+// Shape: a workgroup of four waves takes 128 envs.  The input features are staged in LDS as
+// bf16 in chunks of KC columns (PolicyLds), each wave loading rows with one dword per lane
+// (rows are 4-byte aligned only; consecutive lanes read consecutive columns).  In the hidden
+// layers the waves split the 32-unit output tiles (tile t on wave t & 3) and each takes all four
+// 32-env tiles through it, so every weight fragment (one coalesced 16-byte load per lane from
+// the packed image, L2-resident) is read once per 128 envs; a pass's fragments are all requested
+// before the feature loads or the barrier that precede their use (pol_load_frags).  Units are the MFMA's rows and envs
+// its columns: a lane then holds four consecutive units of one env per register group, which it
+// stores to the next layer's LDS image as one 8-byte word.  The heads are one tile; each wave
+// takes it for its own 32 envs and lanes 0..31 finish the softmax and the draw.
+#include <hip/hip_runtime.h>
+
+#include "wab_policy.h"
+#include "wab_device.h"
+
+namespace wab {
+
+typedef __bf16 pol_bf16x8 __attribute__((ext_vector_type(8)));
+typedef float pol_f32x16 __attribute__((ext_vector_type(16)));
+
+// float32 -> bf16 bits, round to nearest even (NaN -> the quiet NaN 0x7FC0, as torch does)
+__host__ __device__ inline uint32_t pol_bf16(float f) {
+  uint32_t u = __builtin_bit_cast(uint32_t, f);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return u >> 16;
+}
+
+__device__ __forceinline__ pol_bf16x8 pol_frag(uint4 v) { return __builtin_bit_cast(pol_bf16x8, v); }
+
+// ------------------------------------------------------------------------ weight pack
+__device__ __forceinline__ void pack_layer(const float* __restrict__ W, int N, int K, int KS,
+                                           uint16_t* __restrict__ dst, uint32_t i) {
+  // i indexes the layer's image: ((nt * KS + ks) * 64 + lane) * 8 + j
+  const uint32_t j = i & 7u, lane = (i >> 3) & 63u, f = i >> 9;
+  const int nt = (int)(f / (uint32_t)KS), ks = (int)(f % (uint32_t)KS);
+  const int n = 32 * nt + (int)(lane & 31u), k = 16 * ks + 8 * (int)(lane >> 5) + (int)j;
+  dst[i] = (uint16_t)((n < N && k < K) ? pol_bf16(W[(size_t)n * (size_t)K + (size_t)k]) : 0u);
+}
+
+__global__ __launch_bounds__(256) void wab_policy_pack(PolicyPackParams p) {
+  const PolicyDims& d = p.d;
+  const uint32_t stride = gridDim.x * 256u;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < d.w_total; i += stride) {
+    if (i < d.w2) pack_layer(p.w1, d.h1, d.F, d.KS1, p.w + d.w1, i - d.w1);
+    else if (i < d.w3) pack_layer(p.w2, d.h2, d.h1, d.KS2, p.w + d.w2, i - d.w2);
+    else if (i < d.wh) pack_layer(p.w3, d.h3, d.h2, d.KS3, p.w + d.w3, i - d.w3);
+    else {
+      // the head tile: rows 0 .. A-1 of the action head, row 8 the value head
+      const uint32_t e = i - d.wh, j = e & 7u, lane = (e >> 3) & 63u, ks = e >> 9;
+      const int n = (int)(lane & 31u), k = 16 * (int)ks + 8 * (int)(lane >> 5) + (int)j;
+      float v = 0.0f;
+      if (k < d.h3) {
+        if (n < d.A) v = p.wa[(size_t)n * (size_t)d.h3 + (size_t)k];
+        else if (n == kPolicyMaxActions) v = p.wv[k];
+      }
+      p.w[i] = (uint16_t)pol_bf16(v);
+    }
+  }
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < d.b_total; i += stride) {
+    float v = 0.0f;
+    if (i < d.b2) { if ((int)(i - d.b1) < d.h1) v = p.b1[i - d.b1]; }
+    else if (i < d.b3) { if ((int)(i - d.b2) < d.h2) v = p.b2[i - d.b2]; }
+    else if (i < d.bh) { if ((int)(i - d.b3) < d.h3) v = p.b3[i - d.b3]; }
+    else {
+      const int n = (int)(i - d.bh);
+      if (n < d.A) v = p.ba[n];
+      else if (n == kPolicyMaxActions) v = p.bv[0];
+    }
+    p.b[i] = v;
+  }
+}
+
+// ------------------------------------------------------------------------ forward + sample
+// A tile's weight fragments of one pass (at most kPolicyMaxKs k-steps: KC <= 256, widths <= 256)
+// are all requested at once, before the work that precedes their use (layer 1: the chunk's
+// feature loads; later layers: the barrier), so that their L2 latency is not paid per k-step:
+// four k-steps of MFMAs are ~0.2 us, less than one L2 round trip.  wfrag points at this lane's
+// 16 bytes of the first fragment (fragments 64 uint4 apart).
+constexpr int kPolicyMaxKs = 16;
+__device__ __forceinline__ void pol_load_frags(uint4 (&wf)[kPolicyMaxKs], const uint4* __restrict__ wfrag, int nks) {
+#pragma unroll
+  for (int i = 0; i < kPolicyMaxKs; ++i) {
+    wf[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (i < nks) wf[i] = wfrag[(size_t)i * 64u];  // (uniform)
+  }
+}
+
+// acc[mt] += W(tile, the pass's nks k-steps) * X(32-env tile mt): x points at this lane's 16 bytes
+// of k-step 0 of env tile 0 (row r = lane & 31, column 8 (lane >> 5)); env tiles are 32 * pitch
+// elements apart
+__device__ __forceinline__ void pol_mma(pol_f32x16 (&acc)[4], const uint4 (&wf)[kPolicyMaxKs], int nks,
+                                        const uint16_t* x, int pitch) {
+#pragma unroll
+  for (int i = 0; i < kPolicyMaxKs; ++i) {
+    if (i < nks) {  // (uniform)
+      pol_bf16x8 b[4];
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+        b[mt] = pol_frag(*reinterpret_cast<const uint4*>(x + (size_t)(mt * 32) * (size_t)pitch + (size_t)(i * 16)));
+      const pol_bf16x8 a = pol_frag(wf[i]);
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[mt], acc[mt], 0, 0, 0);
+    }
+  }
+}
+
+// bias, leaky_relu (and the clamp after layer 3), bf16, into the next layer's LDS image: register
+// group g of a lane holds units 32 tile + 8 g + 4 (lane >> 5) + 0..3 of env 32 mt + (lane & 31)
+template <bool CLAMP>
+__device__ __forceinline__ void pol_store(const pol_f32x16 (&acc)[4], const float* __restrict__ bias, int tile,
+                                          uint16_t* xn, int pitch, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int n = 32 * tile + 8 * g + 4 * h;
+    const float4 bv = *reinterpret_cast<const float4*>(bias + n);
+    const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      uint32_t o[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float v = acc[mt][4 * g + i] + bb[i];
+        v = v >= 0.0f ? v : 0.01f * v;
+        if (CLAMP) v = fminf(fmaxf(v, -4.0f), 4.0f);
+        o[i] = pol_bf16(v);
+      }
+      uint2 w;
+      w.x = o[0] | (o[1] << 16);
+      w.y = o[2] | (o[3] << 16);
+      *reinterpret_cast<uint2*>(xn + (size_t)(mt * 32 + r) * (size_t)pitch + (size_t)n) = w;
+    }
+  }
+}
+
+__device__ __forceinline__ void pol_zero(pol_f32x16 (&acc)[4]) {
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[mt][i] = 0.0f;
+}
+
+// a hidden layer past the first: wave w takes tiles w and w + 4 through all 128 envs; wf holds
+// tile w's fragments, requested by the caller before the barrier
+template <bool CLAMP>
+__device__ __forceinline__ void pol_layer(uint4 (&wf)[kPolicyMaxKs], const uint4* __restrict__ wimg,
+                                          const float* __restrict__ bias, int NT, int KS, const uint16_t* xin,
+                                          int pitch_in, uint16_t* xout, int pitch_out, int wave, int lane) {
+  const int r = lane & 31, h = lane >> 5;
+  for (int t = wave; t < NT; t += 4) {
+    if (t != wave) pol_load_frags(wf, wimg + (size_t)t * (size_t)KS * 64u + (size_t)lane, KS);
+    pol_f32x16 acc[4];
+    pol_zero(acc);
+    pol_mma(acc, wf, KS, xin + (size_t)r * (size_t)pitch_in + 8 * h, pitch_in);
+    pol_store<CLAMP>(acc, bias, t, xout, pitch_out, lane);
+  }
+}
+
+// TWO: h1 > 128, a wave holds two layer-1 tiles across the chunks (64 more accumulator registers:
+// that instance takes one wave per SIMD's registers, the common one stays at two)
+template <bool TWO>
+__global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_kernel(PolicyParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pol_smem[];
+  uint16_t* const regA = reinterpret_cast<uint16_t*>(pol_smem);
+  uint16_t* const regB = reinterpret_cast<uint16_t*>(pol_smem + p.lds.off_b);
+  const PolicyDims& d = p.d;
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  const int r = lane & 31, h = lane >> 5;
+  const int64_t env0 = (int64_t)blockIdx.x * kPolicyEnvs;
+  const int n_env = (int)(p.B - env0 < kPolicyEnvs ? p.B - env0 : kPolicyEnvs);
+  const uint4* const wimg = reinterpret_cast<const uint4*>(p.w);
+
+  // the sampling lane's env header, asked for early (lanes 0..31 of wave w: env 32 w + lane)
+  const int my_env = 32 * wave + r;
+  const bool sampler = h == 0 && my_env < n_env;
+  uint4 hdr = make_uint4(0u, 0u, 0u, 0u);
+  if (sampler) hdr = p.hdr[env0 + my_env];
+
+  // ---- layer 1: chunks of KC input columns through LDS; wave w holds tiles w and w + 4
+  pol_f32x16 acc0[4], acc1[4];
+  pol_zero(acc0);
+  if (TWO) pol_zero(acc1);
+  const int KC = p.lds.KC, pitch_in = p.lds.pitch_in;
+  const int kpad = 16 * d.KS1;
+  uint4 wf[kPolicyMaxKs];
+  const uint4* const w1t = wimg + (d.w1 >> 3) + (size_t)wave * (size_t)d.KS1 * 64u + (size_t)lane;
+  for (int c = 0; c < p.lds.n_chunks; ++c) {
+    const int k0 = c * KC;
+    const int kn = kpad - k0 < KC ? kpad - k0 : KC;  // columns of this chunk (a multiple of 16)
+    const int ks0 = k0 >> 4, nks = kn >> 4;
+    if (wave < d.NT1) pol_load_frags(wf, w1t + (size_t)ks0 * 64u, nks);
+    if (c > 0) __syncthreads();  // the last chunk's fragments have been read
+    // wave w loads rows w, w + 4, ...: a lane takes one column of 16 rows at a time, the 16 loads
+    // issued together (addresses clamped into the batch, so none is conditional; rows past the
+    // batch and the pad columns are stored as zeros)
+    for (int kl = lane; kl < kn; kl += 64) {
+      const int k = k0 + kl;
+      const bool kin = k < d.F;
+      const float* col = p.features + (size_t)env0 * (size_t)d.F + (size_t)(kin ? k : d.F - 1);
+      constexpr int kRows = 16;  // (32 in flight measured the same: 55.9-56.2 against 55.8-56.0 us)
+      for (int eb = 0; eb < kPolicyEnvs / 4; eb += kRows) {
+        float v[kRows];
+#pragma unroll
+        for (int i = 0; i < kRows; ++i) {
+          const int e = wave + 4 * (eb + i);
+          v[i] = col[(size_t)(e < n_env ? e : n_env - 1) * (size_t)d.F];
+        }
+#pragma unroll
+        for (int i = 0; i < kRows; ++i) {
+          const int e = wave + 4 * (eb + i);
+          regA[(size_t)e * (size_t)pitch_in + (size_t)kl] = (uint16_t)((kin && e < n_env) ? pol_bf16(v[i]) : 0u);
+        }
+      }
+    }
+    __syncthreads();
+    const uint16_t* x = regA + (size_t)r * (size_t)pitch_in + 8 * h;
+    if (wave < d.NT1) pol_mma(acc0, wf, nks, x, pitch_in);
+    if (TWO && wave + 4 < d.NT1) {
+      pol_load_frags(wf, w1t + ((size_t)4 * (size_t)d.KS1 + (size_t)ks0) * 64u, nks);
+      pol_mma(acc1, wf, nks, x, pitch_in);
+    }
+  }
+  if (wave < d.NT1) pol_store<false>(acc0, p.b + d.b1, wave, regB, p.lds.pitch1, lane);
+  if (TWO && wave + 4 < d.NT1) pol_store<false>(acc1, p.b + d.b1, wave + 4, regB, p.lds.pitch1, lane);
+  const uint4* const w2 = wimg + (d.w2 >> 3), * const w3 = wimg + (d.w3 >> 3);
+  if (wave < d.NT2) pol_load_frags(wf, w2 + (size_t)wave * (size_t)d.KS2 * 64u + (size_t)lane, d.KS2);
+  __syncthreads();  // X1 complete; region A free
+
+  // ---- layer 2: X1 (region B) -> X2 (region A); layer 3: X2 -> X3 (region B), clamped
+  pol_layer<false>(wf, w2, p.b + d.b2, d.NT2, d.KS2, regB, p.lds.pitch1, regA, p.lds.pitch2, wave, lane);
+  if (wave < d.NT3) pol_load_frags(wf, w3 + (size_t)wave * (size_t)d.KS3 * 64u + (size_t)lane, d.KS3);
+  __syncthreads();
+  pol_layer<true>(wf, w3, p.b + d.b3, d.NT3, d.KS3, regA, p.lds.pitch2, regB, p.lds.pitch3, wave, lane);
+  pol_load_frags(wf, wimg + (d.wh >> 3) + (size_t)lane, d.KS4);
+  __syncthreads();
+
+  // ---- heads: one tile (rows 0..7 action logits, row 8 the value), wave w on envs 32 w ..
+  pol_f32x16 acc = {};
+  {
+    const uint16_t* x = regB + (size_t)(32 * wave + r) * (size_t)p.lds.pitch3 + 8 * h;
+#pragma unroll
+    for (int i = 0; i < kPolicyMaxKs; ++i) {
+      if (i < d.KS4) {  // (uniform)
+        const pol_bf16x8 b = pol_frag(*reinterpret_cast<const uint4*>(x + (size_t)(i * 16)));
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pol_frag(wf[i]), b, acc, 0, 0, 0);
+      }
+    }
+  }
+  // lane (r, h) holds rows 4 h + 0..3 in registers 0..3 and rows 8 + 4 h + 0..3 in registers 4..7
+  // of env column r: lane (r, 0) takes rows 4..7 from lane (r, 1)
+  float lg[kPolicyMaxActions];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    lg[i] = acc[i];
+    lg[4 + i] = __shfl(acc[i], (lane + 32) & 63, 64);
+  }
+  if (!sampler) return;
+  const float* bh = p.b + d.bh;
+  const int A = d.A;
+  const float val = acc[4] + bh[kPolicyMaxActions];
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < kPolicyMaxActions; ++k) {
+    lg[k] = lg[k] + bh[k];
+    if (k < A) m = fmaxf(m, lg[k]);
+  }
+  float s = 0.0f;
+#pragma unroll
+  for (int k = 0; k < kPolicyMaxActions; ++k) {
+    lg[k] = k < A ? expf(lg[k] - m) : 0.0f;
+    if (k < A) s = s + lg[k];
+  }
+  const float inv = 1.0f / s;
+  // the keyed draw (oracle/keyed_rng.py): site 11, the env's episode and turn, tile (0, 0), k = 0
+  const int64_t env = env0 + my_env;
+  const uint64_t ek = episode_key(p.seed, (uint64_t)(p.env_base + env), (uint64_t)hdr.w);
+  const uint64_t U = draw_U(0u, make_ts(SITE_POLICY, 0u, (int32_t)hdr.y), (uint32_t)ek, (uint32_t)(ek >> 32));
+  const double u = (double)U * 0x1p-53;
+  double c = 0.0;
+  int a = 0;
+#pragma unroll
+  for (int k = 0; k < kPolicyMaxActions; ++k) {
+    const float pk = lg[k] * inv;
+    if (k < A) {
+      if (p.probs) p.probs[(size_t)env * (size_t)A + (size_t)k] = pk;
+      c = c + (double)pk;
+      if (k < A - 1 && c <= u) a += 1;
+    }
+  }
+  p.actions[env] = (int8_t)a;
+  if (p.value) p.value[env] = val;
+}
+
+template __global__ void wab_policy_kernel<false>(PolicyParams p);
+template __global__ void wab_policy_kernel<true>(PolicyParams p);
+
+}  // namespace wab

@@ -80,6 +80,66 @@ class PragmaticObsWrapper:
             self.features.copy_(r["features"][-1])  # as after T step() calls
         return r["features"], r["reward"], r["done"].view(self.env._torch.bool), r["returns"]
 
+    def rollout_policy(self, policy, T, gamma=0.99, store_planes=False):
+        """T closed-loop steps of actor_critic.main's loop (actor_critic.py:185-200) on the env's
+        stream: step t's action is sampled by `policy` (a DevicePolicy) from step t's features
+        (wab_policy_act), then the env steps (wab_step_features): two launches per step, no host
+        synchronisation, so the whole call can be captured in a graph.  It starts from the features
+        of the current observation (recomputed from the env's obs planes when they are valid, else
+        the wrapper's own `features` as its last reset()/step()/rollout left them).  Returns a
+        dict: features [T,B,F] f32 (features[t] is what actions[t] was chosen from), actions [T,B]
+        int8, reward [T,B] f32, done [T,B] u8, value [T,B] f32 and returns [T,B] f32
+        (discounted_returns(env=...), R after the last step = 0).  Afterwards the wrapper's
+        `features` and the env's scalars, reward and done show the last step."""
+        from .env import BatchedWolvesAndBushesEnv
+
+        env = self.env
+        if type(self) is not PragmaticObsWrapper or type(env) is not BatchedWolvesAndBushesEnv:
+            raise NotImplementedError("rollout_policy() runs PragmaticObsWrapper over a plain "
+                                      "BatchedWolvesAndBushesEnv (the egocentric observation and "
+                                      "EpisodeMonitor's statistics are made per step())")
+        if env._term is not None:
+            raise NotImplementedError("rollout_policy() returns no terminal observations "
+                                      "(return_terminal=True)")
+        if not env._reset_once:
+            raise RuntimeError("call reset() before rollout_policy()")
+        if policy.env is not env or policy.in_features != self.feature_dim:
+            raise ValueError("the policy was made for another env or feature length")
+        t = env._torch
+        T, B, F = int(T), env.num_envs, self.feature_dim
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        dev = env.device
+        feats = t.empty((T, B, F), dtype=t.float32, device=dev)
+        actions = t.empty((T, B), dtype=t.int8, device=dev)
+        value = t.empty((T, B), dtype=t.float32, device=dev)
+        rew = t.empty((T, B), dtype=t.float32, device=dev)
+        done = t.empty((T, B), dtype=t.uint8, device=dev)
+        out = {"features": feats, "actions": actions, "reward": rew, "done": done, "value": value,
+               "returns": t.empty((T, B), dtype=t.float32, device=dev)}
+        if T == 0:
+            return out
+        if env._planes_valid:
+            self.observation()
+        feats[0].copy_(self.features)
+        L = _lib.load()
+        o = env._obs["struct"]
+        st = o if store_planes else _lib.WabObs(None, o.food_turns, o.role, o.status)
+        direct = (B * F) % 4 == 0  # every step's feature slice is 16-byte aligned
+        for k in range(T):
+            policy.act(feats[k], out=actions[k], value=value[k])
+            nxt = feats[k + 1] if direct and k + 1 < T else self.features
+            _lib.check(L.wab_step_features(env._h, actions[k].data_ptr(), ctypes.addressof(st),
+                                           rew[k].data_ptr(), done[k].data_ptr(), nxt.data_ptr(),
+                                           env._stream()), "wab_step_features")
+            if not direct and k + 1 < T:
+                feats[k + 1].copy_(self.features)
+        env.reward.copy_(rew[T - 1])
+        env.done.copy_(done[T - 1])
+        env._planes_valid = bool(store_planes)
+        discounted_returns(rew, done, gamma=gamma, out=out["returns"], env=env)
+        return out
+
     def step(self, actions):
         if self.env._term is None and type(self) is PragmaticObsWrapper:
             # one kernel: the step and the features of its obs (wab_step_features)
