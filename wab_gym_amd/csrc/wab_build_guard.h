@@ -19,6 +19,22 @@
 #endif
 #endif
 
+// A/B switches of the small kernel's rollout work (results identical either way; the product
+// build takes the defaults):
+//   WAB_RULES_INSTANCE  1 = default-options handles take the instances with the rules as
+//                       constants (wab_default_rules.h); 0 = every handle takes the generic ones
+//   WAB_ROLL_HOIST      1 = those instances' multi-step build reads its parameters once per launch
+//                       and advances the I/O slices by one step; 0 = re-read at every step
+#ifndef WAB_RULES_INSTANCE
+#define WAB_RULES_INSTANCE 1
+#endif
+#ifndef WAB_ROLL_HOIST
+#define WAB_ROLL_HOIST 1
+#endif
+#if defined(WAB_PRODUCT_BUILD) && (WAB_RULES_INSTANCE != 1 || WAB_ROLL_HOIST != 1)
+#error "WAB_RULES_INSTANCE / WAB_ROLL_HOIST are A/B switches: the product build takes their defaults"
+#endif
+
 #if defined(WAB_DIAGNOSTIC_BUILD) && !defined(__HIP_DEVICE_COMPILE__)
 // (weak: every translation unit of a diagnostic build defines it)
 extern "C" __attribute__((weak, visibility("default"))) int wab_diagnostic_build(void) { return 1; }

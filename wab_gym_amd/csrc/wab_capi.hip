@@ -23,7 +23,7 @@
 namespace wab {
 template <int MODE, int SLOTS, bool SMALL>
 __global__ void wab_kernel(Params p);
-template <int SLOTS, int G, bool FEAT, bool ROLL>
+template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES = false>
 __global__ void wab_step_small(Params p);
 template <int MODE, int SLOTS>
 __global__ void wab_step_wide(Params p);
@@ -64,6 +64,7 @@ struct wab_handle {
   uint32_t* ego_diamond = nullptr;
   int ego_cap = 0, ego_n_diamond = 0;
   bool small_g11 = false;    // the small kernel's 11x11 specialisation (geometry_11)
+  bool small_rules = false;  // ... with the default options' rules as constants too (default_rules)
   wab::RewardTable rewards;  // exact doubles of the rewards a step returns (n = 0: ambiguous)
   size_t wide_lds_bytes = 0;  // LDS per workgroup of the wide kernel (see wab_create)
   size_t wide_roll_lds_bytes = 0;  // ... of its multi-step build (wab_rollout_wide)
@@ -278,7 +279,11 @@ void launch_rollout_wide(int n_blocks, size_t lds, const Params& p, hipStream_t 
 }
 
 template <int G, bool ROLL = false>
-void* small_kernel_ptr(int slots) {
+void* small_kernel_ptr(int slots, bool rules = false) {
+#if WAB_RULES_INSTANCE
+  if constexpr (G == 11)
+    if (slots == 8 && rules) return reinterpret_cast<void*>(&wab::wab_step_small<8, 11, false, ROLL, true>);
+#endif
   switch (slots) {
     case 8: return reinterpret_cast<void*>(&wab::wab_step_small<8, G, false, ROLL>);
     case 16: return reinterpret_cast<void*>(&wab::wab_step_small<16, G, false, ROLL>);
@@ -291,6 +296,14 @@ template <int G, bool FEAT = false, bool ROLL = false>
 void launch_small(wab_handle* h, const Params& p, hipStream_t stream, size_t lds_bytes = 0) {
   const dim3 grid(h->n_blocks), block(256);  // one 64-env group per workgroup, four waves
   const size_t lds = lds_bytes ? lds_bytes : FEAT ? h->small_feat_lds_bytes : h->small_lds_bytes;
+#if WAB_RULES_INSTANCE
+  if constexpr (G == 11) {
+    if (h->small_rules) {  // (8 slots, default_rules)
+      hipLaunchKernelGGL((wab::wab_step_small<8, 11, FEAT, ROLL, true>), grid, block, lds, stream, p);
+      return;
+    }
+  }
+#endif
   switch (h->slots) {
     case 8: hipLaunchKernelGGL((wab::wab_step_small<8, G, FEAT, ROLL>), grid, block, lds, stream, p); break;
     case 16: hipLaunchKernelGGL((wab::wab_step_small<16, G, FEAT, ROLL>), grid, block, lds, stream, p); break;
@@ -342,6 +355,136 @@ void split_threshold(uint64_t T, uint32_t* th, uint32_t* tl) {
     *th = (uint32_t)(T >> 21);
     *tl = (uint32_t)(T & 0x1FFFFFu);
   }
+}
+
+// The rule fields of the parameter block as resolved from the options (the geometry fields W, H,
+// WH, R already set; thr_host the bush threshold table, [max_berries]); gap_out: the spawn-set
+// gap table for the device copy.
+void resolve_rules(const wab_config* c, const uint64_t* thr_host, Params& p, std::vector<uint64_t>* gap_out) {
+  p.n_actions = n_actions_of(c);
+  for (int a = 0; a < 6; ++a) p.act_role[a] = -1;  // moves: wab::decode_action (up right down left)
+  if (c->gatherer_only) p.act_role[4] = 1;       // wab_env.py:149-159
+  else if (c->lookout_only) p.act_role[4] = 0;   // :160-170
+  else { p.act_role[4] = 1; p.act_role[5] = 0; } // :171-182
+  // thresholds on the 53-bit draw U (u = U * 2^-53), each as a ">= T" test
+  const uint64_t keep_ge = (uint64_t)std::floor(std::ldexp(c->wolf_chance_to_despawn, 53)) + 1;  // u > p (:263)
+  const uint64_t spawn_ge = (uint64_t)std::ceil(std::ldexp(c->chance_wolf_on_square / 2.0, 53));  // u < p/2 (:573)
+  p.max_berries = c->max_berries_per_bush;
+  p.bush_power = (float)c->bush_power;
+  const uint64_t bush_ge = p.max_berries > 0 ? thr_host[0] : (1ull << 53);          // food > 0
+  split_threshold(keep_ge, &p.keep_th, &p.keep_tl);
+  split_threshold(bush_ge, &p.bush_th, &p.bush_tl);
+  // keyed spawn sets (oracle/keyed_rng.py gap_thresholds): gap[g] = floor((1 - q)^g 2^53),
+  // the power a running product in double (1 - q exact), so the oracle gets the same table
+  p.n_gap = wab::kGapChunk;
+  std::vector<uint64_t> gap_own;
+  std::vector<uint64_t>& gap_host = gap_out ? *gap_out : gap_own;
+  gap_host.assign((size_t)p.n_gap + 1, 0);
+  {
+    const double omq = std::ldexp((double)((1ull << 53) - spawn_ge), -53);
+    double q = 1.0;
+    gap_host[0] = 1ull << 53;
+    for (int g = 1; g <= p.n_gap; ++g) {
+      q = q * omq;
+      gap_host[(size_t)g] = (uint64_t)std::floor(std::ldexp(q, 53));
+    }
+    p.gap_inv_l2 = spawn_ge > 0 ? (float)(1.0 / std::log2(omq)) : 0.0f;
+    auto last_chunk = [](int n) { return n > 0 ? (n - 1) % wab::kGapChunk + 1 : 0; };
+    split_threshold(gap_host[(size_t)wab::kGapChunk], &p.gap_full_th, &p.gap_full_tl);
+    split_threshold(gap_host[(size_t)last_chunk(p.R)], &p.gap_ring_th, &p.gap_ring_tl);
+    split_threshold(gap_host[(size_t)last_chunk(p.WH)], &p.gap_view_th, &p.gap_view_tl);
+  }
+  p.fill = 1.0 / (double)c->turns_to_fill_food;
+  p.hunger = 1.0 / (double)c->turns_to_empty_food;
+  p.r_turn = c->reward_per_turn;
+  p.r_killed = c->reward_for_being_killed;
+  p.r_starve = c->reward_for_starving;
+  p.r_finish = c->reward_for_finishing;
+  p.r_eat = c->reward_for_eating;
+  p.start_food = c->starting_food;
+  p.start_role = c->starting_role;
+  p.start_food_random = c->starting_food_random;
+  p.start_role_random = c->starting_role_random;
+  p.max_turns = c->max_turns;
+  p.turns_empty = c->turns_to_empty_food;
+  p.lookout_only = c->lookout_only;
+  p.restrict_view = c->restrict_view;
+  p.wolves_on = c->wolves;
+  p.wolves_can_move = c->wolves_can_move;
+  p.god_mode = c->god_mode;
+  p.autoreset = c->autoreset;
+  for (int i = 0; i < 11; ++i) {
+    p.mask_rows[0][i] = row_mask(kLookout[i]);
+    p.mask_rows[1][i] = row_mask(kGatherer[i]);
+  }
+  if (p.W == 11 && p.H == 11)
+    for (int r = 0; r < 2; ++r)
+      for (int i = 0; i < 11; ++i)
+        for (int j = 0; j < 11; ++j)
+          if ((p.mask_rows[r][i] >> j) & 1u) p.view121[r][(i * 11 + j) >> 5] |= 1u << ((i * 11 + j) & 31);
+}
+
+// The default options (include/wab.h's field comments; wab_gym_amd/options.py), a batched surface
+// with autoreset and every "0 = default" extension field at 0.
+wab_config wab_default_config() {
+  wab_config c;
+  std::memset(&c, 0, sizeof(c));
+  c.reward_per_turn = 0.0;
+  c.reward_for_being_killed = -1.0;
+  c.reward_for_starving = -1.0;
+  c.reward_for_finishing = 1.0;
+  c.reward_for_eating = 0.1;
+  c.lookout_only = 1;
+  c.starting_role = 1;
+  c.starting_food = 1.0;
+  c.max_turns = 80;
+  c.height = 11;
+  c.width = 11;
+  c.max_berries_per_bush = 200;
+  c.bush_power = 100.0;
+  c.turns_to_fill_food = 8;
+  c.turns_to_empty_food = 40;
+  c.wolf_spawn_margin = 1;
+  c.chance_wolf_on_square = 0.001;
+  c.wolf_chance_to_despawn = 0.05;
+  c.wolves = 1;
+  c.wolves_can_move = 1;
+  c.autoreset = 1;
+  return c;
+}
+
+// The default-rules instances of the small kernel (wab_step_small<8, 11, .., RULES = true>,
+// wab_default_rules.h) have the rule fields of the parameter block as constants.  A handle takes
+// them when each of those fields, as resolved from its options, is bit-equal to the same field
+// resolved from wab_default_config(): the comparison is against the resolved default, not the
+// header's constants, so a wrong constant there fails the default options' parity tests and
+// never deselects the instance.
+bool default_rules(const Params& p) {
+  static const Params d = [] {
+    const wab_config c = wab_default_config();
+    Params q;
+    std::memset(&q, 0, sizeof(q));
+    q.W = c.width;
+    q.H = c.height;
+    q.WH = q.W * q.H;
+    q.R = (q.W + 2 * c.wolf_spawn_margin) * (q.H + 2 * c.wolf_spawn_margin) - q.WH;
+    std::vector<uint64_t> thr((size_t)c.max_berries_per_bush);
+    wab_bush_thresholds(c.bush_power, c.max_berries_per_bush, thr.data());
+    resolve_rules(&c, thr.data(), q, nullptr);
+    q.eaten_cap = resolved_eaten_capacity(&c);
+    return q;
+  }();
+#define WAB_SAME(field) (std::memcmp(&p.field, &d.field, sizeof(p.field)) == 0)
+  return WAB_SAME(n_actions) && WAB_SAME(act_role) && WAB_SAME(keep_th) && WAB_SAME(keep_tl) && WAB_SAME(bush_th) &&
+         WAB_SAME(bush_tl) && WAB_SAME(n_gap) && WAB_SAME(gap_inv_l2) && WAB_SAME(gap_full_th) &&
+         WAB_SAME(gap_full_tl) && WAB_SAME(gap_ring_th) && WAB_SAME(gap_ring_tl) && WAB_SAME(gap_view_th) &&
+         WAB_SAME(gap_view_tl) && WAB_SAME(max_berries) && WAB_SAME(bush_power) && WAB_SAME(fill) && WAB_SAME(hunger) &&
+         WAB_SAME(r_turn) && WAB_SAME(r_killed) && WAB_SAME(r_starve) && WAB_SAME(r_finish) && WAB_SAME(r_eat) &&
+         WAB_SAME(start_food) && WAB_SAME(start_role) && WAB_SAME(start_food_random) && WAB_SAME(start_role_random) &&
+         WAB_SAME(max_turns) && WAB_SAME(turns_empty) && WAB_SAME(lookout_only) && WAB_SAME(restrict_view) &&
+         WAB_SAME(wolves_on) && WAB_SAME(wolves_can_move) && WAB_SAME(god_mode) && WAB_SAME(autoreset) &&
+         WAB_SAME(mask_rows) && WAB_SAME(view121) && WAB_SAME(eaten_cap);
+#undef WAB_SAME
 }
 
 bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
@@ -535,14 +678,6 @@ int wab_create(const wab_config* c, int64_t batch, uint64_t seed, int64_t env_id
   p.SL = p.W > p.H ? p.W : p.H;
   p.magic_OB = (uint32_t)((1ull << 32) / (uint64_t)p.OB) + 1u;
   p.magic_CPE = p.OB >= 16 ? (uint32_t)((1ull << 32) / (uint64_t)(p.OB / 16)) + 1u : 1u;
-  p.n_actions = n_actions_of(c);
-  for (int a = 0; a < 6; ++a) p.act_role[a] = -1;  // moves: wab::decode_action (up right down left)
-  if (c->gatherer_only) p.act_role[4] = 1;       // wab_env.py:149-159
-  else if (c->lookout_only) p.act_role[4] = 0;   // :160-170
-  else { p.act_role[4] = 1; p.act_role[5] = 0; } // :171-182
-  // thresholds on the 53-bit draw U (u = U * 2^-53), each as a ">= T" test
-  const uint64_t keep_ge = (uint64_t)std::floor(std::ldexp(c->wolf_chance_to_despawn, 53)) + 1;  // u > p (:263)
-  const uint64_t spawn_ge = (uint64_t)std::ceil(std::ldexp(c->chance_wolf_on_square / 2.0, 53));  // u < p/2 (:573)
   p.max_berries = c->max_berries_per_bush;
   p.bush_power = (float)c->bush_power;
   // the caller's table (the Python host computes it with numpy), or the same table from libm
@@ -553,34 +688,8 @@ int wab_create(const wab_config* c, int64_t batch, uint64_t seed, int64_t env_id
     wab_bush_thresholds(c->bush_power, p.max_berries, thr_own.data());
     thr_host = thr_own.data();
   }
-  const uint64_t bush_ge = p.max_berries > 0 ? thr_host[0] : (1ull << 53);          // food > 0
-  split_threshold(keep_ge, &p.keep_th, &p.keep_tl);
-  split_threshold(bush_ge, &p.bush_th, &p.bush_tl);
-  // keyed spawn sets (oracle/keyed_rng.py gap_thresholds): gap[g] = floor((1 - q)^g 2^53),
-  // the power a running product in double (1 - q exact), so the oracle gets the same table
-  p.n_gap = wab::kGapChunk;
-  std::vector<uint64_t> gap_host((size_t)p.n_gap + 1);
-  {
-    const double omq = std::ldexp((double)((1ull << 53) - spawn_ge), -53);
-    double q = 1.0;
-    gap_host[0] = 1ull << 53;
-    for (int g = 1; g <= p.n_gap; ++g) {
-      q = q * omq;
-      gap_host[(size_t)g] = (uint64_t)std::floor(std::ldexp(q, 53));
-    }
-    p.gap_inv_l2 = spawn_ge > 0 ? (float)(1.0 / std::log2(omq)) : 0.0f;
-    auto last_chunk = [](int n) { return n > 0 ? (n - 1) % wab::kGapChunk + 1 : 0; };
-    split_threshold(gap_host[(size_t)wab::kGapChunk], &p.gap_full_th, &p.gap_full_tl);
-    split_threshold(gap_host[(size_t)last_chunk(p.R)], &p.gap_ring_th, &p.gap_ring_tl);
-    split_threshold(gap_host[(size_t)last_chunk(p.WH)], &p.gap_view_th, &p.gap_view_tl);
-  }
-  p.fill = 1.0 / (double)c->turns_to_fill_food;
-  p.hunger = 1.0 / (double)c->turns_to_empty_food;
-  p.r_turn = c->reward_per_turn;
-  p.r_killed = c->reward_for_being_killed;
-  p.r_starve = c->reward_for_starving;
-  p.r_finish = c->reward_for_finishing;
-  p.r_eat = c->reward_for_eating;
+  std::vector<uint64_t> gap_host;
+  resolve_rules(c, thr_host, p, &gap_host);
   {  // the step's possible rewards, accumulated from 0 as wab_env.py:251-340 does
     wab::RewardTable& t = h->rewards;
     t.n = 0;
@@ -602,33 +711,12 @@ int wab_create(const wab_config* c, int64_t batch, uint64_t seed, int64_t env_id
       }
     if (!ok) t.n = -1;
   }
-  p.start_food = c->starting_food;
-  p.start_role = c->starting_role;
-  p.start_food_random = c->starting_food_random;
-  p.start_role_random = c->starting_role_random;
-  p.max_turns = c->max_turns;
-  p.turns_empty = c->turns_to_empty_food;
-  p.lookout_only = c->lookout_only;
-  p.restrict_view = c->restrict_view;
-  p.wolves_on = c->wolves;
-  p.wolves_can_move = c->wolves_can_move;
-  p.god_mode = c->god_mode;
-  p.autoreset = c->autoreset;
-  for (int i = 0; i < 11; ++i) {
-    p.mask_rows[0][i] = row_mask(kLookout[i]);
-    p.mask_rows[1][i] = row_mask(kGatherer[i]);
-  }
   for (int c = 0; c < p.WH && c < 128; ++c) {  // bitmap masks for W*H <= 128 (bit c = i*H + j)
     const int j = c % p.H;
     p.small_masks[2][c >> 5] |= 1u << (c & 31);
     if (j == 0) p.small_masks[0][c >> 5] |= 1u << (c & 31);
     if (j == p.H - 1) p.small_masks[1][c >> 5] |= 1u << (c & 31);
   }
-  if (p.W == 11 && p.H == 11)
-    for (int r = 0; r < 2; ++r)
-      for (int i = 0; i < 11; ++i)
-        for (int j = 0; j < 11; ++j)
-          if ((p.mask_rows[r][i] >> j) & 1u) p.view121[r][(i * 11 + j) >> 5] |= 1u << ((i * 11 + j) & 31);
   h->snapshot_hash = snapshot_hash_of(c, thr_host);
   p.seed = seed;
   p.env_base = env_id_base;
@@ -651,6 +739,7 @@ int wab_create(const wab_config* c, int64_t batch, uint64_t seed, int64_t env_id
       h->small_feat_lds_bytes = (size_t)wab::small_layout(q).total * 4u;
     }
     h->small_g11 = geometry_11(p);
+    h->small_rules = WAB_RULES_INSTANCE && h->small_g11 && slots == 8 && default_rules(p);
   }
   if (h->lds_bytes > 160u * 1024u) {
     delete h;
@@ -735,8 +824,8 @@ int wab_create(const wab_config* c, int64_t batch, uint64_t seed, int64_t env_id
                               (int)h->wide_roll_lds_bytes);
   }
   if (e == hipSuccess && h->step_kernel == KERNEL_SMALL)
-    for (void* k : {h->small_g11 ? small_kernel_ptr<11>(slots) : small_kernel_ptr<0>(slots),
-                    h->small_g11 ? small_kernel_ptr<11, true>(slots) : small_kernel_ptr<0, true>(slots)})
+    for (void* k : {h->small_g11 ? small_kernel_ptr<11>(slots, h->small_rules) : small_kernel_ptr<0>(slots),
+                    h->small_g11 ? small_kernel_ptr<11, true>(slots, h->small_rules) : small_kernel_ptr<0, true>(slots)})
       if (e == hipSuccess)
         e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->small_lds_bytes);
   if (e == hipSuccess) e = hipDeviceSynchronize();

@@ -34,6 +34,7 @@
 // (wab_device.h spawn_hits): one draw per env-step and per new episode unless a wolf spawns.
 #include <hip/hip_runtime.h>
 
+#include "wab_default_rules.h"
 #include "wab_feat.h"
 
 #ifndef WAB_ROLL_THROTTLE  // (tuning A/B: 1 = W0 / W2 drain their obs stores at each step's start)
@@ -70,6 +71,27 @@ __device__ __forceinline__ uint4 m_pack(const M128& m) {
 }
 __device__ __forceinline__ M128 m_unpack(const uint4& v) { return m_make(v.x, v.y, v.z, v.w); }
 
+// COLD (the multi-step build of the default-rules instances, which keeps what every step reads
+// in registers across its step loop): the fields only the first or the last step or a rare path
+// reads (state arrays, tables, counters) come from a fresh copy of the kernel argument behind a
+// pointer made opaque at the point of use, so that their scalar loads stay in that branch and
+// out of the loop's every-step path.  Otherwise: p itself.
+template <bool COLD>
+__device__ __forceinline__ decltype(auto) cold_of(const Params& p) {
+#if __HIP_DEVICE_COMPILE__
+  if constexpr (COLD) {
+    typedef const Params __attribute__((address_space(4))) KernargParams;
+    KernargParams* pk = (KernargParams*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(pk));
+    return (*pk);
+  } else {
+    return (p);
+  }
+#else
+  return (p);
+#endif
+}
+
 // The part of the state every wave reads: header and action, the move (:252-258), the key.
 struct Head {
   bool active, valid_action;
@@ -89,10 +111,11 @@ struct HeadRaw {
 };
 // (loads are unconditional, from env 0 for an inactive lane, so that no branch splits a
 // wave's loads; head_decode zeroes an inactive lane's header)
+template <bool COLD = false>
 __device__ __forceinline__ HeadRaw head_fetch(const Params& p, int64_t g, bool active) {
   const int64_t gl = active ? g : 0;
   HeadRaw r;
-  r.hdr = p.hdr[gl];
+  r.hdr = cold_of<COLD>(p).hdr[gl];
   r.a = (int)p.actions[gl];
   return r;
 }
@@ -605,7 +628,7 @@ __device__ __forceinline__ uint4 new_header(const NewEp& n, const Head& h) {
 // needs only the new key (state, scalars, initial wolves = the view's spawn set at turn 0,
 // initialize_wolves :578-593, and the wolf and ostrich planes of its obs segment, which must
 // be clear); B the job's reset bush draws (bushmap, bush plane).  Returns the new role.
-template <int SLOTS, bool ROLL = false>
+template <int SLOTS, bool ROLL = false, bool COLD = false>
 __device__ __forceinline__ int new_episode_a(const Params& p, const Lds& s, const Head& h, int64_t g, uint32_t kb0,
                                              uint32_t kb1, uint32_t ebit, unsigned long long& wolf_of,
                                              bool last = true) {
@@ -632,17 +655,17 @@ __device__ __forceinline__ int new_episode_a(const Params& p, const Lds& s, cons
       const int b = __ffsll((unsigned long long)bits) - 1;
       bits &= bits - 1;
       if (n < SLOTS) {
-        if (store) p.wolves[(int64_t)n * p.B + g] = s.tiles[64 * half + b];
+        if (store) cold_of<COLD>(p).wolves[(int64_t)n * p.B + g] = s.tiles[64 * half + b];
         n += 1;
       } else {
         wolf_of += 1;
-        atomicAdd(&p.counters[CTR_WOLF_OVERFLOW_RESET], 1ull);
+        atomicAdd(&cold_of<COLD>(p).counters[CTR_WOLF_OVERFLOW_RESET], 1ull);
       }
     }
   }
   if (store) {
-    p.hdr[g] = make_uint4(xy_pack(0, 0), 0u, misc_pack((uint32_t)role2, 0u, (uint32_t)n, 0u, 0u), h.hdr.w + 1u);
-    p.food[g] = food2;
+    cold_of<COLD>(p).hdr[g] = make_uint4(xy_pack(0, 0), 0u, misc_pack((uint32_t)role2, 0u, (uint32_t)n, 0u, 0u), h.hdr.w + 1u);
+    cold_of<COLD>(p).food[g] = food2;
   }
   if constexpr (ROLL) {  // for the next step's waves (the wolves as cells: W2 takes the first SLOTS)
     const uint64_t fb = (uint64_t)__double_as_longlong(food2);
@@ -659,15 +682,16 @@ __device__ __forceinline__ int new_episode_a(const Params& p, const Lds& s, cons
   return role2;
 }
 
+template <bool COLD = false>
 __device__ __forceinline__ void new_episode_b(const Params& p, const Lds& s, int64_t g, int j, uint32_t ebit,
                                               int role2, bool store = true) {
   const M128 nbm = m_unpack(*reinterpret_cast<const uint4*>(&s.jbm[4 * j]));
   stream_or128(s.stream, ebit + (uint32_t)p.WH, p.restrict_view ? m_andn(nbm, view_mask_of(p, role2)) : nbm);
   if (!store) return;  // (ROLL: W0 takes the bitmap from jbm itself)
-  p.bushmap[g] = m_word<0>(nbm);
-  if (p.WHW > 1) p.bushmap[p.B + g] = m_word<1>(nbm);
-  if (p.WHW > 2) p.bushmap[2 * p.B + g] = m_word<2>(nbm);
-  if (p.WHW > 3) p.bushmap[3 * p.B + g] = m_word<3>(nbm);
+  cold_of<COLD>(p).bushmap[g] = m_word<0>(nbm);
+  if (p.WHW > 1) cold_of<COLD>(p).bushmap[p.B + g] = m_word<1>(nbm);
+  if (p.WHW > 2) cold_of<COLD>(p).bushmap[2 * p.B + g] = m_word<2>(nbm);
+  if (p.WHW > 3) cold_of<COLD>(p).bushmap[3 * p.B + g] = m_word<3>(nbm);
 }
 
 // --------------------------------------------------------------------------- fused features: early lines
@@ -692,11 +716,12 @@ __device__ __forceinline__ uint8_t reward_code(bool ate, int status, bool done) 
   return (uint8_t)((ate ? 1u : 0u) | (outcome << 1) | (done ? 8u : 0u));
 }
 
+template <bool COLD = false>
 __device__ __forceinline__ void rollout_returns(const Params& p, const Lds& s, int64_t g, bool active, int lane) {
   if (!active) return;
-  const double r_eat = p.r_eat, gamma = p.gamma;
+  const double r_eat = p.r_eat, gamma = cold_of<COLD>(p).gamma;
   const double rx[4] = {p.r_turn, p.r_finish, p.r_starve, p.r_killed};
-  double R = p.bootstrap ? (double)p.bootstrap[g] : 0.0;
+  double R = cold_of<COLD>(p).bootstrap ? (double)cold_of<COLD>(p).bootstrap[g] : 0.0;
   for (int t = p.n_steps - 1; t >= 0; --t) {
     const uint32_t c = s.rcode[64 * t + lane];
     const uint32_t o = (c >> 1) & 3u;
@@ -710,7 +735,7 @@ __device__ __forceinline__ void rollout_returns(const Params& p, const Lds& s, i
 }
 
 // --------------------------------------------------------------------------- W0: bushes
-template <int SLOTS, int G, bool ROLL = false>
+template <int SLOTS, int G, bool ROLL = false, bool COLD = false>
 __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const SmallLayout& L, uint32_t* lds, int lane,
                                                           CarryW0* carry = nullptr, int t = 0, bool last = true) {
   const Lds s = lds_of(lds, L);
@@ -740,20 +765,20 @@ __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const
       lrem[i] = carry->lrem[i];
     }
   } else {
-  hr = head_fetch(p, g, active);
+  hr = head_fetch<COLD>(p, g, active);
   {  // (unconditional: an inactive lane reads env 0; entries at or past eaten_cap read the
      // last entry and are never used, entry i counts only below the log length <= cap)
     const int64_t gl = active ? g : 0;
-    food = p.food[gl];
-    bw0 = p.bushmap[gl];
-    if (p.WHW > 1) bw1 = p.bushmap[p.B + gl];
-    if (p.WHW > 2) bw2 = p.bushmap[2 * p.B + gl];
-    if (p.WHW > 3) bw3 = p.bushmap[3 * p.B + gl];
+    food = cold_of<COLD>(p).food[gl];
+    bw0 = cold_of<COLD>(p).bushmap[gl];
+    if (p.WHW > 1) bw1 = cold_of<COLD>(p).bushmap[p.B + gl];
+    if (p.WHW > 2) bw2 = cold_of<COLD>(p).bushmap[2 * p.B + gl];
+    if (p.WHW > 3) bw3 = cold_of<COLD>(p).bushmap[3 * p.B + gl];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int64_t at = (int64_t)min(i, p.eaten_cap - 1) * p.B + gl;
-      lxy[i] = p.eaten_xy[at];
-      lrem[i] = p.eaten_rem[at];
+      lxy[i] = cold_of<COLD>(p).eaten_xy[at];
+      lrem[i] = cold_of<COLD>(p).eaten_rem[at];
     }
   }
   opaque_head(hr);
@@ -789,8 +814,8 @@ __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const
   if (ROLL && t == 0) {  // entries 4 .. kSmallLog - 1 into LDS, for the whole launch
     for (int i = 4; i < kSmallLog; ++i)
       if (active && i < ne && i < p.eaten_cap) {
-        s.elxy[(i - 4) * 64 + lane] = p.eaten_xy[(int64_t)i * p.B + g];
-        s.elrem[(i - 4) * 64 + lane] = p.eaten_rem[(int64_t)i * p.B + g];
+        s.elxy[(i - 4) * 64 + lane] = cold_of<COLD>(p).eaten_xy[(int64_t)i * p.B + g];
+        s.elrem[(i - 4) * 64 + lane] = cold_of<COLD>(p).eaten_rem[(int64_t)i * p.B + g];
       }
     __builtin_amdgcn_s_waitcnt(0);  // (settled inside the branch: no vmcnt wait at the join)
   }
@@ -841,8 +866,8 @@ __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (i0 + k < ne) {
-          exy[k] = p.eaten_xy[(int64_t)(i0 + k) * p.B + g];
-          erem[k] = p.eaten_rem[(int64_t)(i0 + k) * p.B + g];
+          exy[k] = cold_of<COLD>(p).eaten_xy[(int64_t)(i0 + k) * p.B + g];
+          erem[k] = cold_of<COLD>(p).eaten_rem[(int64_t)(i0 + k) * p.B + g];
         }
       scan_log(p, h, exy, erem, i0, ne, found, found_rem, gone);
     }
@@ -888,10 +913,10 @@ __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const
       s.elrem[(ne - 4) * 64 + lane] = (uint8_t)(rem - 1);
       ne += 1;
     } else if (found >= 0) {
-      p.eaten_rem[(int64_t)found * p.B + g] = (uint8_t)(rem - 1);
+      cold_of<COLD>(p).eaten_rem[(int64_t)found * p.B + g] = (uint8_t)(rem - 1);
     } else if (ne < p.eaten_cap) {
-      p.eaten_xy[(int64_t)ne * p.B + g] = h.cpos;
-      p.eaten_rem[(int64_t)ne * p.B + g] = (uint8_t)(rem - 1);
+      cold_of<COLD>(p).eaten_xy[(int64_t)ne * p.B + g] = h.cpos;
+      cold_of<COLD>(p).eaten_rem[(int64_t)ne * p.B + g] = (uint8_t)(rem - 1);
       ne += 1;
     } else {
       eaten_of += 1;
@@ -940,17 +965,18 @@ __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const
     if (!job) {
       bm = m_or(bm, m_andn(strip_of(p, s, lane, h.dir), gone));
       if (!ROLL || last) {
-        p.bushmap[g] = m_word<0>(bm);
-        if (p.WHW > 1) p.bushmap[p.B + g] = m_word<1>(bm);
-        if (p.WHW > 2) p.bushmap[2 * p.B + g] = m_word<2>(bm);
-        if (p.WHW > 3) p.bushmap[3 * p.B + g] = m_word<3>(bm);
-        p.food[g] = food;
+        cold_of<COLD>(p).bushmap[g] = m_word<0>(bm);
+        if (p.WHW > 1) cold_of<COLD>(p).bushmap[p.B + g] = m_word<1>(bm);
+        if (p.WHW > 2) cold_of<COLD>(p).bushmap[2 * p.B + g] = m_word<2>(bm);
+        if (p.WHW > 3) cold_of<COLD>(p).bushmap[3 * p.B + g] = m_word<3>(bm);
+        cold_of<COLD>(p).food[g] = food;
       }
     }
   }
-  if (eaten_of) atomicAdd(&p.counters[CTR_EATEN_OVERFLOW], eaten_of);
-  if (active && !h.valid_action) atomicAdd(&p.counters[CTR_BAD_ACTIONS], 1ull);
-  count_steps(p);
+  if (eaten_of) atomicAdd(&cold_of<COLD>(p).counters[CTR_EATEN_OVERFLOW], eaten_of);
+  if (active && !h.valid_action) atomicAdd(&cold_of<COLD>(p).counters[CTR_BAD_ACTIONS], 1ull);
+  if (blockIdx.x == 0 && threadIdx.x == 0)  // (count_steps)
+    atomicAdd(&cold_of<COLD>(p).counters[CTR_STEPS], (unsigned long long)p.B);
   const unsigned long long jm = __ballot(job);
   if (lane == 0 && jm) atomicAdd(&p.block_resets[blockIdx.x], (unsigned long long)__popcll(jm));  // (no-return: a load here would wait for the stores)
   if (ROLL && carry->prev_stream) store_units_nt<G, 128, 12, 0>(p, carry->prev_planes, carry->prev_stream, lane);
@@ -978,7 +1004,7 @@ __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const
         new_episode_b(p, s, g, j, ebit, role2);
       }
     }
-    if (wolf_of) atomicAdd(&p.counters[CTR_WOLF_OVERFLOW], wolf_of);
+    if (wolf_of) atomicAdd(&cold_of<COLD>(p).counters[CTR_WOLF_OVERFLOW], wolf_of);
     lds_barrier();  // B3
   }
   if constexpr (ROLL) {
@@ -1011,23 +1037,23 @@ __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         if (i < ne && i < p.eaten_cap) {
-          p.eaten_xy[(int64_t)i * p.B + g] = lxy[i];
-          p.eaten_rem[(int64_t)i * p.B + g] = (uint8_t)lrem[i];
+          cold_of<COLD>(p).eaten_xy[(int64_t)i * p.B + g] = lxy[i];
+          cold_of<COLD>(p).eaten_rem[(int64_t)i * p.B + g] = (uint8_t)lrem[i];
         }
       for (int i = 4; i < kSmallLog; ++i)
         if (i < ne && i < p.eaten_cap) {
-          p.eaten_xy[(int64_t)i * p.B + g] = s.elxy[(i - 4) * 64 + lane];
-          p.eaten_rem[(int64_t)i * p.B + g] = s.elrem[(i - 4) * 64 + lane];
+          cold_of<COLD>(p).eaten_xy[(int64_t)i * p.B + g] = s.elxy[(i - 4) * 64 + lane];
+          cold_of<COLD>(p).eaten_rem[(int64_t)i * p.B + g] = s.elrem[(i - 4) * 64 + lane];
         }
     }
   }
-  if (ROLL && last && p.returns) rollout_returns(p, s, g, active, lane);
+  if (ROLL && last && p.returns) rollout_returns<COLD>(p, s, g, active, lane);
   SMALL_STAMP(5);
   return jm;
 }
 
 // --------------------------------------------------------------------------- W1: draws
-template <int G, bool ROLL = false>
+template <int G, bool ROLL = false, bool COLD = false>
 __device__ __forceinline__ unsigned long long draws_wave(const Params& p, const SmallLayout& L, uint32_t* lds, int lane,
                                                          CarryHdr* carry = nullptr, int t = 0, bool last = true) {
   const Lds s = lds_of(lds, L);
@@ -1039,12 +1065,12 @@ __device__ __forceinline__ unsigned long long draws_wave(const Params& p, const 
     hr.hdr = carry->hdr;
     hr.a = act_of(s, lane);
   } else {
-  hr = head_fetch(p, g, g < p.B);
+  hr = head_fetch<COLD>(p, g, g < p.B);
   {  // every threshold load in flight at once (a copy loop waits for each before the next)
     const int nthr = p.max_berries;  // <= 255
     uint64_t tv[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) tv[k] = p.thresholds[min(64 * k + lane, max(nthr, 1) - 1)];  // (>= 1 entry)
+    for (int k = 0; k < 4; ++k) tv[k] = cold_of<COLD>(p).thresholds[min(64 * k + lane, max(nthr, 1) - 1)];  // (>= 1 entry)
     opaque_head(hr);
 #pragma unroll
     for (int k = 0; k < 4; ++k) opaque(tv[k]);
@@ -1115,7 +1141,7 @@ __device__ __forceinline__ unsigned long long draws_wave(const Params& p, const 
 }
 
 // --------------------------------------------------------------------------- W2: wolves
-template <int SLOTS, int G, bool ROLL = false>
+template <int SLOTS, int G, bool ROLL = false, bool COLD = false>
 __device__ __forceinline__ unsigned long long wolves_wave(const Params& p, const SmallLayout& L, uint32_t* lds, int lane,
                                                           CarryW2<SLOTS>* carry = nullptr, int t = 0, bool last = true) {
   const Lds s = lds_of(lds, L);
@@ -1146,9 +1172,9 @@ __device__ __forceinline__ unsigned long long wolves_wave(const Params& p, const
   {
     const int64_t gl = active ? g : 0;  // (unconditional; an inactive lane has no live wolf)
 #pragma unroll
-    for (int k = 0; k < kSpecSlots; ++k) wr[k] = p.wolves[(int64_t)k * p.B + gl];  // speculatively
+    for (int k = 0; k < kSpecSlots; ++k) wr[k] = cold_of<COLD>(p).wolves[(int64_t)k * p.B + gl];  // speculatively
   }
-  hr = head_fetch(p, g, active);
+  hr = head_fetch<COLD>(p, g, active);
   opaque_head(hr);
 #pragma unroll
   for (int k = 0; k < kSpecSlots; ++k) opaque(wr[k]);
@@ -1160,7 +1186,7 @@ __device__ __forceinline__ unsigned long long wolves_wave(const Params& p, const
   if (!carried) {
 #pragma unroll
     for (int k = kSpecSlots; k < SLOTS; ++k)
-      if (k < nw) wr[k] = p.wolves[(int64_t)k * p.B + g];
+      if (k < nw) wr[k] = cold_of<COLD>(p).wolves[(int64_t)k * p.B + g];
   }
   const uint64_t ek = mix64(h.kenv ^ (uint64_t)h.hdr.w);
   const uint32_t b0 = (uint32_t)ek, b1 = (uint32_t)(ek >> 32);
@@ -1248,7 +1274,7 @@ __device__ __forceinline__ unsigned long long wolves_wave(const Params& p, const
         const int b = __ffsll((unsigned long long)bits) - 1;
         bits &= bits - 1;
         const int r = 64 * half + b;
-        const uint32_t w = xy_add(h.cpos, G == 11 ? ring11(r) : p.tables[p.ring_at + r]);
+        const uint32_t w = xy_add(h.cpos, G == 11 ? ring11(r) : cold_of<COLD>(p).tables[p.ring_at + r]);
         bool placed = false;
 #pragma unroll
         for (int k = 0; k < SLOTS; ++k)
@@ -1263,13 +1289,13 @@ __device__ __forceinline__ unsigned long long wolves_wave(const Params& p, const
     int n = 0;
 #pragma unroll
     for (int k = 0; k < SLOTS; ++k)
-      if ((live >> k) & 1u) p.wolves[(int64_t)(n++) * p.B + g] = wr[k];
+      if ((live >> k) & 1u) cold_of<COLD>(p).wolves[(int64_t)(n++) * p.B + g] = wr[k];
     const uint32_t status = starved ? 1u : kill ? 2u : misc_status(h.hdr.z);
-    p.hdr[g] = make_uint4(h.cpos, (uint32_t)h.turn,
+    cold_of<COLD>(p).hdr[g] = make_uint4(h.cpos, (uint32_t)h.turn,
                           misc_pack((info >> 8) & 0xFFu, status, (uint32_t)n, (info >> 16) & 0xFFu, info >> 24),
                           h.hdr.w);
   }
-  if (wolf_of) atomicAdd(&p.counters[CTR_WOLF_OVERFLOW], wolf_of);
+  if (wolf_of) atomicAdd(&cold_of<COLD>(p).counters[CTR_WOLF_OVERFLOW], wolf_of);
   const unsigned long long jm = __ballot(job);
   if (ROLL && carry->prev_stream) store_units_nt<G, 128, 12, 64>(p, carry->prev_planes, carry->prev_stream, lane);
   SMALL_STAMP(19);
@@ -1312,7 +1338,7 @@ __device__ __forceinline__ unsigned long long wolves_wave(const Params& p, const
 }
 
 // --------------------------------------------------------------------------- W3: ring
-template <int SLOTS, int G, bool ROLL = false>
+template <int SLOTS, int G, bool ROLL = false, bool COLD = false>
 __device__ __forceinline__ unsigned long long ring_wave(const Params& p, const SmallLayout& L, uint32_t* lds, int lane,
                                                         CarryHdr* carry = nullptr, int t = 0, bool last = true) {
   const Lds s = lds_of(lds, L);
@@ -1325,13 +1351,13 @@ __device__ __forceinline__ unsigned long long ring_wave(const Params& p, const S
     hr.a = act_of(s, lane);
     reinterpret_cast<uint4*>(s.jbm)[lane] = make_uint4(0u, 0u, 0u, 0u);  // reset bitmaps [64][4]
   } else {
-  hr = head_fetch(p, g, g < p.B);
+  hr = head_fetch<COLD>(p, g, g < p.B);
   if constexpr (G == 11) {  // view-cell offsets (cw - i, ch - j) of cell c = 11 i + j, computed
     for (int c = lane; c < 121; c += 64) s.tiles[c] = xy_pack(5 - c / 11, 5 - c % 11);
   } else {
     uint32_t tv[2];  // WH <= 128: both loads in flight at once
 #pragma unroll
-    for (int k = 0; k < 2; ++k) tv[k] = p.tables[min(64 * k + lane, p.WH - 1)];
+    for (int k = 0; k < 2; ++k) tv[k] = cold_of<COLD>(p).tables[min(64 * k + lane, p.WH - 1)];
 #pragma unroll
     for (int k = 0; k < 2; ++k)
       if (64 * k + lane < p.WH) s.tiles[64 * k + lane] = tv[k];
@@ -1341,7 +1367,7 @@ __device__ __forceinline__ unsigned long long ring_wave(const Params& p, const S
     const int n = p.n_gap + 1;  // <= 129
     uint64_t gv[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) gv[k] = p.gap[min(64 * k + lane, n - 1)];
+    for (int k = 0; k < 3; ++k) gv[k] = cold_of<COLD>(p).gap[min(64 * k + lane, n - 1)];
     opaque_head(hr);
 #pragma unroll
     for (int k = 0; k < 3; ++k) opaque(gv[k]);
@@ -1396,11 +1422,11 @@ __device__ __forceinline__ unsigned long long ring_wave(const Params& p, const S
       // the part of the new episode that needs only its key, while W1 may still be drawing
       unsigned long long wolf_of = 0;
       const uint32_t ebit = (uint32_t)lane * (uint32_t)p.OB;
-      if (job) role2 = new_episode_a<SLOTS, ROLL>(p, s, h, g, (uint32_t)ek2, (uint32_t)(ek2 >> 32), ebit, wolf_of, last);
+      if (job) role2 = new_episode_a<SLOTS, ROLL, COLD>(p, s, h, g, (uint32_t)ek2, (uint32_t)(ek2 >> 32), ebit, wolf_of, last);
       lds_await(p, &s.flag[1]);  // W1's part of the draws
       SMALL_STAMP(9);
-      if (job) new_episode_b(p, s, g, j, ebit, role2, !ROLL || last);
-      if (wolf_of) atomicAdd(&p.counters[CTR_WOLF_OVERFLOW], wolf_of);
+      if (job) new_episode_b<COLD>(p, s, g, j, ebit, role2, !ROLL || last);
+      if (wolf_of) atomicAdd(&cold_of<COLD>(p).counters[CTR_WOLF_OVERFLOW], wolf_of);
     }
   }
   SMALL_STAMP(25);
@@ -1588,7 +1614,8 @@ __device__ __forceinline__ void step_features(const Params& p, const SmallLayout
 // the wave that uses them.  (A plain copy of the kernel argument has every field loaded at
 // the kernel's entry, before the wave branch, and spilled to VGPR lanes: ~190 v_writelane /
 // v_readlane and a chain of scalar-load waits ahead of every wave's first global load.)
-template <int G, bool FEAT>
+// RULES: the default options' rule fields as constants too (specialise_rules, wab_default_rules.h)
+template <int G, bool FEAT, bool RULES>
 __device__ __forceinline__ Params wave_params(const Params& p0) {
 #if __HIP_DEVICE_COMPILE__  // (the host pass only type-checks the kernel body)
   typedef const Params __attribute__((address_space(4))) KernargParams;
@@ -1599,6 +1626,7 @@ __device__ __forceinline__ Params wave_params(const Params& p0) {
   Params p = p0;
 #endif
   specialise_geometry<G>(p);
+  specialise_rules<RULES>(p);
   if constexpr (!FEAT) p.features = nullptr;
   return p;
 }
@@ -1617,7 +1645,52 @@ __device__ __forceinline__ void step_slice(Params& p, int t) {
   if (p.features) p.features += o * pragmatic_dim(p.W / 2 + p.H / 2 + 1, p.turns_empty);
 }
 
-template <int SLOTS, int G, bool FEAT, bool ROLL>
+// The I/O slices of a multi-step launch and what else every step of it reads from the parameter
+// block, read once per launch and kept in scalar registers across the step loop (the default-rules
+// instances: with the rules constants the set is small enough to stay there).  Each step's copy
+// of the block has these fields replaced; the fields only the first or the last step or a rare
+// path reads (the state arrays, the tables) are loaded in the branch that uses them (cold_of).
+struct RollSlices {
+  const int8_t* actions;
+  uint8_t *planes, *food_turns, *role, *status, *done;
+  float *reward, *features, *returns;
+  int64_t B, env_base, d_planes, d_features;  // d_*: one step's planes / feature rows
+  uint64_t seed;
+  unsigned long long* block_resets;
+  int32_t n_steps;
+};
+
+__device__ __forceinline__ RollSlices roll_slices(const Params& p) {
+  RollSlices r;
+  r.actions = p.actions; r.planes = p.planes; r.food_turns = p.food_turns; r.role = p.role;
+  r.status = p.status; r.done = p.done; r.reward = p.reward; r.features = p.features; r.returns = p.returns;
+  r.B = p.B; r.env_base = p.env_base; r.seed = p.seed;
+  r.block_resets = p.block_resets; r.n_steps = p.n_steps;
+  r.d_planes = p.B * p.OB;
+  r.d_features = p.B * pragmatic_dim(p.W / 2 + p.H / 2 + 1, p.turns_empty);
+  return r;
+}
+// the slices of the next step (step_slice, one step at a time: no multiply)
+__device__ __forceinline__ void roll_advance(RollSlices& r) {
+  r.actions += r.B;
+  if (r.planes) r.planes += r.d_planes;
+  r.food_turns += r.B;
+  r.role += r.B;
+  r.status += r.B;
+  r.reward += r.B;
+  r.done += r.B;
+  if (r.features) r.features += r.d_features;
+}
+__device__ __forceinline__ void roll_apply(Params& p, const RollSlices& r) {
+  p.actions = r.actions; p.planes = r.planes; p.food_turns = r.food_turns; p.role = r.role;
+  p.status = r.status; p.done = r.done; p.reward = r.reward; p.features = r.features; p.returns = r.returns;
+  p.B = r.B; p.env_base = r.env_base; p.seed = r.seed;
+  p.block_resets = r.block_resets; p.n_steps = r.n_steps;
+  // (a multi-step launch has no terminal side buffers: nothing is stored through these)
+  p.t_planes = nullptr; p.t_food_turns = r.food_turns; p.t_role = r.role; p.t_status = r.status;
+}
+
+template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 1))) void wab_step_small(Params p0) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 #ifdef WAB_STAMPS
@@ -1651,20 +1724,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
       // the bushes wave carries the longest chain and shares its SIMD with three helper waves
       // of other groups: let the arbiter issue its instructions first
       __builtin_amdgcn_s_setprio(3);
-      const Params p = wave_params<G, FEAT>(p0);
+      const Params p = wave_params<G, FEAT, RULES>(p0);
       jm = bushes_wave<SLOTS, G>(p, small_layout(p), lds, lane);
       __builtin_amdgcn_s_setprio(0);
     } else if (wave == 1) {
-      const Params p = wave_params<G, FEAT>(p0);
+      const Params p = wave_params<G, FEAT, RULES>(p0);
       jm = draws_wave<G>(p, small_layout(p), lds, lane);
     } else if (wave == 2) {
-      const Params p = wave_params<G, FEAT>(p0);
+      const Params p = wave_params<G, FEAT, RULES>(p0);
       jm = wolves_wave<SLOTS, G>(p, small_layout(p), lds, lane);
     } else {
-      const Params p = wave_params<G, FEAT>(p0);
+      const Params p = wave_params<G, FEAT, RULES>(p0);
       jm = ring_wave<SLOTS, G>(p, small_layout(p), lds, lane);
     }
-    const Params p = wave_params<G, FEAT>(p0);
+    const Params p = wave_params<G, FEAT, RULES>(p0);
     const SmallLayout L = small_layout(p);
     (void)jm;
     if (!FEAT || p.planes) store_obs(p, lds + L.stream, threadIdx.x);
@@ -1674,6 +1747,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
     // depend on nothing outside it), each wave's state carried in registers from step to step
     // (see CarryW0): one barrier closes a step (its LDS is reused by the next)
     const int T = p0.n_steps;
+    // the default-rules instances read their parameters once per launch (RollSlices); not
+    // wab_rollout_features' (FEAT), at the 128-VGPR ceiling already: it would take scratch
+    constexpr bool HOIST = WAB_ROLL_HOIST && RULES && !FEAT;
 #ifdef WAB_STAMPS
 #define ROLL_LOOP_STAMP(slot, cond)                                                          \
   do {                                                                                       \
@@ -1684,22 +1760,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
 #define ROLL_LOOP_STAMP(slot, cond) do {} while (0)
 #endif
     {  // the second stream starts clear (the first is cleared by W0 in step 0)
-      const SmallLayout L = small_layout(p0);
+      const SmallLayout L = small_layout(wave_params<G, FEAT, RULES>(p0));
       uint4* z = reinterpret_cast<uint4*>(lds + L.stream2);
       for (uint32_t i = threadIdx.x; i < L.stream_words / 4u; i += 256) z[i] = make_uint4(0u, 0u, 0u, 0u);
     }
     // one step of wave W's part; step t renders into stream t & 1 while W0 and W2 store step
     // t - 1's obs from the other one; the last step's obs go out at its end, by every thread
 #define WAB_ROLL_STEP(...)                                                                   \
+    RollSlices io = roll_slices(wave_params<G, FEAT, RULES>(p0));                            \
     for (int t = 0; t < T; ++t) {                                                            \
       ROLL_LOOP_STAMP(35, t == T / 2);  /* the middle step's loop top (before its parameters) */ \
       if (WAB_ROLL_THROTTLE && (wave == 0 || wave == 2)) __builtin_amdgcn_s_waitcnt(0x0F70);  \
-      Params p = wave_params<G, FEAT>(p0);                                                   \
-      step_slice(p, t);                                                                      \
+      Params p = wave_params<G, FEAT, RULES>(p0);                                            \
+      if constexpr (HOIST) {                                                                 \
+        if (t > 0) roll_advance(io);                                                         \
+        roll_apply(p, io);                                                                   \
+      } else {                                                                               \
+        step_slice(p, t);                                                                    \
+      }                                                                                      \
       const SmallLayout L0 = small_layout(p);                                                \
       SmallLayout L = L0;                                                                    \
       if (t & 1) L.stream = L0.stream2;                                                      \
-      c.prev_planes = p.planes ? p.planes - (int64_t)p.B * p.OB : nullptr;                   \
+      c.prev_planes = !p.planes ? nullptr : HOIST ? p.planes - io.d_planes : p.planes - (int64_t)p.B * p.OB; \
       c.prev_stream = t > 0 ? lds + ((t & 1) ? L0.stream : L0.stream2) : nullptr;           \
       if (WAB_ROLL_FLOOR) {  /* diagnostic floor: the stores alone (results wrong by design) */ \
         lds_barrier();                                                                       \
@@ -1723,21 +1805,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
       CarryW0 c;
       WAB_ROLL_STEP({
         role_prio<true>(3, t, p.features != nullptr);
-        bushes_wave<SLOTS, G, true>(p, L, lds, lane, &c, t, t == T - 1);
+        bushes_wave<SLOTS, G, true, HOIST>(p, L, lds, lane, &c, t, t == T - 1);
         role_prio<true>(0, t, p.features != nullptr);
       })
     } else if (wave == 1) {
       constexpr int kWave = 1;
       CarryPtr<CarryHdr> c;
-      WAB_ROLL_STEP(draws_wave<G, true>(p, L, lds, lane, &c.c, t, t == T - 1))
+      WAB_ROLL_STEP((draws_wave<G, true, HOIST>(p, L, lds, lane, &c.c, t, t == T - 1)))
     } else if (wave == 2) {
       constexpr int kWave = 2;
       CarryW2<SLOTS> c;
-      WAB_ROLL_STEP((wolves_wave<SLOTS, G, true>(p, L, lds, lane, &c, t, t == T - 1)))
+      WAB_ROLL_STEP((wolves_wave<SLOTS, G, true, HOIST>(p, L, lds, lane, &c, t, t == T - 1)))
     } else {
       constexpr int kWave = 3;
       CarryPtr<CarryHdr> c;
-      WAB_ROLL_STEP((ring_wave<SLOTS, G, true>(p, L, lds, lane, &c.c, t, t == T - 1)))
+      WAB_ROLL_STEP((ring_wave<SLOTS, G, true, HOIST>(p, L, lds, lane, &c.c, t, t == T - 1)))
     }
 #undef WAB_ROLL_STEP
 #undef ROLL_LOOP_STAMP
@@ -1750,29 +1832,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
   }
 }
 
-template __global__ void wab_step_small<8, 0, false, false>(Params);
-template __global__ void wab_step_small<8, 0, true, false>(Params);
-template __global__ void wab_step_small<8, 0, false, true>(Params);
-template __global__ void wab_step_small<8, 0, true, true>(Params);
-template __global__ void wab_step_small<8, 11, false, false>(Params);
-template __global__ void wab_step_small<8, 11, true, false>(Params);
-template __global__ void wab_step_small<8, 11, false, true>(Params);
-template __global__ void wab_step_small<8, 11, true, true>(Params);
-template __global__ void wab_step_small<16, 0, false, false>(Params);
-template __global__ void wab_step_small<16, 0, true, false>(Params);
-template __global__ void wab_step_small<16, 0, false, true>(Params);
-template __global__ void wab_step_small<16, 0, true, true>(Params);
-template __global__ void wab_step_small<16, 11, false, false>(Params);
-template __global__ void wab_step_small<16, 11, true, false>(Params);
-template __global__ void wab_step_small<16, 11, false, true>(Params);
-template __global__ void wab_step_small<16, 11, true, true>(Params);
-template __global__ void wab_step_small<32, 0, false, false>(Params);
-template __global__ void wab_step_small<32, 0, true, false>(Params);
-template __global__ void wab_step_small<32, 0, false, true>(Params);
-template __global__ void wab_step_small<32, 0, true, true>(Params);
-template __global__ void wab_step_small<32, 11, false, false>(Params);
-template __global__ void wab_step_small<32, 11, true, false>(Params);
-template __global__ void wab_step_small<32, 11, false, true>(Params);
-template __global__ void wab_step_small<32, 11, true, true>(Params);
+#if WAB_RULES_INSTANCE
+template __global__ void wab_step_small<8, 11, false, false, true>(Params);
+template __global__ void wab_step_small<8, 11, true, false, true>(Params);
+template __global__ void wab_step_small<8, 11, false, true, true>(Params);
+template __global__ void wab_step_small<8, 11, true, true, true>(Params);
+#endif
+#ifndef WAB_ONLY_WAVE  // (tools/isa_count.py reads the SLOTS = 8, G = 11 instances only)
+template __global__ void wab_step_small<8, 0, false, false, false>(Params);
+template __global__ void wab_step_small<8, 0, true, false, false>(Params);
+template __global__ void wab_step_small<8, 0, false, true, false>(Params);
+template __global__ void wab_step_small<8, 0, true, true, false>(Params);
+#endif
+template __global__ void wab_step_small<8, 11, false, false, false>(Params);
+template __global__ void wab_step_small<8, 11, true, false, false>(Params);
+template __global__ void wab_step_small<8, 11, false, true, false>(Params);
+template __global__ void wab_step_small<8, 11, true, true, false>(Params);
+#ifndef WAB_ONLY_WAVE
+template __global__ void wab_step_small<16, 0, false, false, false>(Params);
+template __global__ void wab_step_small<16, 0, true, false, false>(Params);
+template __global__ void wab_step_small<16, 0, false, true, false>(Params);
+template __global__ void wab_step_small<16, 0, true, true, false>(Params);
+template __global__ void wab_step_small<16, 11, false, false, false>(Params);
+template __global__ void wab_step_small<16, 11, true, false, false>(Params);
+template __global__ void wab_step_small<16, 11, false, true, false>(Params);
+template __global__ void wab_step_small<16, 11, true, true, false>(Params);
+template __global__ void wab_step_small<32, 0, false, false, false>(Params);
+template __global__ void wab_step_small<32, 0, true, false, false>(Params);
+template __global__ void wab_step_small<32, 0, false, true, false>(Params);
+template __global__ void wab_step_small<32, 0, true, true, false>(Params);
+template __global__ void wab_step_small<32, 11, false, false, false>(Params);
+template __global__ void wab_step_small<32, 11, true, false, false>(Params);
+template __global__ void wab_step_small<32, 11, false, true, false>(Params);
+template __global__ void wab_step_small<32, 11, true, true, false>(Params);
 
+#endif
 }  // namespace wab
