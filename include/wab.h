@@ -37,6 +37,8 @@
  *   wab_snapshot_save / wab_snapshot_restore <- (no counterpart: the reference has no
  *                            checkpoint, resume or rewind of an env)
  *   wab_policy_act        <- Policy.forward + select_action's sample  actor_critic.py:76-125
+ *   wab_rollout_policy    <- T steps of actor_critic.main's loop with   actor_critic.py:108-125,
+ *                            select_action choosing each action          185-200
  */
 #ifndef WAB_H_
 #define WAB_H_
@@ -48,7 +50,7 @@
 extern "C" {
 #endif
 
-#define WAB_ABI_VERSION 7
+#define WAB_ABI_VERSION 8
 #define WAB_MAX_WOLF_SLOTS 32 /* largest per-env live-wolf slot count (wab_config.wolf_slots) */
 #define WAB_MAX_VIEW 63       /* largest odd width/height accepted */
 
@@ -133,7 +135,7 @@ typedef struct wab_counters {
                               * guard; nonzero means results are invalid; must stay 0) */
   uint64_t wolf_overflow_reset; /* the part of wolf_overflow dropped by resets (a new episode's
                                  * initial wolves beyond the slots); the rest are ring spawns */
-  uint64_t rollout_launches;   /* wab_rollout / wab_rollout_features calls that ran as ONE launch
+  uint64_t rollout_launches;   /* wab_rollout / wab_rollout_features / wab_rollout_policy calls that ran as ONE launch
                                 * (host-side tally) */
   uint64_t rollout_step_calls; /* ... that ran as T per-step calls instead (misaligned plane
                                 * slices, other kernels; host-side tally) */
@@ -417,6 +419,52 @@ int wab_policy_act(wab_handle* h, wab_policy* p, const float* features, int8_t* 
 
 /* Free the policy (synchronises its device). */
 int wab_policy_destroy(wab_policy* p);
+
+/* ---- closed-loop rollout: policy and env step, T steps (actor_critic.py:108-125, 185-200) -- */
+
+/* 1 when wab_rollout_policy(h, p, ...) runs as one launch, 0 when it runs as 2 T launches;
+ * host only, no device work.  Negative WAB_E_* for NULL or a policy of another device.
+ * One launch needs: the small-view kernel at the 11x11 geometry with 8 wolf slots and its fused
+ * featurizer (the default options and any other rules at that geometry); a policy whose
+ * in_features is wab_feature_dim(h) (every width wab_policy_create accepts is fused);
+ * batch * feature_dim a multiple of 4; and the
+ * kernel's LDS (the step's, a 128-step returns scan's, and the policy's bf16 images of 64 envs)
+ * within the device's limit per workgroup.  The answer is for calls without planes; a call
+ * with obs_seq->planes also needs batch * 3 * W * S to be a multiple of 16 and otherwise runs as
+ * the 2 T launches. */
+int wab_rollout_policy_fused(const wab_handle* h, const wab_policy* p);
+
+/* T closed-loop steps.  The call equals, bit for bit, for t = 0 .. T-1:
+ *   wab_policy_act(h, p, t == 0 ? features0 : features[t], actions[t], probs[t], value[t]);
+ *   wab_step_features(h, actions[t], obs_seq[t], reward[t], done[t],
+ *                     t + 1 < T ? features[t + 1] : features_last);
+ * after which slice 0 of `features` holds features0 (features == features0 is allowed) and, if
+ * `returns` is non-NULL, wab_discounted_returns_exact has run over the [T][B] reward / done with
+ * `bootstrap` (as in wab_rollout_features: in the launch for T <= 128, the same refusal when two
+ * of the options' rewards round to one float32).
+ * features0 [B][F] float32, 4-byte aligned, any values (rounded to bf16 as wab_policy_act rounds
+ * them); obs_seq scalars [T][B], planes [T][B][3][W][S] or NULL; actions [T][B] int8; value
+ * [T][B], probs [T][B][n_actions], features [T][B][F] and returns [T][B] float32 or NULL;
+ * reward [T][B] float32, done [T][B] uint8 and features_last [B][F] float32 are required;
+ * features and features_last 16-byte aligned; features_last may be features0 (a continuing
+ * rollout keeps one row array).  Where the answer is 0, wab_last_error() says which condition
+ * failed.  With features == NULL the intermediate feature
+ * rows are never written to device memory.
+ * Where wab_rollout_policy_fused is 1 the call is one launch (each workgroup takes its 64 envs
+ * through the T steps, the policy between them on the feature bits still on chip, the draw keyed
+ * by the env's episode and turn after the step), with no allocation and no synchronisation, safe
+ * to capture in a hipGraph.  Elsewhere it is the 2 T calls above on `stream`; with features ==
+ * NULL, or feature slices that are not 16-byte aligned, that path goes through a handle-owned
+ * pair of feature rows, which the first such call allocates (hipMalloc: make one such call
+ * before capturing a graph; freed by wab_destroy).
+ * wab_counters.steps and the resets advance as under the two calls; bad_actions stays 0.
+ * WAB_E_STATE before the first wab_policy_load or wab_reset; WAB_E_INVALID for another n_actions
+ * or in_features than the handle's, a policy on another device, a NULL required argument, or
+ * misaligned features. */
+int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int32_t T,
+                       const wab_obs* obs_seq, int8_t* actions, float* value, float* probs,
+                       float* reward, uint8_t* done, float* features, float* features_last,
+                       double gamma, const float* bootstrap, float* returns, void* stream);
 
 /* Test hook: the bush value (berries, generate_n_bush_values wab_env.py:631-635) the step
  * kernels give the 53-bit draws U[n] under h's threshold table, computed by the kernels' own

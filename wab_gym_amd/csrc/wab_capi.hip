@@ -23,7 +23,7 @@
 namespace wab {
 template <int MODE, int SLOTS, bool SMALL>
 __global__ void wab_kernel(Params p);
-template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES = false>
+template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES = false, bool POLICY = false>
 __global__ void wab_step_small(Params p);
 template <int MODE, int SLOTS>
 __global__ void wab_step_wide(Params p);
@@ -59,6 +59,8 @@ struct wab_handle {
   bool reset_done = false;
   std::vector<void*> allocs;
   uint8_t* scratch_planes = nullptr;  // wab_step_features without planes, not fusable (lazy)
+  float* bounce_rows = nullptr;       // wab_rollout_policy's 2 T launches: two [B][F] feature rows (lazy)
+  size_t lds_max = 0;                 // the device's LDS limit per workgroup (wab_rollout_policy_fused)
   // egocentric observation (allocated by the first wab_egocentric call)
   uint4* ego_path = nullptr;
   uint32_t* ego_diamond = nullptr;
@@ -570,6 +572,55 @@ uint8_t* scratch_planes(wab_handle* h) {
   return h->scratch_planes;
 }
 
+// a handle-owned pair of [B][F] feature rows (16-byte aligned), allocated by the first call that needs it
+float* bounce_rows(wab_handle* h, size_t row_floats) {
+  if (!h->bounce_rows) {
+    DeviceGuard guard(h->device);
+    void* ptr = nullptr;
+    if (hipMalloc(&ptr, std::max<size_t>(16, 2u * ((row_floats + 3u) & ~(size_t)3u) * 4u)) != hipSuccess) return nullptr;
+    h->allocs.push_back(ptr);
+    h->bounce_rows = static_cast<float*>(ptr);
+  }
+  return h->bounce_rows;
+}
+
+// wab_rollout_policy as one launch: the POLICY instances of the small kernel (8 slots, 11x11)
+void* roll_policy_kernel(bool rules) {
+#if WAB_RULES_INSTANCE
+  if (rules) return reinterpret_cast<void*>(&wab::wab_step_small<8, 11, true, true, true, true>);
+#endif
+  return reinterpret_cast<void*>(&wab::wab_step_small<8, 11, true, true, false, true>);
+}
+
+// Whether (h, p) takes the one-launch path, and its LDS for T steps (returns scanned in the
+// launch or not).  The answer does not depend on T: the limit is tested with the longest
+// in-launch returns scan's reward codes.
+bool roll_policy_plan(const wab_handle* h, const wab_policy* p, int32_t T, bool fused_returns, wab::RollPolicy* out,
+                      std::string* why) {
+  const auto no = [&](const char* msg) {
+    if (why) *why = msg;
+    return false;
+  };
+  if (h->step_kernel != KERNEL_SMALL || !h->small_g11 || h->slots != 8 || !h->small_feat_lds_bytes)
+    return no("the one-launch kernel is built for the 11x11 small-view kernel with 8 wolf slots and the fused "
+              "featurizer");
+  const int F = wab_feature_dim(h);
+  if (F < 0 || p->dims.F != F) return no("the policy's in_features is not the handle's feature length");
+  if (((size_t)h->p.B * (size_t)F) % 4u != 0) return no("batch * feature_dim is not a multiple of 4");
+  Params q = h->p;
+  q.features = reinterpret_cast<float*>(16);  // (layout only)
+  q.returns = reinterpret_cast<float*>(16);
+  q.n_steps = wab::kMaxFusedReturnSteps;
+  if (wab::roll_policy_lds(p->dims, wab::small_layout(q).total * 4u).total > h->lds_max)
+    return no("the kernel's LDS exceeds the device's limit per workgroup");
+  if (out) {
+    q.n_steps = T;
+    if (!fused_returns) q.returns = nullptr;
+    *out = wab::roll_policy_lds(p->dims, wab::small_layout(q).total * 4u);
+  }
+  return true;
+}
+
 int check_obs(const wab_obs* o, const char* what) {
   if (!o || !o->planes || !o->food_turns || !o->role || !o->status)
     return fail(WAB_E_INVALID, std::string(what) + ": every wab_obs pointer must be set");
@@ -747,6 +798,11 @@ int wab_create(const wab_config* c, int64_t batch, uint64_t seed, int64_t env_id
   }
 
   DeviceGuard guard(device);
+  {
+    int lds_max = 0;
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && lds_max > 0)
+      h->lds_max = (size_t)lds_max;
+  }
   auto alloc = [&](void** ptr, size_t bytes) -> int {
     if (bytes == 0) bytes = 16;
     hipError_t e = hipMalloc(ptr, bytes);
@@ -1489,6 +1545,11 @@ int wab_policy_create(const wab_policy_shape* shape, int device, wab_policy** ou
     e = hipFuncSetAttribute(p->dims.NT1 > 4 ? reinterpret_cast<void*>(&wab::wab_policy_kernel<true>)
                                             : reinterpret_cast<void*>(&wab::wab_policy_kernel<false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+  // the same for wab_rollout_policy's one-launch instances on this device (both: which one a
+  // handle takes depends on its options)
+  for (bool rules : {false, true})
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(roll_policy_kernel(rules), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
   void *w = nullptr, *b = nullptr;
   if (e == hipSuccess) e = hipMalloc(&w, (size_t)p->dims.w_total * 2u);
   if (e == hipSuccess) e = hipMalloc(&b, (size_t)p->dims.b_total * 4u);
@@ -1573,6 +1634,145 @@ int wab_policy_act(wab_handle* h, wab_policy* p, const float* features, int8_t* 
     hipLaunchKernelGGL(wab::wab_policy_kernel<false>, grid, dim3(256), p->lds.total, (hipStream_t)stream, pp);
   HIP_TRY(hipGetLastError());
   return WAB_OK;
+}
+
+int wab_rollout_policy_fused(const wab_handle* h, const wab_policy* p) {
+  g_err.clear();
+  if (!h || !p) return fail(WAB_E_INVALID, "wab_rollout_policy_fused: NULL argument");
+  if (p->device != h->device)
+    return fail(WAB_E_INVALID, "wab_rollout_policy_fused: the policy is on device " + std::to_string(p->device) +
+                                   ", the handle on device " + std::to_string(h->device));
+  return roll_policy_plan(h, p, 1, false, nullptr, &g_err) ? 1 : 0;
+}
+
+int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int32_t T, const wab_obs* obs_seq,
+                       int8_t* actions, float* value, float* probs, float* reward, uint8_t* done, float* features,
+                       float* features_last, double gamma, const float* bootstrap, float* returns, void* stream) {
+  g_err.clear();
+  if (!h || !p) return fail(WAB_E_INVALID, "wab_rollout_policy: NULL argument");
+  if (T < 0) return fail(WAB_E_INVALID, "wab_rollout_policy: T must be >= 0");
+  if (!features0 || !actions || !reward || !done || !features_last || !obs_seq || !obs_seq->food_turns ||
+      !obs_seq->role || !obs_seq->status)
+    return fail(WAB_E_INVALID, "wab_rollout_policy: NULL argument (features0, actions, reward, done, features_last "
+                               "and the scalars of obs_seq are required)");
+  if (p->device != h->device)
+    return fail(WAB_E_INVALID, "wab_rollout_policy: the policy is on device " + std::to_string(p->device) +
+                                   ", the handle on device " + std::to_string(h->device));
+  if (p->dims.A != h->p.n_actions)
+    return fail(WAB_E_INVALID, "wab_rollout_policy: the policy has " + std::to_string(p->dims.A) +
+                                   " actions, the handle's options " + std::to_string(h->p.n_actions));
+  const int F = wab_feature_dim(h);
+  if (F < 0) return fail(WAB_E_INVALID, "wab_rollout_policy: the wrapper cannot index this viewport");
+  if (p->dims.F != F)
+    return fail(WAB_E_INVALID, "wab_rollout_policy: the policy takes " + std::to_string(p->dims.F) +
+                                   " features, the handle's rows have " + std::to_string(F));
+  if (!p->loaded) return fail(WAB_E_STATE, "wab_rollout_policy: call wab_policy_load first");
+  if (!h->reset_done) return fail(WAB_E_STATE, "wab_rollout_policy: call wab_reset first (no env has an episode yet)");
+  const auto misaligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3u) != 0; };
+  if (misaligned4(features0) || (probs && misaligned4(probs)) || (value && misaligned4(value)))
+    return fail(WAB_E_INVALID, "wab_rollout_policy: features0, probs and value must be 4-byte aligned");
+  if (!aligned16(features_last) || (features && !aligned16(features)))
+    return fail(WAB_E_INVALID, "wab_rollout_policy: features and features_last must be 16-byte aligned");
+  if (obs_seq->planes && !aligned16(obs_seq->planes))
+    return fail(WAB_E_INVALID, "wab_rollout_policy: planes must be 16-byte aligned");
+  const int64_t B = h->p.B;
+  const size_t OB = (size_t)h->p.OB, BF = (size_t)B * (size_t)F;
+  if (T == 0 || B == 0) return WAB_OK;
+  const bool fused_returns = returns && T <= wab::kMaxFusedReturnSteps;
+  wab::RollPolicy rp;
+  bool fused = roll_policy_plan(h, p, T, fused_returns, &rp, nullptr);
+  if (obs_seq->planes && ((size_t)B * OB) % 16u != 0) fused = false;  // (the launch's 16-byte obs stores)
+  if (returns && !(fused && fused_returns) && h->rewards.n < 0)  // (checked before anything runs)
+    return fail(WAB_E_INVALID, "wab_rollout_policy: returns of this segment need the exact-reward scan, and two of "
+                               "the options' rewards round to the same float32 (pass returns = NULL)");
+  if (fused) {
+    // one launch: each workgroup runs its 64 envs through the T steps, the policy between them
+    // (wab_step_small<8, 11, FEAT, ROLL, .., POLICY>), the returns of the segment at its end
+    Params q = h->p;
+    q.actions = actions;
+    q.planes = obs_seq->planes;
+    q.food_turns = obs_seq->food_turns;
+    q.role = obs_seq->role;
+    q.status = obs_seq->status;
+    q.reward = reward;
+    q.done = done;
+    q.features = features_last;  // (non-null: the featurizer is on; the rows go where q.pol says)
+    q.n_steps = T;
+    if (fused_returns) {
+      q.returns = returns;
+      q.bootstrap = bootstrap;
+      q.gamma = gamma;
+    }
+    rp.features0 = features0;
+    rp.features = features;
+    rp.features_last = features_last;
+    rp.actions = actions;
+    rp.probs = probs;
+    rp.value = value;
+    rp.w = p->w;
+    rp.b = p->b;
+    q.pol = rp;
+    DeviceGuard guard(h->device);
+    ++h->rollout_launches;
+    const dim3 grid(h->n_blocks), block(256);
+    bool launched = false;
+#if WAB_RULES_INSTANCE
+    if (h->small_rules) {
+      hipLaunchKernelGGL((wab::wab_step_small<8, 11, true, true, true, true>), grid, block, rp.total, (hipStream_t)stream, q);
+      launched = true;
+    }
+#endif
+    if (!launched)
+      hipLaunchKernelGGL((wab::wab_step_small<8, 11, true, true, false, true>), grid, block, rp.total, (hipStream_t)stream, q);
+    HIP_TRY(hipGetLastError());
+    if (fused_returns || !returns) return WAB_OK;
+    return wab_discounted_returns_exact(h, reward, done, T, B, gamma, bootstrap, returns, stream);
+  }
+  // the 2 T calls; a step's rows go straight to their slice when there is one and it is aligned,
+  // else through the handle's pair of rows (alternating: step t reads one, writes the other)
+  ++h->rollout_step_calls;
+  const bool direct = features && (BF * 4u) % 16u == 0;
+  float* bounce = nullptr;
+  if (!direct && T > 1) {
+    bounce = bounce_rows(h, BF);
+    if (!bounce) return fail(WAB_E_NOMEM, "wab_rollout_policy: hipMalloc");
+  }
+  const size_t bounce_stride = (BF + 3u) & ~(size_t)3u;
+  if (features && features != features0) {
+    DeviceGuard guard(h->device);
+    HIP_TRY(hipMemcpyAsync(features, features0, BF * 4u, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  }
+  const float* cur = features0;
+  for (int32_t t = 0; t < T; ++t) {
+    const size_t tb = (size_t)t * (size_t)B;
+    int rc = wab_policy_act(h, p, cur, actions + tb, probs ? probs + tb * (size_t)p->dims.A : nullptr,
+                            value ? value + tb : nullptr, stream);
+    if (rc != WAB_OK) return rc;
+    wab_obs o;
+    o.planes = obs_seq->planes ? obs_seq->planes + tb * OB : nullptr;
+    uint8_t* pdst = o.planes;
+    if (pdst && !aligned16(pdst)) {  // (as in wab_rollout_features: through the handle's buffer)
+      o.planes = scratch_planes(h);
+      if (!o.planes) return fail(WAB_E_NOMEM, "wab_rollout_policy: hipMalloc");
+    }
+    o.food_turns = obs_seq->food_turns + tb;
+    o.role = obs_seq->role + tb;
+    o.status = obs_seq->status + tb;
+    float* slice = features && t + 1 < T ? features + (size_t)(t + 1) * BF : nullptr;
+    float* dst = t + 1 == T ? features_last : direct ? slice : bounce + (size_t)(t & 1) * bounce_stride;
+    rc = wab_step_features(h, actions + tb, &o, reward + tb, done + tb, dst, stream);
+    if (rc != WAB_OK) return rc;
+    if ((pdst && o.planes != pdst) || (slice && dst != slice)) {
+      DeviceGuard guard(h->device);
+      if (pdst && o.planes != pdst)
+        HIP_TRY(hipMemcpyAsync(pdst, o.planes, (size_t)B * OB, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+      if (slice && dst != slice)
+        HIP_TRY(hipMemcpyAsync(slice, dst, BF * 4u, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+    cur = dst;
+  }
+  if (!returns) return WAB_OK;
+  return wab_discounted_returns_exact(h, reward, done, T, B, gamma, bootstrap, returns, stream);
 }
 
 int wab_debug_bush_values(wab_handle* h, const uint64_t* U, int32_t* out, int64_t n, void* stream) {

@@ -8,6 +8,8 @@
 
 #include <stdint.h>
 
+#include "wab_policy.h"
+
 namespace wab {
 
 constexpr int kEnvsPerBlock = 64;   // env lanes = wave 0 of the block
@@ -49,6 +51,44 @@ __host__ __device__ inline int32_t xy_y(uint32_t p) { return (int32_t)(int16_t)(
 
 // diagnostic builds (-DWAB_STAMPS): int64 stamps per workgroup (tools/phase_stamps.py)
 constexpr int kStampStride = 48;
+
+// wab_rollout_policy's one-launch path (the POLICY build of wab_step_small): the device policy
+// (packed image, wab_policy.h), where each step's actions, value and probs go, and the LDS of
+// the policy phase behind the step's own (SmallLayout): region A holds a chunk of the bf16
+// input image [64][KC + 8], then X2; region B holds X1, then X3 (as PolicyLds, for 64 envs).
+struct RollPolicy {
+  PolicyDims d;
+  int32_t KC, n_chunks;                      // input columns per chunk (a multiple of 16), chunks
+  int32_t pitch_in, pitch1, pitch2, pitch3;  // elements
+  uint32_t reg_a, reg_b, total;              // byte offsets of the regions in the workgroup's LDS, its bytes
+  const float* features0;   // [B][F]: what actions[0] is chosen from
+  float* features;          // [T][B][F] or null: slice t is what actions[t] was chosen from
+  float* features_last;     // [B][F]: the features after the last step
+  int8_t* actions;          // [T][B]
+  float* probs;             // [T][B][A] or null
+  float* value;             // [T][B] or null
+  const uint16_t* w;        // packed bf16 image (PolicyDims::w*)
+  const float* b;           // packed biases (PolicyDims::b*)
+};
+
+// the policy phase's LDS for a step layout of `base` bytes
+__host__ __device__ inline RollPolicy roll_policy_lds(const PolicyDims& d, uint32_t base) {
+  RollPolicy r = {};
+  r.d = d;
+  r.pitch1 = 32 * d.NT1 + 8;
+  r.pitch2 = 32 * d.NT2 + 8;
+  r.pitch3 = 32 * d.NT3 + 8;
+  const int kpad = 16 * d.KS1;
+  r.n_chunks = (kpad + kPolicyMaxChunk - 1) / kPolicyMaxChunk;
+  r.KC = ((kpad + r.n_chunks - 1) / r.n_chunks + 15) / 16 * 16;
+  r.pitch_in = r.KC + 8;
+  const uint32_t rows = 64u * 2u;  // bytes per element column of 64 envs
+  const uint32_t chunk = rows * (uint32_t)r.pitch_in, x2 = rows * (uint32_t)r.pitch2;
+  r.reg_a = (base + 15u) & ~15u;
+  r.reg_b = r.reg_a + (chunk > x2 ? chunk : x2);
+  r.total = r.reg_b + rows * (uint32_t)(r.pitch1 > r.pitch3 ? r.pitch1 : r.pitch3);
+  return r;
+}
 
 struct Params {
   // ---- geometry
@@ -127,6 +167,7 @@ struct Params {
   const float* bootstrap;  // ... R after the last step [B] (null: 0)
   double gamma;
   unsigned long long* stamps;  // diagnostic builds only (-DWAB_STAMPS): [n_blocks][40] s_memrealtime
+  RollPolicy pol;      // wab_rollout_policy's one-launch path only
 };
 
 // LDS carve of one workgroup (dword offsets, each region 16-byte aligned).

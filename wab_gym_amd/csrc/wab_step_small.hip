@@ -36,6 +36,7 @@
 
 #include "wab_default_rules.h"
 #include "wab_feat.h"
+#include "wab_policy_dev.h"
 
 #ifndef WAB_ROLL_THROTTLE  // (tuning A/B: 1 = W0 / W2 drain their obs stores at each step's start)
 #define WAB_ROLL_THROTTLE 0
@@ -737,7 +738,8 @@ __device__ __forceinline__ void rollout_returns(const Params& p, const Lds& s, i
 // --------------------------------------------------------------------------- W0: bushes
 template <int SLOTS, int G, bool ROLL = false, bool COLD = false>
 __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const SmallLayout& L, uint32_t* lds, int lane,
-                                                          CarryW0* carry = nullptr, int t = 0, bool last = true) {
+                                                          CarryW0* carry = nullptr, int t = 0, bool last = true,
+                                                          bool pol = false) {
   const Lds s = lds_of(lds, L);
   const int64_t g0 = (int64_t)blockIdx.x * 64;
   const int64_t g = g0 + lane;
@@ -804,6 +806,7 @@ __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const
     uint4* z = reinterpret_cast<uint4*>(s.stream);
     for (uint32_t i = lane; i < L.stream_words / 4u; i += 64) z[i] = make_uint4(0u, 0u, 0u, 0u);
   }
+  if (ROLL && pol) hr.a = act_of(s, lane);  // (the policy build: step 0's actions are in LDS too)
   const Head h = head_decode(p, g, active, hr);
   if (lane == 0 && init) {
     s.flag[0] = 0u;
@@ -1055,7 +1058,8 @@ __device__ __forceinline__ unsigned long long bushes_wave(const Params& p, const
 // --------------------------------------------------------------------------- W1: draws
 template <int G, bool ROLL = false, bool COLD = false>
 __device__ __forceinline__ unsigned long long draws_wave(const Params& p, const SmallLayout& L, uint32_t* lds, int lane,
-                                                         CarryHdr* carry = nullptr, int t = 0, bool last = true) {
+                                                         CarryHdr* carry = nullptr, int t = 0, bool last = true,
+                                                         bool pol = false) {
   const Lds s = lds_of(lds, L);
   const int64_t g = (int64_t)blockIdx.x * 64 + lane;
   SMALL_STAMP(10);
@@ -1080,6 +1084,7 @@ __device__ __forceinline__ unsigned long long draws_wave(const Params& p, const 
     if (lane == 0) bush_thr_pads(s.thr, nthr);
   }
   }
+  if (ROLL && pol) hr.a = act_of(s, lane);  // (the policy build: step 0's actions are in LDS too)
   const Head h = head_decode(p, g, g < p.B, hr);
   if (!ROLL || t == 0) lds_barrier();  // B_init
   SMALL_STAMP(30);
@@ -1123,7 +1128,7 @@ __device__ __forceinline__ unsigned long long draws_wave(const Params& p, const 
   }
   // the next step's actions (in LDS by the step's end), after the draws W3 waits for: the
   // scalar load's wait is then off that chain
-  if (ROLL && !last) prefetch_actions(p, s, lane);
+  if (ROLL && !last && !pol) prefetch_actions(p, s, lane);  // (the policy build: the policy phase writes them)
   SMALL_STAMP(13);
   lds_barrier();  // B2
   if (!ROLL && p.t_planes) lds_barrier();  // B3
@@ -1143,7 +1148,8 @@ __device__ __forceinline__ unsigned long long draws_wave(const Params& p, const 
 // --------------------------------------------------------------------------- W2: wolves
 template <int SLOTS, int G, bool ROLL = false, bool COLD = false>
 __device__ __forceinline__ unsigned long long wolves_wave(const Params& p, const SmallLayout& L, uint32_t* lds, int lane,
-                                                          CarryW2<SLOTS>* carry = nullptr, int t = 0, bool last = true) {
+                                                          CarryW2<SLOTS>* carry = nullptr, int t = 0, bool last = true,
+                                                          bool pol = false) {
   const Lds s = lds_of(lds, L);
   const int64_t g = (int64_t)blockIdx.x * 64 + lane;
   const bool active = g < p.B;
@@ -1179,6 +1185,7 @@ __device__ __forceinline__ unsigned long long wolves_wave(const Params& p, const
 #pragma unroll
   for (int k = 0; k < kSpecSlots; ++k) opaque(wr[k]);
   }
+  if (ROLL && pol) hr.a = act_of(s, lane);  // (the policy build: step 0's actions are in LDS too)
   const Head h = head_decode(p, g, active, hr);
   if (!ROLL || t == 0) lds_barrier();  // B_init
   SMALL_STAMP(28);
@@ -1340,7 +1347,8 @@ __device__ __forceinline__ unsigned long long wolves_wave(const Params& p, const
 // --------------------------------------------------------------------------- W3: ring
 template <int SLOTS, int G, bool ROLL = false, bool COLD = false>
 __device__ __forceinline__ unsigned long long ring_wave(const Params& p, const SmallLayout& L, uint32_t* lds, int lane,
-                                                        CarryHdr* carry = nullptr, int t = 0, bool last = true) {
+                                                        CarryHdr* carry = nullptr, int t = 0, bool last = true,
+                                                        bool pol = false) {
   const Lds s = lds_of(lds, L);
   const int64_t g = (int64_t)blockIdx.x * 64 + lane;
   SMALL_STAMP(22);
@@ -1382,6 +1390,7 @@ __device__ __forceinline__ unsigned long long ring_wave(const Params& p, const S
     const uint32_t nz = ROLL && t > 0 ? L.ftab - L.fbits : L.fzero;
     for (uint32_t i = lane; i < nz / 4u; i += 64) z[i] = make_uint4(0u, 0u, 0u, 0u);
   }
+  if (ROLL && pol) hr.a = act_of(s, lane);  // (the policy build: step 0's actions are in LDS too)
   const Head h = head_decode(p, g, g < p.B, hr);
   if (!ROLL || t == 0) lds_barrier();  // B_init
   if (p.features) {
@@ -1539,9 +1548,10 @@ __device__ __forceinline__ void store_obs(const Params& p, uint32_t* stream, int
 // from the rendered bit-stream (after B2, or B3) and the scalars each env's writer handed over:
 // W0 the wolf plane, W1 the bush plane, W2 the scalars and view mask, one more barrier, then
 // all 256 threads expand the feature bits to float32 (the featurizer's phases 2 and 3).
-template <bool ROLL = false>
+// POLICY (wab_rollout_policy): the rows go to `rows` (that step's [B][F] slice), nowhere if null.
+template <bool ROLL = false, bool POLICY = false>
 __device__ __forceinline__ void step_features(const Params& p, const SmallLayout& L, uint32_t* lds, int wave,
-                                              int lane, int t = 0) {
+                                              int lane, int t = 0, float* rows = nullptr) {
   const int md = p.W / 2 + p.H / 2 + 1;
   const uint32_t F = (uint32_t)pragmatic_dim(md, p.turns_empty), WH = (uint32_t)p.WH;
   const int64_t g0 = (int64_t)blockIdx.x * 64;
@@ -1599,11 +1609,152 @@ __device__ __forceinline__ void step_features(const Params& p, const SmallLayout
   // stored early in each step.)  Multi-step launches store the rows non-temporal.
   lds_barrier();
   constexpr bool NT = ROLL;
+  if constexpr (POLICY) {
+    if (rows) store_feature_bits<NT>(ob, rows + (size_t)g0 * F, n_active * F, (int)threadIdx.x, 256);
+    return;
+  }
   if (p.restrict_view || ROLL) store_feature_bits<NT>(ob, p.features + (size_t)g0 * F, n_active * F, (int)threadIdx.x, 256);
   else store_rows_skip_views<NT>(ob, p.features + (size_t)g0 * F, n_active * F, F, (int)threadIdx.x, 256);
 #ifdef WAB_STAMPS
   stamp(37);  // wave 0's row stores issued
 #endif
+}
+
+// --------------------------------------------------------------------------- fused policy
+// wab_rollout_policy (the POLICY build of the multi-step kernel): the device policy of
+// wab_policy.hip run by the group's four waves on its own 64 envs, between two steps, on the
+// feature bits step_features<true> left in LDS (FIRST: before step 0, on the group's rows of
+// RollPolicy::features0 in HBM, rounded to bf16 as wab_policy_kernel rounds them, and copied to
+// slice 0 of RollPolicy::features).  Phases, each closed by a workgroup barrier:
+//
+//   per chunk of KC input columns   all: this chunk's layer-1 fragments requested; the bits
+//                                   expanded to bf16 rows in region A (0 and 1 are exact)
+//                                   wave w: tiles w and w + 4 of layer 1, both 32-env tiles, the
+//                                   accumulators kept across the chunks (k-steps ascending)
+//   X1 -> region B                  wave w: bias, leaky_relu, bf16 (pol_store)
+//   layer 2: B -> A, layer 3: A -> B   wave w: tiles w, w + 4 (pol_layer)
+//   heads                           waves 0, 1: the head tile of envs 32 w .., lanes 0..31 the
+//                                   softmax, the value and the draw; the action to HBM and Lds::act
+//
+// Every sum is made by the functions of wab_policy_dev.h in wab_policy_kernel's order (one fp32
+// accumulator per output tile and env tile, zero-initialised, k-steps ascending), so the results
+// are wab_policy_act's bit for bit.  `episode` and `turn` are those of this lane's env (lane =
+// env of the group) at the time of the draw: the carried header after the step, not the handle's
+// HBM header, which is stale inside a multi-step launch.  The caller closes the phase with a
+// barrier before Lds::act is read.
+__device__ __forceinline__ uint4 carry_hdr(const CarryW0& c) { return c.hdr; }
+template <int SLOTS>
+__device__ __forceinline__ uint4 carry_hdr(const CarryW2<SLOTS>& c) { return c.hdr; }
+__device__ __forceinline__ uint4 carry_hdr(const CarryPtr<CarryHdr>& c) { return c.c.hdr; }
+
+template <bool FIRST>
+__device__ __forceinline__ void roll_policy(const Params& p, const SmallLayout& L, uint32_t* lds, int wave, int lane,
+                                            uint32_t episode, uint32_t turn, int t_out) {
+  const RollPolicy& q = p.pol;
+  const PolicyDims& d = q.d;
+  unsigned char* const smem = reinterpret_cast<unsigned char*>(lds);
+  uint16_t* const regA = reinterpret_cast<uint16_t*>(smem + q.reg_a);
+  uint16_t* const regB = reinterpret_cast<uint16_t*>(smem + q.reg_b);
+  const int r = lane & 31, h = lane >> 5;
+  const int64_t g0 = (int64_t)blockIdx.x * 64;
+  const int n_env = (int)min((int64_t)64, p.B - g0);
+  const uint32_t F = (uint32_t)d.F;
+  const uint4* const wimg = reinterpret_cast<const uint4*>(q.w);
+
+  // ---- layer 1: chunks of KC input columns through region A; wave w holds tiles w and w + 4
+  pol_f32x16 acc0[2], acc1[2];
+  pol_zero(acc0);
+  pol_zero(acc1);
+  const int KC = q.KC, pitch_in = q.pitch_in;
+  const int kpad = 16 * d.KS1;
+  uint4 wf[kPolicyMaxKs];
+  const uint4* const w1t = wimg + (d.w1 >> 3) + (size_t)wave * (size_t)d.KS1 * 64u + (size_t)lane;
+  for (int c = 0; c < q.n_chunks; ++c) {
+    const int k0 = c * KC;
+    const int kn = kpad - k0 < KC ? kpad - k0 : KC;  // columns of this chunk (a multiple of 16)
+    const int ks0 = k0 >> 4, nks = kn >> 4;
+    if (wave < d.NT1) pol_load_frags(wf, w1t + (size_t)ks0 * 64u, nks);
+    if (c > 0) lds_barrier();  // the last chunk's rows have been read
+    if constexpr (FIRST) {
+      // as wab_policy_kernel loads them: wave w takes rows w, w + 4, ..., a lane one column of the
+      // 16 rows, the loads issued together (addresses clamped into the batch; rows past it and the
+      // pad columns are stored as zeros)
+      const float* const f0 = q.features0 + (size_t)g0 * F;
+      float* const copy = q.features && q.features != q.features0 ? q.features + (size_t)g0 * F : nullptr;
+      for (int kl = lane; kl < kn; kl += 64) {
+        const int k = k0 + kl;
+        const bool kin = (uint32_t)k < F;
+        const float* col = f0 + (size_t)(kin ? (uint32_t)k : F - 1u);
+        float v[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int e = wave + 4 * i;
+          v[i] = col[(size_t)(e < n_env ? e : n_env - 1) * F];
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int e = wave + 4 * i;
+          const bool in = kin && e < n_env;
+          regA[(size_t)e * (size_t)pitch_in + (size_t)kl] = (uint16_t)(in ? pol_bf16(v[i]) : 0u);
+          if (copy && in) copy[(size_t)e * F + (uint32_t)k] = v[i];
+        }
+      }
+    } else {
+      // eight columns of one env per thread and pass: bits e F + k .. + 7 of the feature bits, as
+      // 16 bytes of its row (an inactive env's bits are zero: step_features emits nothing for it)
+      const uint32_t* const ob = lds + L.fbits;
+      const uint32_t nj = (uint32_t)kn >> 3;
+      for (uint32_t i = threadIdx.x; i < 64u * nj; i += 256u) {
+        const uint32_t e = i / nj, j = i - e * nj;
+        const uint32_t k = (uint32_t)k0 + 8u * j;
+        uint32_t bits = 0u;
+        if (k < F) {
+          const uint32_t at = e * F + k;  // (the word after the env's last is the bits' slack)
+          const uint64_t ww = (uint64_t)ob[at >> 5] | ((uint64_t)ob[(at >> 5) + 1u] << 32);
+          bits = (uint32_t)(ww >> (at & 31u));
+          bits &= F - k >= 8u ? 0xFFu : (1u << (F - k)) - 1u;
+        }
+        uint4 v;  // bf16 1.0 = 0x3F80
+        v.x = ((bits & 1u) ? 0x3F80u : 0u) | ((bits & 2u) ? 0x3F800000u : 0u);
+        v.y = ((bits & 4u) ? 0x3F80u : 0u) | ((bits & 8u) ? 0x3F800000u : 0u);
+        v.z = ((bits & 16u) ? 0x3F80u : 0u) | ((bits & 32u) ? 0x3F800000u : 0u);
+        v.w = ((bits & 64u) ? 0x3F80u : 0u) | ((bits & 128u) ? 0x3F800000u : 0u);
+        *reinterpret_cast<uint4*>(regA + (size_t)e * (size_t)pitch_in + (size_t)(8u * j)) = v;
+      }
+    }
+    lds_barrier();
+    const uint16_t* x = regA + (size_t)r * (size_t)pitch_in + 8 * h;
+    if (wave < d.NT1) pol_mma(acc0, wf, nks, x, pitch_in);
+    if (wave + 4 < d.NT1) {
+      pol_load_frags(wf, w1t + ((size_t)4 * (size_t)d.KS1 + (size_t)ks0) * 64u, nks);
+      pol_mma(acc1, wf, nks, x, pitch_in);
+    }
+  }
+  if (wave < d.NT1) pol_store<false>(acc0, q.b + d.b1, wave, regB, q.pitch1, lane);
+  if (wave + 4 < d.NT1) pol_store<false>(acc1, q.b + d.b1, wave + 4, regB, q.pitch1, lane);
+  const uint4* const w2 = wimg + (d.w2 >> 3), * const w3 = wimg + (d.w3 >> 3);
+  if (wave < d.NT2) pol_load_frags(wf, w2 + (size_t)wave * (size_t)d.KS2 * 64u + (size_t)lane, d.KS2);
+  lds_barrier();  // X1 complete; region A free
+
+  // ---- layer 2: X1 (region B) -> X2 (region A); layer 3: X2 -> X3 (region B), clamped
+  pol_layer<false, 2>(wf, w2, q.b + d.b2, d.NT2, d.KS2, regB, q.pitch1, regA, q.pitch2, wave, lane);
+  if (wave < d.NT3) pol_load_frags(wf, w3 + (size_t)wave * (size_t)d.KS3 * 64u + (size_t)lane, d.KS3);
+  lds_barrier();
+  pol_layer<true, 2>(wf, w3, q.b + d.b3, d.NT3, d.KS3, regA, q.pitch2, regB, q.pitch3, wave, lane);
+  if (wave < 2) pol_load_frags(wf, wimg + (d.wh >> 3) + (size_t)lane, d.KS4);
+  lds_barrier();
+
+  // ---- heads: waves 0 and 1, envs 32 w + (lane & 31); the draw's key from the env's own lane
+  if (wave < 2) {
+    const int my_env = 32 * wave + r;
+    const bool sampler = h == 0 && my_env < n_env;
+    const uint32_t ep = (uint32_t)__shfl((int)episode, my_env, 64), tu = (uint32_t)__shfl((int)turn, my_env, 64);
+    const pol_f32x16 acc = pol_head_mma(wf, d.KS4, regB + (size_t)my_env * (size_t)q.pitch3 + 8 * h);
+    const int64_t o = (int64_t)t_out * p.B;
+    const int a = pol_sample(acc, lane, sampler, q.b + d.bh, d.A, p.seed, p.env_base, g0 + my_env, ep, tu, q.actions + o,
+                             q.probs ? q.probs + o * d.A : nullptr, q.value ? q.value + o : nullptr);
+    if (sampler) reinterpret_cast<int8_t*>(lds + L.act)[my_env] = (int8_t)a;
+  }
 }
 
 }  // namespace
@@ -1690,8 +1841,12 @@ __device__ __forceinline__ void roll_apply(Params& p, const RollSlices& r) {
   p.t_planes = nullptr; p.t_food_turns = r.food_turns; p.t_role = r.role; p.t_status = r.status;
 }
 
-template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 1))) void wab_step_small(Params p0) {
+// POLICY (wab_rollout_policy; with FEAT and ROLL): the device policy chooses each step's actions
+// inside the launch (roll_policy); its fragments and accumulators sit next to the carried state,
+// so these instances take two waves per SIMD's registers
+template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES, bool POLICY = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(POLICY ? 2 : ROLL ? 4 : 1))) void wab_step_small(Params p0) {
+  static_assert(!POLICY || (FEAT && ROLL), "the policy build is a build of wab_rollout_features' kernel");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 #ifdef WAB_STAMPS
   uint64_t t_entry;  // before the first kernel-argument load
@@ -1768,6 +1923,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
     // t - 1's obs from the other one; the last step's obs go out at its end, by every thread
 #define WAB_ROLL_STEP(...)                                                                   \
     RollSlices io = roll_slices(wave_params<G, FEAT, RULES>(p0));                            \
+    if constexpr (POLICY) {  /* actions[0] from features0, keyed by the headers step 0 loads */ \
+      const Params p = wave_params<G, FEAT, RULES>(p0);                                      \
+      const int64_t g = (int64_t)blockIdx.x * 64 + lane;                                     \
+      const uint4 h0 = p.hdr[g < p.B ? g : 0];                                               \
+      roll_policy<true>(p, small_layout(p), lds, wave, lane, h0.w, h0.y, 0);                 \
+      lds_barrier();                                                                         \
+    }                                                                                        \
     for (int t = 0; t < T; ++t) {                                                            \
       ROLL_LOOP_STAMP(35, t == T / 2);  /* the middle step's loop top (before its parameters) */ \
       if (WAB_ROLL_THROTTLE && (wave == 0 || wave == 2)) __builtin_amdgcn_s_waitcnt(0x0F70);  \
@@ -1777,6 +1939,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
         roll_apply(p, io);                                                                   \
       } else {                                                                               \
         step_slice(p, t);                                                                    \
+      }                                                                                      \
+      float* rows = nullptr;  /* POLICY: where this step's feature rows go, if anywhere */    \
+      if constexpr (POLICY) {                                                                \
+        p.features = p.pol.features_last;  /* (non-null: the featurizer is on) */            \
+        rows = t == T - 1 ? p.pol.features_last                                              \
+               : p.pol.features ? p.pol.features + (int64_t)(t + 1) * p.B * p.pol.d.F : nullptr; \
       }                                                                                      \
       const SmallLayout L0 = small_layout(p);                                                \
       SmallLayout L = L0;                                                                    \
@@ -1792,7 +1960,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
       } else {                                                                               \
         __VA_ARGS__;                                                                         \
       }                                                                                      \
-      if (FEAT) step_features<true>(p, L, lds, wave, lane, t);  /* this step's rows */     \
+      if (FEAT) step_features<true, POLICY>(p, L, lds, wave, lane, t, rows);  /* this step's rows */ \
+      if constexpr (POLICY) {  /* the next step's actions, keyed by the envs' state after this one */ \
+        if (t < T - 1) {                                                                     \
+          const uint4 ch = carry_hdr(c);                                                     \
+          roll_policy<false>(p, L, lds, wave, lane, ch.w, ch.y, t + 1);                      \
+        }                                                                                    \
+      }                                                                                      \
       if (t == T - 1 && p.planes) {                                                          \
         lds_barrier();                                                                       \
         store_units_of<G, 0, 6, kWave>(p, lds + L.stream, lane);                               \
@@ -1805,21 +1979,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROLL ? 4 : 
       CarryW0 c;
       WAB_ROLL_STEP({
         role_prio<true>(3, t, p.features != nullptr);
-        bushes_wave<SLOTS, G, true, HOIST>(p, L, lds, lane, &c, t, t == T - 1);
+        bushes_wave<SLOTS, G, true, HOIST>(p, L, lds, lane, &c, t, t == T - 1, POLICY);
         role_prio<true>(0, t, p.features != nullptr);
       })
     } else if (wave == 1) {
       constexpr int kWave = 1;
       CarryPtr<CarryHdr> c;
-      WAB_ROLL_STEP((draws_wave<G, true, HOIST>(p, L, lds, lane, &c.c, t, t == T - 1)))
+      WAB_ROLL_STEP((draws_wave<G, true, HOIST>(p, L, lds, lane, &c.c, t, t == T - 1, POLICY)))
     } else if (wave == 2) {
       constexpr int kWave = 2;
       CarryW2<SLOTS> c;
-      WAB_ROLL_STEP((wolves_wave<SLOTS, G, true, HOIST>(p, L, lds, lane, &c, t, t == T - 1)))
+      WAB_ROLL_STEP((wolves_wave<SLOTS, G, true, HOIST>(p, L, lds, lane, &c, t, t == T - 1, POLICY)))
     } else {
       constexpr int kWave = 3;
       CarryPtr<CarryHdr> c;
-      WAB_ROLL_STEP((ring_wave<SLOTS, G, true, HOIST>(p, L, lds, lane, &c.c, t, t == T - 1)))
+      WAB_ROLL_STEP((ring_wave<SLOTS, G, true, HOIST>(p, L, lds, lane, &c.c, t, t == T - 1, POLICY)))
     }
 #undef WAB_ROLL_STEP
 #undef ROLL_LOOP_STAMP
@@ -1837,6 +2011,7 @@ template __global__ void wab_step_small<8, 11, false, false, true>(Params);
 template __global__ void wab_step_small<8, 11, true, false, true>(Params);
 template __global__ void wab_step_small<8, 11, false, true, true>(Params);
 template __global__ void wab_step_small<8, 11, true, true, true>(Params);
+template __global__ void wab_step_small<8, 11, true, true, true, true>(Params);  // wab_rollout_policy
 #endif
 #ifndef WAB_ONLY_WAVE  // (tools/isa_count.py reads the SLOTS = 8, G = 11 instances only)
 template __global__ void wab_step_small<8, 0, false, false, false>(Params);
@@ -1848,6 +2023,7 @@ template __global__ void wab_step_small<8, 11, false, false, false>(Params);
 template __global__ void wab_step_small<8, 11, true, false, false>(Params);
 template __global__ void wab_step_small<8, 11, false, true, false>(Params);
 template __global__ void wab_step_small<8, 11, true, true, false>(Params);
+template __global__ void wab_step_small<8, 11, true, true, false, true>(Params);  // wab_rollout_policy
 #ifndef WAB_ONLY_WAVE
 template __global__ void wab_step_small<16, 0, false, false, false>(Params);
 template __global__ void wab_step_small<16, 0, true, false, false>(Params);

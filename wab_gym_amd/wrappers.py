@@ -80,17 +80,28 @@ class PragmaticObsWrapper:
             self.features.copy_(r["features"][-1])  # as after T step() calls
         return r["features"], r["reward"], r["done"].view(self.env._torch.bool), r["returns"]
 
-    def rollout_policy(self, policy, T, gamma=0.99, store_planes=False):
+    def rollout_policy(self, policy, T, gamma=0.99, store_planes=False, store_features=True, return_probs=False,
+                       fused=None):
         """T closed-loop steps of actor_critic.main's loop (actor_critic.py:185-200) on the env's
-        stream: step t's action is sampled by `policy` (a DevicePolicy) from step t's features
-        (wab_policy_act), then the env steps (wab_step_features): two launches per step, no host
-        synchronisation, so the whole call can be captured in a graph.  It starts from the features
-        of the current observation (recomputed from the env's obs planes when they are valid, else
-        the wrapper's own `features` as its last reset()/step()/rollout left them).  Returns a
-        dict: features [T,B,F] f32 (features[t] is what actions[t] was chosen from), actions [T,B]
-        int8, reward [T,B] f32, done [T,B] u8, value [T,B] f32 and returns [T,B] f32
-        (discounted_returns(env=...), R after the last step = 0).  Afterwards the wrapper's
-        `features` and the env's scalars, reward and done show the last step."""
+        stream: step t's action is sampled by `policy` (a DevicePolicy) from step t's features, then
+        the env steps.  No host synchronisation, so the whole call can be captured in a graph.  It
+        starts from the features of the current observation (recomputed from the env's obs planes
+        when they are valid, else the wrapper's own `features` as its last reset()/step()/rollout
+        left them).  Returns a dict: features [T,B,F] f32 (features[t] is what actions[t] was chosen
+        from; None with store_features=False), actions [T,B] int8, reward [T,B] f32, done [T,B] u8,
+        value [T,B] f32, returns [T,B] f32 (discounted_returns(env=...), R after the last step = 0)
+        and, with return_probs, probs [T,B,A] f32.  Afterwards the wrapper's `features` and the
+        env's scalars, reward and done show the last step.
+
+        fused=None runs the call as one launch (wab_rollout_policy: the policy between the steps of
+        the multi-step kernel, the features never leaving the chip unless they are stored) where
+        wab_rollout_policy_fused says so and store_planes is False (store_planes=True writes each
+        step into the env's single obs buffer, which the launch's [T][B] layout does not express);
+        otherwise as the loop of wab_policy_act + wab_step_features, two launches per step.  Both
+        give the same bits (with T > 128 the returns of the one-launch path are made by
+        discounted_returns after it, as in the loop).  fused=False forces the loop; fused=True
+        raises NotImplementedError where the one launch does not apply.  store_features=False
+        stores no intermediate feature rows (the loop then alternates between two rows)."""
         from .env import BatchedWolvesAndBushesEnv
 
         env = self.env
@@ -110,30 +121,71 @@ class PragmaticObsWrapper:
         if T < 0:
             raise ValueError("T must be >= 0")
         dev = env.device
-        feats = t.empty((T, B, F), dtype=t.float32, device=dev)
+        L = _lib.load()
+        one_launch = fused is None or bool(fused)
+        if one_launch:
+            why = None
+            if store_planes:
+                why = "store_planes=True writes every step into the env's single obs buffer"
+            elif int(L.wab_rollout_policy_fused(env._h, policy._p)) != 1:
+                why = L.wab_last_error().decode(errors="replace") or "wab_rollout_policy_fused is 0"
+            if why is not None:
+                if fused:
+                    raise NotImplementedError("rollout_policy(fused=True): " + why)
+                one_launch = False
+        feats = t.empty((T, B, F), dtype=t.float32, device=dev) if store_features else None
         actions = t.empty((T, B), dtype=t.int8, device=dev)
         value = t.empty((T, B), dtype=t.float32, device=dev)
         rew = t.empty((T, B), dtype=t.float32, device=dev)
         done = t.empty((T, B), dtype=t.uint8, device=dev)
         out = {"features": feats, "actions": actions, "reward": rew, "done": done, "value": value,
                "returns": t.empty((T, B), dtype=t.float32, device=dev)}
+        probs = None
+        if return_probs:
+            probs = out["probs"] = t.empty((T, B, policy.n_actions), dtype=t.float32, device=dev)
         if T == 0:
             return out
         if env._planes_valid:
             self.observation()
-        feats[0].copy_(self.features)
-        L = _lib.load()
+        if feats is not None:
+            feats[0].copy_(self.features)
         o = env._obs["struct"]
+        if one_launch:
+            scal = t.empty((3, T, B), dtype=t.uint8, device=dev)
+            st = _lib.WabObs(None, scal[0].data_ptr(), scal[1].data_ptr(), scal[2].data_ptr())
+            in_launch = T <= 128  # (the launch's returns scan; longer segments: the kernel of the loop)
+            first = self.features if feats is None else feats
+            _lib.check(L.wab_rollout_policy(env._h, policy._p, first.data_ptr(), T, ctypes.addressof(st),
+                                            actions.data_ptr(), value.data_ptr(),
+                                            None if probs is None else probs.data_ptr(), rew.data_ptr(),
+                                            done.data_ptr(), None if feats is None else feats.data_ptr(),
+                                            self.features.data_ptr(), float(gamma), None,
+                                            out["returns"].data_ptr() if in_launch else None, env._stream()),
+                       "wab_rollout_policy")
+            env._sync_last_step(scal[:, T - 1], rew[T - 1], done[T - 1])
+            env._planes_valid = False
+            if not in_launch:
+                discounted_returns(rew, done, gamma=gamma, out=out["returns"], env=env)
+            return out
         st = o if store_planes else _lib.WabObs(None, o.food_turns, o.role, o.status)
         direct = (B * F) % 4 == 0  # every step's feature slice is 16-byte aligned
+        cur = self.features
+        spare = None if feats is not None else t.empty_like(self.features)
         for k in range(T):
-            policy.act(feats[k], out=actions[k], value=value[k])
-            nxt = feats[k + 1] if direct and k + 1 < T else self.features
+            src = cur if feats is None else feats[k]
+            policy.act(src, out=actions[k], value=value[k], probs=None if probs is None else probs[k])
+            if feats is None:
+                nxt = spare if cur is self.features else self.features
+            else:
+                nxt = feats[k + 1] if direct and k + 1 < T else self.features
             _lib.check(L.wab_step_features(env._h, actions[k].data_ptr(), ctypes.addressof(st),
                                            rew[k].data_ptr(), done[k].data_ptr(), nxt.data_ptr(),
                                            env._stream()), "wab_step_features")
-            if not direct and k + 1 < T:
+            if feats is not None and not direct and k + 1 < T:
                 feats[k + 1].copy_(self.features)
+            cur = nxt
+        if feats is None and cur is not self.features:
+            self.features.copy_(cur)
         env.reward.copy_(rew[T - 1])
         env.done.copy_(done[T - 1])
         env._planes_valid = bool(store_planes)
