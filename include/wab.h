@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define WAB_ABI_VERSION 8
+#define WAB_ABI_VERSION 9
 #define WAB_MAX_WOLF_SLOTS 32 /* largest per-env live-wolf slot count (wab_config.wolf_slots) */
 #define WAB_MAX_VIEW 63       /* largest odd width/height accepted */
 
@@ -470,6 +470,22 @@ int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int
  * kernels give the 53-bit draws U[n] under h's threshold table, computed by the kernels' own
  * bracketed search (bush_value_fast).  U, out device pointers. */
 int wab_debug_bush_values(wab_handle* h, const uint64_t* U, int32_t* out, int64_t n, void* stream);
+
+/* Test hook: which instance of the returns scan wab_discounted_returns (h == NULL) or
+ * wab_discounted_returns_exact (h) launches for these pointers and this B: out = {VEC, NE}.  VEC,
+ * the envs per thread, is 4, else 2, else 1: the widest with B % VEC == 0, B / VEC >= 65536,
+ * reward and returns aligned to 4 VEC bytes and done to VEC bytes.  NE is the number of the
+ * handle's step rewards whose float32 is not their double (0 without a handle), 5 to 7 padded
+ * to 8.  The launch takes its instance from the same host function.  Host only: launches
+ * nothing, reads no device memory.  WAB_E_INVALID where wab_discounted_returns_exact refuses
+ * the handle. */
+int wab_debug_returns_plan(const wab_handle* h, const float* reward, const uint8_t* done, const float* returns,
+                           int64_t B, int32_t out[2]);
+
+/* Test hook: how wab_policy_act runs this policy: out = {input chunks of layer 1, columns per
+ * chunk, columns of the last chunk, LDS bytes per workgroup, 1 for the instance with two
+ * layer-1 tiles per wave (h1 > 128) or 0}.  Host only. */
+int wab_debug_policy_plan(const wab_policy* p, int32_t out[5]);
 
 #ifdef __cplusplus
 }

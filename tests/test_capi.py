@@ -74,6 +74,34 @@ def test_library_loads_and_reports_abi():
     assert L.wab_num_actions(ctypes.addressof(cfg)) == 6
 
 
+def test_returns_plan_thresholds():
+    """wab_debug_returns_plan without a handle (host only: the pointers are never read): VEC is
+    the widest of 4, 2, 1 with B % VEC == 0, B / VEC >= 65536, reward and returns aligned to
+    4 VEC bytes and done to VEC bytes; NE is 0 without a reward table."""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("libwab_hip.so not built")
+    L = _lib.load()
+
+    def vec(B, reward=4096, done=8192, returns=12288):
+        out = (ctypes.c_int32 * 2)(-1, -1)
+        assert L.wab_debug_returns_plan(None, reward, done, returns, B, out) == 0
+        assert out[1] == 0
+        return out[0]
+
+    assert [vec(B) for B in (1, 65536, 131068, 131070, 131072, 131074, 262140, 262143, 262144, 262145, 262146,
+                             262148, 1 << 33)] == [1, 1, 1, 1, 2, 2, 2, 1, 4, 1, 2, 4, 4]
+    B = 262144
+    assert [vec(B, reward=4096 + o) for o in (4, 8, 12, 16)] == [1, 2, 1, 4]
+    assert [vec(B, returns=4096 + o) for o in (4, 8, 12, 16)] == [1, 2, 1, 4]
+    assert [vec(B, done=8192 + o) for o in (1, 2, 3, 4)] == [1, 2, 1, 4]
+    assert vec(B, reward=4104, done=8194, returns=12296) == 2
+    out = (ctypes.c_int32 * 2)()
+    assert L.wab_debug_returns_plan(None, None, 8192, 12288, B, out) == -1
+    assert L.wab_debug_returns_plan(None, 4096, 8192, 12288, -1, out) == -1
+    assert L.wab_debug_returns_plan(None, 4096, 8192, 12288, B, None) == -1
+    assert L.wab_debug_policy_plan(None, out) == -1
+
+
 def test_ctypes_layout_matches_c(tmp_path):
     prog = tmp_path / "layout.c"
     fields = [f for f, _ in WabConfig._fields_]

@@ -102,6 +102,75 @@ def step_reward_values(opts=None):
     return [0 + r for r in rx] + [0 + o["reward_for_eating"] + r for r in rx]
 
 
+def reward_table(opts=None):
+    """The table rule of wab_create, restated: the step rewards deduplicated by their float32
+    bits, as [(float32 bits, double)]; None when two different doubles share one float32 (the
+    doubles are then not recoverable and wab_discounted_returns_exact refuses the handle)."""
+    table = {}
+    for v in step_reward_values(opts):
+        v = float(v)
+        bits = int(np.float32(v).view(np.uint32))
+        if table.setdefault(bits, v) != v:
+            return None
+    return sorted(table.items())
+
+
+def inexact_count(opts=None):
+    """The entries of reward_table whose float32 is not their double: what the returns kernel
+    has to look up (NE of wab_returns_kernel<VEC, NE>, 5 to 7 padded to 8)."""
+    return sum(1 for bits, v in reward_table(opts) if float(np.uint32(bits).view(np.float32)) != v)
+
+
+def test_option_sets_select_every_reward_table_size():
+    """The option sets of tests/returns_cases.py have the inexact counts they are named for,
+    0, 1, 2, 3, 4, 6 and 8, so that together they launch every NE instance (0, 1, 2, 3, 4, 8) and
+    the padding of 6 up to 8; none has two rewards that collide in float32, and every inexact
+    entry changes the oracle's scan (its double differs from its float32)."""
+    import returns_cases as rc
+
+    assert reward_table({"reward_for_eating": 2.0 ** -30, "reward_per_turn": 1.0}) is None  # 1 + 2^-30 -> 1.0f
+    seen = set()
+    for name, _, ne in rc.OPTION_SETS:
+        opts = rc.options_of(name)
+        table = reward_table(opts)
+        assert table is not None, name
+        values = step_reward_values(opts)
+        assert len(table) == len({np.float32(v).tobytes() for v in values}) == len(set(map(float, values))), name
+        assert inexact_count(opts) == rc.INEXACT[name], name
+        assert rc.launched_ne(rc.INEXACT[name]) == ne, name
+        seen.add(ne)
+    assert seen == {0, 1, 2, 3, 4, 8}
+    assert rc.INEXACT["six"] == 6 and rc.launched_ne(5) == rc.launched_ne(7) == 8
+    assert inexact_count() == 3 and rc.options_of("defaults") == {}
+
+
+def test_returns_case_helper_has_every_edge():
+    """make_case: the three reward sources, the four done bytes with neighbours differing, the
+    forced dones at t = 0, T - 1, 31 and 32, an all-done and a never-done column."""
+    import returns_cases as rc
+
+    values = step_reward_values()
+    T, B = 65, 1000
+    reward, done, boot = rc.make_case(T, B, values)
+    assert reward.dtype == np.float32 and done.dtype == np.uint8 and boot.dtype == np.float32
+    table32 = np.asarray(values, np.float64).astype(np.float32)
+    assert all((reward == v).any() for v in table32)
+    assert (np.signbit(reward) & (reward == 0)).any()                      # -0.0
+    assert (~np.isin(reward, table32)).sum() > T * B // 8                  # arbitrary floats
+    assert set(np.unique(done).tolist()) == {0, 1, 0x80, 0xFF}
+    both = (done[:, :-1] != 0) & (done[:, 1:] != 0)
+    assert both.any() and (done[:, :-1][both] != done[:, 1:][both]).all()  # neighbours never share a byte
+    for c0, step in ((0, 1), (B - 1, -1)):
+        assert not done[:, c0].any() and done[:, c0 + step].all()
+        for k, t in enumerate((0, T - 1, 31, 32)):
+            assert done[t, c0 + (2 + k) * step]
+    assert rc.make_case(T, B, values, bootstrap=False)[2] is None
+    r1, d1, _ = rc.make_case(33, 1, values)
+    assert d1[0, 0] and d1[31, 0] and d1[32, 0]
+    again = rc.make_case(T, B, values)
+    assert np.array_equal(again[0].view(np.uint32), reward.view(np.uint32)) and np.array_equal(again[1], done)
+
+
 def test_returns_pinned_by_reference_finish_episode():
     """a14 pinned by the reference itself: tests/golden/returns.npz holds the double returns
     actor_critic.finish_episode computed (actor_critic.py:139-145, run unmodified by

@@ -2,7 +2,9 @@
 against reference_forward within half of E_bf16 (what the bf16 contract itself costs on the same
 inputs, tests/test_policy_host.py), actions exactly sample_reference of the kernel's own probs and
 the C oracle's (episode, turn); sharding, reloading, rollout_policy eager and graph-captured, and
-the refusals.
+the refusals.  Nets whose sums are exact in any order (policy_cases.exact_net) are compared bit
+for bit instead, at the shapes where policy_lds and the kernel's two instances change path, each
+asserted through wab_debug_policy_plan.
 
 Measured on an MI355X (max |kernel - reference_forward| / E_bf16, worst of the B cases): see
 DESIGN.md, "wab_policy_act"."""
@@ -128,6 +130,71 @@ def test_wide_net_two_layer1_tiles_per_wave():
     pol = policy.DevicePolicy(sd, env)
     probs, value = pol_outputs(pol, torch.as_tensor(x, device=DEV))
     check_outputs(sd, x, probs, value, "wide net B=%d" % B)
+    check_actions(pol.actions, probs, orc)
+
+
+def policy_plan(pol):
+    out = (ctypes.c_int32 * 5)(*[-1] * 5)
+    _lib.check(_lib.load().wab_debug_policy_plan(pol._p, out), "wab_debug_policy_plan")
+    return tuple(out)
+
+
+# The exact nets' probabilities differ from the reference's only by expf, the sum of A terms and
+# one divide.  Worst |p - p_ref| / p_ref measured on an MI355X over every exact case (p_ref the
+# float64 softmax of reference_forward): EXACT_PROBS_MEASURED; the gate is four times that, rounded
+# up to a power of two (expf's error varies with its argument and the cases sample only some).
+EXACT_PROBS_MEASURED = 2.269e-07  # 3.81 * 2^-24, at (16, 130, 8, 8, 6), B = 128
+EXACT_PROBS_GATE = 2.0 ** -20       # 9.54e-07 >= 4 * 2.269e-07 = 9.08e-07
+
+
+@pytest.mark.parametrize("B", pc.EXACT_BATCHES)
+@pytest.mark.parametrize("shape", list(pc.EXACT_SHAPES))
+def test_exact_net_is_bit_equal(shape, B):
+    """Nets whose every fp32 sum is exact in any order (pc.exact_certificate, asserted here on
+    this case's own inputs): a dropped pad column, two swapped units or a wrong fragment row has no
+    rounding band to hide in.  value == float32(reference value) bit for bit; actions are
+    sample_reference of the kernel's own probs; probs within EXACT_PROBS_GATE of the float64
+    softmax, relative; and the launch is the planned one (chunks, KC, last chunk, LDS, instance).
+    Worst relative probs error measured on an MI355X over all 50 cases: 2.269e-07 (3.81 * 2^-24);
+    the gate is 2^-20."""
+    F, A = shape[0], shape[4]
+    sd = pc.exact_net(shape)
+    x = pc.exact_features(B, F)
+    pc.exact_certificate(sd, x)
+    check_reference_has_every_path(sd, pc.exact_features(257, F))
+    opts = pc.OPTS_REF if A == 5 else pc.OPTS_ODD
+    env, _ = warmed_env(B, opts)
+    assert env.n_actions == A
+    orc = pc.oracle_after_warmup(B, opts)
+    pol = policy.DevicePolicy(sd, env)
+    assert policy_plan(pol) == pc.EXACT_SHAPES[shape]
+    probs, value = pol_outputs(pol, torch.as_tensor(x, device=DEV))
+    rp, rv = policy.reference_forward(sd, x)
+    want_v = rv.to(torch.float32)
+    assert torch.equal(want_v.double(), rv)  # (the certificate: the value is a float32)
+    assert np.array_equal(value.cpu().numpy().view(np.uint32), want_v.numpy().view(np.uint32))
+    check_actions(pol.actions, probs, orc)
+    p = probs.cpu().double()
+    ratio = float(((p - rp).abs() / rp).max())
+    print("exact net %s B=%d: worst |p - p_ref| / p_ref = %.3e (%.2f * 2^-24), smallest p_ref %.3e"
+          % (shape, B, ratio, ratio * 2.0 ** 24, float(rp.min())))
+    assert float((p.sum(1) - 1).abs().max()) <= 4 * A * 2.0 ** -23
+    assert ratio <= EXACT_PROBS_GATE, (shape, B, ratio)
+
+
+@pytest.mark.parametrize("B", [128, 257])
+@pytest.mark.parametrize("net", [(449, 129, 150, 128, 5), (449, 256, 256, 256, 5)])
+def test_widest_nets_with_random_weights(net, B):
+    """The first <true> net (NT1 = 5) and the all-256 net (two chunks, 132 KB of LDS) with
+    torch-initialised weights on real features, under the random-weight gate 0.5 * E_bf16."""
+    sd = pc.make_state_dict(net, 77)
+    check_reference_has_every_path(sd, pc.ref_features(257))
+    env, feats = warmed_env(B)
+    orc = pc.oracle_after_warmup(B)
+    pol = policy.DevicePolicy(sd, env)
+    assert policy_plan(pol)[4] == 1
+    probs, value = pol_outputs(pol, feats)
+    check_outputs(sd, pc.ref_features(B), probs, value, "net %s B=%d" % (net, B))
     check_actions(pol.actions, probs, orc)
 
 

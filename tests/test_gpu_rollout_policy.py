@@ -20,6 +20,8 @@ DEV = "cuda:0"
 WARM = 3
 NET_ODD449 = (449, 17, 40, 9, 5)      # nothing a multiple of the tile
 NET_WIDE449 = (449, 200, 256, 130, 5)  # two layer-1 tiles on every wave, eight layer-2 tiles
+NET_MAX449 = (449, 256, 256, 256, 5)   # every width at the limit
+NET_MIN449 = (449, 1, 1, 1, 5)         # every width at its minimum
 KEYS = ("features", "actions", "value", "probs", "reward", "done", "returns")
 # host-side tallies of how a call ran (one launch / per-step calls): they differ by design
 TALLIES = ("rollout_launches", "rollout_step_calls")
@@ -29,7 +31,7 @@ TALLIES = ("rollout_launches", "rollout_step_calls")
 def state_dict(net):
     if net == "ref":
         return pc.weights("ref")
-    return pc.make_state_dict({"odd": NET_ODD449, "wide": NET_WIDE449}[net], 4321)
+    return pc.make_state_dict({"odd": NET_ODD449, "wide": NET_WIDE449, "max": NET_MAX449, "min": NET_MIN449}[net], 4321)
 
 
 def closed_loop(B, opts, net="ref", base=0, warm=None, **env_kw):
@@ -138,10 +140,11 @@ def test_default_rules_instance():
     assert_left_behind(env, w, left)
 
 
-@pytest.mark.parametrize("net,T", [("odd", 5), ("wide", 3)])
+@pytest.mark.parametrize("net,T", [("odd", 5), ("wide", 3), ("max", 3), ("min", 5)])
 def test_other_widths(net, T):
-    """449-17-40-9-5 (no width a multiple of the tile) and 449-200-256-130-5 (the widest layers:
-    two layer-1 tiles on every wave) are fused and equal the loop."""
+    """449-17-40-9-5 (no width a multiple of the tile), 449-200-256-130-5 (the widest layers:
+    two layer-1 tiles on every wave), 449-256-256-256-5 (every width at the limit) and 449-1-1-1-5
+    (every width at its minimum) are fused and equal the loop."""
     B = 68
     env, w, pol = closed_loop(B, pc.OPTS_REF, net)
     assert fused_flag(env, pol) == 1

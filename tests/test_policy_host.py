@@ -125,3 +125,39 @@ def test_contract_cost_E_bf16(capsys):
     with capsys.disabled():
         for r in rows:
             print("E_bf16 net %-3s B %3d: probs %.3e value %.3e" % r)
+
+
+@pytest.mark.parametrize("shape", list(pc.EXACT_SHAPES))
+def test_exact_nets_hold_their_certificate(shape):
+    """The exact-arithmetic nets of tests/test_gpu_policy.py: every fp32 sum of the forward pass is
+    exact in any order and the float32 activation step gives the reference's bf16 values
+    (pc.exact_certificate), every column and unit carries a weight, all numbers are small dyadic,
+    and the reference alone has negative pre-activations in every hidden layer and units at both
+    clamp limits."""
+    sd = pc.exact_net(shape)
+    assert policy.shape_of(sd) == shape
+    for name in policy.LAYERS:
+        w, b = sd[name + ".weight"], sd[name + ".bias"]
+        assert bool((w != 0).any(dim=0).all()) and bool((w != 0).any(dim=1).all()), name
+        for x in (w, b):
+            assert torch.equal(x * 4, (x * 4).round()) and float(x.abs().max()) <= 448, name  # multiples of 1/4
+        if name != "value_head":  # sparse: three picked columns and a unit's share of the columns nobody picked
+            assert int((w != 0).sum(dim=1).max()) <= 3 + -(-w.shape[1] // w.shape[0]), name
+    F = shape[0]
+    x = pc.exact_features(257, F)
+    assert x.min() >= 0 and x.max() <= 2 and np.array_equal(x * 8, np.round(x * 8))
+    assert ((x != 0) & (x != 1)).any() and (x == 1).any() and (x == 0).any()
+    for B in pc.EXACT_BATCHES:
+        assert pc.exact_certificate(sd, pc.exact_features(B, F)) > 0
+    hidden = []
+    rp, _ = policy.reference_forward(sd, x, hidden=hidden)
+    assert all(bool((z < 0).any()) for z, _ in hidden)
+    assert bool((hidden[2][1] == 4.0).any()) and bool((hidden[2][1] == -4.0).any())
+    assert float(rp.min()) > 1e-30  # every probability a normal float32, far from underflow
+
+
+def test_exact_certificate_refuses_an_ordinary_net():
+    """Random weights round in nearly every sum: the certificate must not pass them."""
+    with pytest.raises(AssertionError):
+        pc.exact_certificate(pc.weights("odd"), pc.odd_features(65))
+    assert pc._low_bit_exponent(np.array([0.0, 1.0, 0.75, -96.0, 2.0 ** -20])).tolist() == [1 << 20, 0, -2, 5, -20]

@@ -21,7 +21,7 @@ EXPORTED = [
     "wab_bush_thresholds", "wab_rollout_features", "wab_render_envs", "wab_set_obs_placement",
     "wab_snapshot_bytes", "wab_snapshot_hash", "wab_snapshot_save", "wab_snapshot_restore",
     "wab_policy_create", "wab_policy_load", "wab_policy_act", "wab_policy_destroy",
-    "wab_rollout_policy", "wab_rollout_policy_fused",
+    "wab_rollout_policy", "wab_rollout_policy_fused", "wab_debug_returns_plan", "wab_debug_policy_plan",
     # include/wab_torus.h: the Environment 2.0 torus world
     "wab2_abi_version", "wab2_last_error", "wab2_record_size", "wab2_create", "wab2_destroy",
     "wab2_batch", "wab2_reset", "wab2_step", "wab2_rollout", "wab2_get_state", "wab2_get_counters",
@@ -31,7 +31,7 @@ EXPORTED = [
 ABI2_VERSION = 1
 OBS_SAME_BUFFER, OBS_FRESH_BUFFER = 0, 1  # wab_set_obs_placement
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 SNAPSHOT_MAGIC, SNAPSHOT_VERSION = 0x53424157, 1  # 'WABS' (wab_snapshot_info)
 
 
@@ -127,6 +127,8 @@ def load():
     L.wab_policy_destroy.argtypes = [P]
     L.wab_rollout_policy_fused.argtypes = [P, P]
     L.wab_rollout_policy.argtypes = [P, P, P, I32, P, P, P, P, P, P, P, P, ctypes.c_double, P, P, P]
+    L.wab_debug_returns_plan.argtypes = [P, P, P, P, I64, P]
+    L.wab_debug_policy_plan.argtypes = [P, P]
     L.wab2_abi_version.restype = ctypes.c_int
     L.wab2_last_error.restype = ctypes.c_char_p
     L.wab2_record_size.argtypes = [P]

@@ -513,9 +513,17 @@ bool feat_small_ok(const Params& p) {
 // the discounted-return scan: VEC envs per thread, the widest whose grid still gives each of
 // the 1024 SIMDs a 64-thread wave and whose rows stay aligned; the reward table reduced to the
 // entries whose float32 is not the double itself (the others convert exactly)
-int launch_returns(const float* reward, const uint8_t* done, int32_t T, int64_t B, double gamma,
-                   const float* bootstrap, float* returns, const wab::RewardTable& tab, void* stream) {
-  wab::RewardTable inexact;
+// The choice is made here alone, on the host, and launches nothing: launch_returns runs what
+// this returns and wab_debug_returns_plan reports it.
+struct ReturnsPlan {
+  int vec, ne;               // the instance wab_returns_kernel<vec, ne>
+  wab::RewardTable inexact;  // its table: the inexact entries, padded to ne
+};
+
+ReturnsPlan returns_plan(const float* reward, const uint8_t* done, const float* returns, int64_t B,
+                         const wab::RewardTable& tab) {
+  ReturnsPlan plan;
+  wab::RewardTable& inexact = plan.inexact;
   std::memset(&inexact, 0, sizeof(inexact));
   for (int k = 0; k < tab.n; ++k) {
     float f;
@@ -531,12 +539,20 @@ int launch_returns(const float* reward, const uint8_t* done, int32_t T, int64_t 
     return B % v == 0 && B / v >= 64 * 1024 && ((uintptr_t)reward & a) == 0 && ((uintptr_t)returns & a) == 0 &&
            ((uintptr_t)done & (uintptr_t)(v - 1)) == 0;
   };
-  const int vec = fits(4) ? 4 : fits(2) ? 2 : 1;
-  const int ne = inexact.n <= 4 ? inexact.n : 8;
-  for (int k = inexact.n; k < ne; ++k) {  // pads: copies of entry 0 (same key, same value)
+  plan.vec = fits(4) ? 4 : fits(2) ? 2 : 1;
+  plan.ne = inexact.n <= 4 ? inexact.n : 8;
+  for (int k = inexact.n; k < plan.ne; ++k) {  // pads: copies of entry 0 (same key, same value)
     inexact.f32[k] = inexact.f32[0];
     inexact.f64[k] = inexact.f64[0];
   }
+  return plan;
+}
+
+int launch_returns(const float* reward, const uint8_t* done, int32_t T, int64_t B, double gamma,
+                   const float* bootstrap, float* returns, const wab::RewardTable& tab, void* stream) {
+  const ReturnsPlan plan = returns_plan(reward, done, returns, B, tab);
+  const int vec = plan.vec, ne = plan.ne;
+  const wab::RewardTable& inexact = plan.inexact;
   const dim3 grid((unsigned)((B / vec + 63) / 64));
   hipStream_t s = (hipStream_t)stream;
 #define WAB_RET(V, N) \
@@ -583,6 +599,9 @@ float* bounce_rows(wab_handle* h, size_t row_floats) {
   }
   return h->bounce_rows;
 }
+
+// which wab_policy_kernel instance a net takes: <true> for h1 > 128, two layer-1 tiles per wave
+bool policy_two_tiles(const wab::PolicyDims& d) { return d.NT1 > 4; }
 
 // wab_rollout_policy as one launch: the POLICY instances of the small kernel (8 slots, 11x11)
 void* roll_policy_kernel(bool rules) {
@@ -1542,8 +1561,8 @@ int wab_policy_create(const wab_policy_shape* shape, int device, wab_policy** ou
     return fail(WAB_E_INVALID, "wab_policy_create: the device's LDS is smaller than the kernel needs");
   }
   if (e == hipSuccess)
-    e = hipFuncSetAttribute(p->dims.NT1 > 4 ? reinterpret_cast<void*>(&wab::wab_policy_kernel<true>)
-                                            : reinterpret_cast<void*>(&wab::wab_policy_kernel<false>),
+    e = hipFuncSetAttribute(policy_two_tiles(p->dims) ? reinterpret_cast<void*>(&wab::wab_policy_kernel<true>)
+                                                      : reinterpret_cast<void*>(&wab::wab_policy_kernel<false>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
   // the same for wab_rollout_policy's one-launch instances on this device (both: which one a
   // handle takes depends on its options)
@@ -1628,7 +1647,7 @@ int wab_policy_act(wab_handle* h, wab_policy* p, const float* features, int8_t* 
   pp.b = p->b;
   DeviceGuard guard(h->device);
   const dim3 grid((unsigned)((h->p.B + wab::kPolicyEnvs - 1) / wab::kPolicyEnvs));
-  if (p->dims.NT1 > 4)  // h1 > 128: two layer-1 tiles per wave
+  if (policy_two_tiles(p->dims))
     hipLaunchKernelGGL(wab::wab_policy_kernel<true>, grid, dim3(256), p->lds.total, (hipStream_t)stream, pp);
   else
     hipLaunchKernelGGL(wab::wab_policy_kernel<false>, grid, dim3(256), p->lds.total, (hipStream_t)stream, pp);
@@ -1783,6 +1802,32 @@ int wab_debug_bush_values(wab_handle* h, const uint64_t* U, int32_t* out, int64_
   hipLaunchKernelGGL(bush_values_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, h->p.thresholds,
                      h->p.max_berries, h->p.bush_power, U, out, n);
   HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+int wab_debug_returns_plan(const wab_handle* h, const float* reward, const uint8_t* done, const float* returns,
+                           int64_t B, int32_t out[2]) {
+  g_err.clear();
+  if (!reward || !done || !returns || B < 0 || !out) return fail(WAB_E_INVALID, "wab_debug_returns_plan: bad argument");
+  if (h && h->rewards.n < 0)
+    return fail(WAB_E_INVALID, "wab_debug_returns_plan: two of the options' rewards round to the same float32; "
+                               "wab_discounted_returns_exact refuses this handle");
+  wab::RewardTable none;
+  std::memset(&none, 0, sizeof(none));
+  const ReturnsPlan plan = returns_plan(reward, done, returns, B, h ? h->rewards : none);
+  out[0] = plan.vec;
+  out[1] = plan.ne;
+  return WAB_OK;
+}
+
+int wab_debug_policy_plan(const wab_policy* p, int32_t out[5]) {
+  g_err.clear();
+  if (!p || !out) return fail(WAB_E_INVALID, "wab_debug_policy_plan: NULL argument");
+  out[0] = p->lds.n_chunks;
+  out[1] = p->lds.KC;
+  out[2] = 16 * p->dims.KS1 - (p->lds.n_chunks - 1) * p->lds.KC;
+  out[3] = (int32_t)p->lds.total;
+  out[4] = policy_two_tiles(p->dims) ? 1 : 0;
   return WAB_OK;
 }
 
