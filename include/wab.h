@@ -34,6 +34,10 @@
  *                            + gym.spaces.flatten                    actor_critic.py:188
  *   wab_discounted_returns<- finish_episode's return loop             actor_critic.py:139-143
  *   wab_discounted_returns_exact <- the same on the env's own rewards   actor_critic.py:139-145
+ *   wab_episode_stats_update <- gym.wrappers.Monitor's episode returns   actor_critic.py:46,
+ *                            and lengths, over a [T][B] segment          210-224
+ *   wab_normalize_episode_returns <- finish_episode's (R - mean) /       actor_critic.py:145-146
+ *                            (std + eps), per episode
  *   wab_snapshot_save / wab_snapshot_restore <- (no counterpart: the reference has no
  *                            checkpoint, resume or rewind of an env)
  *   wab_policy_act        <- Policy.forward + select_action's sample  actor_critic.py:76-125
@@ -50,7 +54,7 @@
 extern "C" {
 #endif
 
-#define WAB_ABI_VERSION 9
+#define WAB_ABI_VERSION 10
 #define WAB_MAX_WOLF_SLOTS 32 /* largest per-env live-wolf slot count (wab_config.wolf_slots) */
 #define WAB_MAX_VIEW 63       /* largest odd width/height accepted */
 
@@ -320,6 +324,43 @@ int wab_discounted_returns(const float* reward, const uint8_t* done, int32_t T, 
 int wab_discounted_returns_exact(const wab_handle* h, const float* reward, const uint8_t* done, int32_t T,
                                  int64_t B, double gamma, const float* bootstrap, float* returns,
                                  void* stream);
+
+/* ---- per-episode statistics of a rollout segment ----------------------------------- */
+
+/* Bytes of device workspace wab_episode_stats_update needs for a [T][B] segment (may be 0 for
+ * T = 0), or WAB_E_INVALID (T < 0, B outside [1, 2^31), T * ceil(B / 64) >= 2^39). */
+int64_t wab_episode_stats_workspace(int32_t T, int64_t B);
+
+/* The episode returns and lengths gym.wrappers.Monitor keeps for the reference's training loop
+ * (actor_critic.py:46, its "running reward" :210-224), over the reward f32 / done u8 [T][B] of a
+ * rollout segment, for all B envs at once.  `ret` f64 [B] and `length` i64 [B] are the caller's
+ * running state, read and written: for t = 0..T-1 in order, per env, ret += r, length += 1, and
+ * where done[t][b] one finished episode (ret, length, env b, step t) is emitted and ret and
+ * length restart at 0.  With a handle each float32 reward is first mapped to the exact double the
+ * reference's step() returns (the table and rule of wab_discounted_returns_exact), so an
+ * episode's return is the Monitor's own sum of Python floats bit for bit; with h = NULL rewards
+ * are used as given.  The double adds of an env happen in step order.
+ * The finished episodes are written compacted into ep_return f64, ep_length i32, ep_env i32 and
+ * ep_step i32, each [capacity], in ascending (step, env) order; count i64 [2] receives
+ * {finished, written}: when finished > capacity only the first `capacity` episodes of that order
+ * are written and nothing past `capacity` is touched.  The four arrays may be NULL with
+ * capacity 0 (count only).  workspace: wab_episode_stats_workspace(T, B) bytes, 8-byte aligned,
+ * its contents meaningless before and after.  All pointers device; stream-ordered, no host
+ * synchronisation, no atomics: the output is the same on every run.  T = 0 writes count = {0, 0}.
+ * WAB_E_INVALID if two of the handle's rewards round to the same float32. */
+int wab_episode_stats_update(const wab_handle* h, const float* reward, const uint8_t* done, int32_t T,
+                             int64_t B, double* ret, int64_t* length, double* ep_return, int32_t* ep_length,
+                             int32_t* ep_env, int32_t* ep_step, int64_t capacity, int64_t* count,
+                             void* workspace, void* stream);
+
+/* finish_episode's normalisation (actor_critic.py:145-146) per episode of a returns f32 / done u8
+ * [T][B] segment: in every env's column a segment ends at each done, and one still open at step
+ * T - 1 is normalised as it stands.  Per segment of n steps, in float64, sequential in step order:
+ * mean = sum(x) / n, var = sum((x - mean)^2) / (n - 1) (torch.std is unbiased),
+ * out = float32((x - mean) / (sqrt(var) + eps)); a one-step segment gives NaN, as torch.std does.
+ * out f32 [T][B] may be `returns` itself.  All pointers device. */
+int wab_normalize_episode_returns(const float* returns, const uint8_t* done, int32_t T, int64_t B, double eps,
+                                  float* out, void* stream);
 
 /* ---- snapshots: save and restore env state ---------------------------------------- */
 

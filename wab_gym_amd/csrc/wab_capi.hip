@@ -19,6 +19,7 @@
 #include "wab_device.h"
 #include "wab_feat.h"
 #include "wab_policy.h"
+#include "wab_episodes.h"
 
 namespace wab {
 template <int MODE, int SLOTS, bool SMALL>
@@ -38,6 +39,13 @@ template <int VEC, int NE>
 __global__ void wab_returns_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done, int32_t T,
                                    int64_t B, double gamma, const float* __restrict__ bootstrap,
                                    float* __restrict__ out, RewardTable tab);
+__global__ void wab_episode_count_kernel(EpisodeParams p);
+__global__ void wab_episode_scan_kernel(EpisodeParams p);
+template <int NE>
+__global__ void wab_episode_walk_kernel(EpisodeParams p);
+__global__ void wab_normalize_kernel(const float* x, const uint8_t* done, int32_t T, int64_t B, double eps, float* out);
+__global__ void wab_normalize_lds_kernel(const float* x, const uint8_t* done, int32_t T, int64_t B, double eps,
+                                         float* out);
 __global__ void wab_snapshot_pack(SnapParams p);
 __global__ void wab_snapshot_unpack(SnapParams p);
 __global__ void wab_policy_pack(PolicyPackParams p);
@@ -520,10 +528,10 @@ struct ReturnsPlan {
   wab::RewardTable inexact;  // its table: the inexact entries, padded to ne
 };
 
-ReturnsPlan returns_plan(const float* reward, const uint8_t* done, const float* returns, int64_t B,
-                         const wab::RewardTable& tab) {
-  ReturnsPlan plan;
-  wab::RewardTable& inexact = plan.inexact;
+// the entries of `tab` whose float32 is not the double itself, and the NE instance that holds
+// them (0..4, or 8), padded to it with copies of entry 0 (same key, same value)
+wab::RewardTable inexact_rewards(const wab::RewardTable& tab, int* ne) {
+  wab::RewardTable inexact;
   std::memset(&inexact, 0, sizeof(inexact));
   for (int k = 0; k < tab.n; ++k) {
     float f;
@@ -534,17 +542,24 @@ ReturnsPlan returns_plan(const float* reward, const uint8_t* done, const float* 
       inexact.n++;
     }
   }
+  *ne = inexact.n <= 4 ? inexact.n : 8;
+  for (int k = inexact.n; k < *ne; ++k) {
+    inexact.f32[k] = inexact.f32[0];
+    inexact.f64[k] = inexact.f64[0];
+  }
+  return inexact;
+}
+
+ReturnsPlan returns_plan(const float* reward, const uint8_t* done, const float* returns, int64_t B,
+                         const wab::RewardTable& tab) {
+  ReturnsPlan plan;
+  plan.inexact = inexact_rewards(tab, &plan.ne);
   const auto fits = [&](int v) {
     const uintptr_t a = 4u * (uintptr_t)v - 1u;
     return B % v == 0 && B / v >= 64 * 1024 && ((uintptr_t)reward & a) == 0 && ((uintptr_t)returns & a) == 0 &&
            ((uintptr_t)done & (uintptr_t)(v - 1)) == 0;
   };
   plan.vec = fits(4) ? 4 : fits(2) ? 2 : 1;
-  plan.ne = inexact.n <= 4 ? inexact.n : 8;
-  for (int k = inexact.n; k < plan.ne; ++k) {  // pads: copies of entry 0 (same key, same value)
-    inexact.f32[k] = inexact.f32[0];
-    inexact.f64[k] = inexact.f64[0];
-  }
   return plan;
 }
 
@@ -1401,6 +1416,101 @@ int wab_discounted_returns_exact(const wab_handle* h, const float* reward, const
   if (T == 0 || B == 0) return WAB_OK;
   DeviceGuard guard(h->device);
   return launch_returns(reward, done, T, B, gamma, bootstrap, returns, h->rewards, stream);
+}
+
+namespace {
+// the count table of wab_episode_stats_update (wab_episodes.h): W waves per step, N entries,
+// n_tiles tiles; false where the table is larger than a grid can cover
+bool episode_table(int32_t T, int64_t B, int64_t* W, int64_t* N, int64_t* n_tiles) {
+  *W = (B + 63) / 64;
+  *N = (int64_t)T * *W;
+  *n_tiles = (*N + wab::kEpTile - 1) / wab::kEpTile;
+  return *n_tiles <= 0x7FFFFFFF;
+}
+}  // namespace
+
+int64_t wab_episode_stats_workspace(int32_t T, int64_t B) {
+  g_err.clear();
+  int64_t W, N, n_tiles;
+  if (T < 0 || B < 1 || B > 0x7FFFFFFF || !episode_table(T, B, &W, &N, &n_tiles))
+    return fail(WAB_E_INVALID, "wab_episode_stats_workspace: T >= 0, 1 <= B < 2^31 and T * ceil(B / 64) < 2^39");
+  return n_tiles * 8 + N * 4;  // tile_off i64 [n_tiles], then local u32 [N]
+}
+
+int wab_episode_stats_update(const wab_handle* h, const float* reward, const uint8_t* done, int32_t T, int64_t B,
+                             double* ret, int64_t* length, double* ep_return, int32_t* ep_length, int32_t* ep_env,
+                             int32_t* ep_step, int64_t capacity, int64_t* count, void* workspace, void* stream) {
+  g_err.clear();
+  wab::EpisodeParams q;
+  std::memset(&q, 0, sizeof(q));
+  if (T < 0 || B < 1 || B > 0x7FFFFFFF || !episode_table(T, B, &q.W, &q.N, &q.n_tiles))
+    return fail(WAB_E_INVALID, "wab_episode_stats_update: T >= 0, 1 <= B < 2^31 and T * ceil(B / 64) < 2^39");
+  if (!ret || !length || !count || capacity < 0 || (T > 0 && (!reward || !done)))
+    return fail(WAB_E_INVALID, "wab_episode_stats_update: bad argument");
+  if (capacity > 0 && (!ep_return || !ep_length || !ep_env || !ep_step))
+    return fail(WAB_E_INVALID, "wab_episode_stats_update: the record arrays may be NULL with capacity 0 only");
+  if (T > 0 && (!workspace || ((uintptr_t)workspace & 7u) != 0))
+    return fail(WAB_E_INVALID, "wab_episode_stats_update: workspace must be 8-byte aligned and hold "
+                               "wab_episode_stats_workspace(T, B) bytes");
+  if (h && h->rewards.n < 0)
+    return fail(WAB_E_INVALID, "wab_episode_stats_update: two of the options' rewards round to the same "
+                               "float32; the double rewards are not recoverable");
+  int ne = 0;
+  if (h) q.tab = inexact_rewards(h->rewards, &ne);
+  q.reward = reward;
+  q.done = done;
+  q.T = T;
+  q.B = B;
+  q.ret = ret;
+  q.length = length;
+  q.ep_return = ep_return;
+  q.ep_length = ep_length;
+  q.ep_env = ep_env;
+  q.ep_step = ep_step;
+  q.capacity = capacity;
+  q.count = count;
+  q.tile_off = static_cast<int64_t*>(workspace);
+  q.local = reinterpret_cast<uint32_t*>(q.tile_off + q.n_tiles);
+  int device = 0;
+  if (h) device = h->device;
+  else HIP_TRY(hipGetDevice(&device));
+  DeviceGuard guard(device);
+  hipStream_t s = (hipStream_t)stream;
+  if (T > 0) hipLaunchKernelGGL(wab::wab_episode_count_kernel, dim3((unsigned)q.n_tiles), dim3(256), 0, s, q);
+  hipLaunchKernelGGL(wab::wab_episode_scan_kernel, dim3(1), dim3(256), 0, s, q);  // (T = 0: count = {0, 0})
+  if (T > 0) {
+    const dim3 grid((unsigned)q.W);
+#define WAB_WALK(N) hipLaunchKernelGGL((wab::wab_episode_walk_kernel<N>), grid, dim3(64), 0, s, q)
+    switch (ne) {
+      case 0: WAB_WALK(0); break;
+      case 1: WAB_WALK(1); break;
+      case 2: WAB_WALK(2); break;
+      case 3: WAB_WALK(3); break;
+      case 4: WAB_WALK(4); break;
+      default: WAB_WALK(8);
+    }
+#undef WAB_WALK
+  }
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+int wab_normalize_episode_returns(const float* returns, const uint8_t* done, int32_t T, int64_t B, double eps,
+                                  float* out, void* stream) {
+  g_err.clear();
+  if (!returns || !done || !out || T < 0 || B < 0)
+    return fail(WAB_E_INVALID, "wab_normalize_episode_returns: bad argument");
+  if (T == 0 || B == 0) return WAB_OK;
+  if ((B + 63) / 64 > 0x7FFFFFFF) return fail(WAB_E_INVALID, "wab_normalize_episode_returns: B too large");
+  const dim3 grid((unsigned)((B + 63) / 64));
+  if (T <= wab::kNormLdsSteps)  // the wave's columns in LDS, T x 64 floats
+    hipLaunchKernelGGL(wab::wab_normalize_lds_kernel, grid, dim3(64), (size_t)T * 256u, (hipStream_t)stream, returns,
+                       done, T, B, eps, out);
+  else
+    hipLaunchKernelGGL(wab::wab_normalize_kernel, grid, dim3(64), 0, (hipStream_t)stream, returns, done, T, B, eps,
+                       out);
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
 }
 
 namespace {

@@ -25,9 +25,16 @@ step's double is recovered exactly from the few values a step can produce, `r_x`
 `r_eat + r_x` for r_x in (per turn, finishing, starving, killed) (wab_env.py:299-340), then
 summed in float64 on device.  Finished episodes are gathered every `flush_every` steps (one
 host synchronisation), so the per-step path stays asynchronous.
+
+The multi-step launches (`rollout`, `rollout_features`, `rollout_policy`) are accounted a whole
+[T, B] segment at a time: `EpisodeStats.update_rollout` is one call of wab_episode_stats_update
+(include/wab.h), the same adds in the same order as T `update` calls, its finished episodes
+compacted on device in (step, env) order and gathered at the next flush.  The episodes of one such
+call share one timestamp (the call's), and rollouts record no video.
 """
 from __future__ import annotations
 
+import ctypes
 import json
 import os
 import time
@@ -58,13 +65,19 @@ class EpisodeStats:
     """Per-env episode return (float64) and length on device; finished episodes are gathered
     into host lists in (step, env) order by flush()."""
 
-    def __init__(self, game_options, num_envs, device, flush_every=32):
+    MAX_QUEUED = 4  # rollout segments held on device before update_rollout flushes on its own
+
+    def __init__(self, game_options, num_envs, device, flush_every=32, handle=None):
         import torch
 
         self._torch = torch
         self.num_envs = int(num_envs)
         self.device = torch.device(device)
         self.flush_every = int(flush_every)
+        self._game_options = game_options
+        self._handle = handle  # the env's wab_handle (its exact reward table), for update_rollout
+        self._own_handle = None
+        self._queue = []  # pending segments in finishing order: ("steps", ...) or ("rollout", ...)
         tab = reward_table(game_options)
         self._f32 = torch.tensor([f for f, _ in tab], dtype=torch.float32, device=self.device)
         self._f64 = torch.tensor([d for _, d in tab], dtype=torch.float64, device=self.device)
@@ -111,20 +124,128 @@ class EpisodeStats:
         if len(self._times) == self.flush_every:
             self.flush()
 
-    def flush(self):
-        """Gather the episodes finished since the last flush (synchronises)."""
+    def _rollout_handle(self):
+        """The wab_handle whose reward table update_rollout uses: the env's, or one of this
+        object's own (one env, made from the game options) when it was built without."""
+        if self._handle is not None:
+            return self._handle
+        if self._own_handle is None:
+            from . import _lib
+            from .options import make_config
+
+            cfg, self._own_keep = make_config(self._game_options)
+            dev = self.device.index if self.device.index is not None else self._torch.cuda.current_device()
+            h = ctypes.c_void_p()
+            _lib.check(_lib.load().wab_create(ctypes.addressof(cfg), 1, 0, 0, dev, ctypes.byref(h)), "wab_create")
+            self._own_handle = h
+        return self._own_handle
+
+    def __del__(self):
+        h, self._own_handle = getattr(self, "_own_handle", None), None
+        if h is not None:
+            try:
+                from . import _lib
+
+                _lib.load().wab_destroy(h)
+            except Exception:
+                pass
+
+    def _queue_steps(self):
+        """Move the per-step entries not yet gathered into the queue (device copies, no
+        synchronisation), so that what is recorded after them is gathered after them."""
         k = len(self._times)
-        if k == 0:
+        if k:
+            self._queue.append(("steps", self._buf_ret[:k].clone(), self._buf_len[:k].clone(), self._times))
+            self._times = []
+
+    def update_rollout(self, reward, done, max_episodes=None):
+        """T steps of every env at once: `reward` and `done` [T, B] of a multi-step launch, the same
+        statistics as T update() calls (the same double adds in the same order).  On a HIP device it
+        is one wab_episode_stats_update call on the current stream, without host synchronisation: the
+        finished episodes stay on device, compacted in (step, env) order, until flush(); after
+        MAX_QUEUED such segments the next call flushes first.  max_episodes bounds the episodes one
+        call can record (device buffers of that many records, 20 bytes each); None means T * B, which
+        cannot overflow; when more finish than a smaller bound holds, flush() raises RuntimeError
+        naming both numbers, after recording the first max_episodes.  All episodes of one call get
+        the call's timestamp.  CPU tensors take the update() loop."""
+        t = self._torch
+        reward, done = t.as_tensor(reward), t.as_tensor(done)
+        if reward.dim() != 2 or reward.shape[1] != self.num_envs:
+            raise ValueError("reward must have shape [T, %d], not %s" % (self.num_envs, tuple(reward.shape)))
+        if tuple(done.shape) != tuple(reward.shape):
+            raise ValueError("done must have the shape of reward %s, not %s" % (tuple(reward.shape), tuple(done.shape)))
+        if not reward.dtype.is_floating_point:
+            raise ValueError("reward must be a floating-point tensor, not %s" % reward.dtype)
+        if done.dtype not in (t.bool, t.uint8):
+            raise ValueError("done must be a bool or uint8 tensor, not %s" % done.dtype)
+        if reward.device != done.device:
+            raise ValueError("reward is on %s, done on %s" % (reward.device, done.device))
+        T, B = reward.shape
+        if max_episodes is not None and int(max_episodes) < 0:
+            raise ValueError("max_episodes must be >= 0")
+        if reward.device.type != "cuda" or self.device.type != "cuda":
+            for k in range(T):
+                self.update(reward[k], done[k])
             return
-        lens = self._buf_len[:k].cpu().numpy()
-        rets = self._buf_ret[:k].cpu().numpy()
-        steps, envs = np.nonzero(lens)
-        self.episode_rewards.extend(float(x) for x in rets[steps, envs])
-        self.episode_lengths.extend(int(x) for x in lens[steps, envs])
+        if reward.device != self.device and self.device.index is not None:
+            raise ValueError("reward is on %s, the statistics on %s" % (reward.device, self.device))
+        from . import _lib
+
+        L = _lib.load()
+        if len(self._queue) >= self.MAX_QUEUED:
+            self.flush()
+        self._queue_steps()
+        dev = reward.device
+        r = reward.to(t.float32).contiguous()
+        d = (done.view(t.uint8) if done.dtype == t.bool else done).contiguous()
+        cap = T * B if max_episodes is None else min(int(max_episodes), T * B)
+        ws_bytes = int(L.wab_episode_stats_workspace(T, B))
+        if ws_bytes < 0:
+            _lib.check(ws_bytes, "wab_episode_stats_workspace")
+        ws = t.empty(ws_bytes // 8 + 1, dtype=t.int64, device=dev)
+        ep_ret = t.empty(cap, dtype=t.float64, device=dev)
+        ep_i32 = t.empty((3, cap), dtype=t.int32, device=dev)  # length, env, step
+        count = t.empty(2, dtype=t.int64, device=dev)
+        ptr = (lambda x: x.data_ptr()) if cap > 0 else (lambda x: None)
+        stream = ctypes.c_void_p(t.cuda.current_stream(dev).cuda_stream)
+        _lib.check(L.wab_episode_stats_update(self._rollout_handle(), r.data_ptr(), d.data_ptr(), T, B,
+                                              self.ret.data_ptr(), self.length.data_ptr(), ptr(ep_ret),
+                                              ptr(ep_i32[0]), ptr(ep_i32[1]), ptr(ep_i32[2]), cap, count.data_ptr(),
+                                              ws.data_ptr(), stream), "wab_episode_stats_update")
+        self._queue.append(("rollout", ep_ret, ep_i32, count, cap, time.time()))
+        self.total_steps += T * B
+
+    def _record(self, rets, lens, envs, times):
+        self.episode_rewards.extend(float(x) for x in rets)
+        self.episode_lengths.extend(int(x) for x in lens)
         self.episode_envs.extend(int(x) for x in envs)
-        self.timestamps.extend(self._times[s] for s in steps)
-        self.episode_types.extend("t" for _ in steps)
-        self._times = []
+        self.timestamps.extend(times)
+        self.episode_types.extend("t" for _ in envs)
+
+    def _record_steps(self, buf_ret, buf_len, times):
+        lens = buf_len.cpu().numpy()
+        rets = buf_ret.cpu().numpy()
+        steps, envs = np.nonzero(lens)
+        self._record(rets[steps, envs], lens[steps, envs], envs, [times[s] for s in steps])
+
+    def flush(self):
+        """Gather the episodes finished since the last flush, in finishing order (synchronises)."""
+        while self._queue:
+            item = self._queue.pop(0)
+            if item[0] == "steps":
+                self._record_steps(*item[1:])
+                continue
+            _, ep_ret, ep_i32, count, cap, stamp = item
+            finished, written = (int(x) for x in count.cpu())
+            i32 = ep_i32[:, :written].cpu().numpy()
+            self._record(ep_ret[:written].cpu().numpy(), i32[0], i32[1], [stamp] * written)
+            if finished > cap:
+                raise RuntimeError("update_rollout: %d episodes finished in one call, max_episodes holds %d; "
+                                   "the first %d were recorded, the rest are lost" % (finished, cap, cap))
+        k = len(self._times)
+        if k:
+            self._record_steps(self._buf_ret[:k], self._buf_len[:k], self._times)
+            self._times = []
 
 
 def capped_cubic_video_schedule(episode_id):
@@ -178,7 +299,10 @@ class GifRecorder:
 class EpisodeMonitor:
     """`gym.wrappers.Monitor(env, directory, video_callable, force)` for a batched env: episode
     statistics of every env, video of env `video_env`'s scheduled episodes (module
-    docstring).  video_callable=False records none.  Attributes of the wrapped env pass
+    docstring).  video_callable=False records none.  rollout(), rollout_features() and
+    rollout_policy() call the wrapped object's method and account its [T, B] reward and done in
+    one device call (EpisodeStats.update_rollout); they record no video and raise
+    NotImplementedError while video is enabled.  Other attributes of the wrapped env pass
     through, except snapshot() and restore(): the running episode sums and the video recorder
     are not part of an EnvSnapshot, so after a restore the statistics would describe episodes
     that were never played; both raise NotImplementedError here."""
@@ -186,7 +310,8 @@ class EpisodeMonitor:
     def __init__(self, env, directory=None, force=False, flush_every=32, monitor_id=0, video_callable=None,
                  video_env=0, video_scale=32):
         self.env = env
-        self.stats = EpisodeStats(env.game_options, env.num_envs, env.device, flush_every)
+        self.stats = EpisodeStats(env.game_options, env.num_envs, env.device, flush_every,
+                                  handle=getattr(env, "_h", None))
         self.directory = directory
         self.initial_reset_timestamp = None
         self._infix = "%d.%d" % (monitor_id, os.getpid())
@@ -234,6 +359,40 @@ class EpisodeMonitor:
             self._video_step(done)
         self.stats.update(reward, done)
         return obs, reward, done, info
+
+    # ------------------------------------------------------------------ multi-step launches
+    def _account_rollout(self, name, result):
+        """Feed a rollout's reward and done [T, B] to the statistics; the forms are the env's
+        (planes, scalars, reward, done), the wrapper's (features, reward, done, returns) and the
+        dicts of rollout_features / rollout_policy."""
+        if isinstance(result, dict):
+            reward, done = result["reward"], result["done"]
+        elif isinstance(result, tuple) and len(result) == 4:
+            wrapper_form = result[1].dtype.is_floating_point
+            reward, done = (result[1], result[2]) if wrapper_form else (result[2], result[3])
+        else:
+            raise TypeError("%s() of %s returned neither a 4-tuple nor a dict" % (name, type(self.env).__name__))
+        self.stats.update_rollout(reward, done)
+        return result
+
+    def _rollout_call(self, name, args, kwargs):
+        if self._video_on:
+            raise NotImplementedError("EpisodeMonitor.%s() records no video: pass video_callable=False (or no "
+                                      "directory), or step() the episodes to be filmed" % name)
+        return self._account_rollout(name, getattr(self.env, name)(*args, **kwargs))
+
+    def rollout(self, *args, **kwargs):
+        """The wrapped env's or wrapper's rollout(), its episodes accounted; the result unchanged."""
+        return self._rollout_call("rollout", args, kwargs)
+
+    def rollout_features(self, *args, **kwargs):
+        """The wrapped env's rollout_features(), its episodes accounted; the result unchanged."""
+        return self._rollout_call("rollout_features", args, kwargs)
+
+    def rollout_policy(self, *args, **kwargs):
+        """The wrapped PragmaticObsWrapper's rollout_policy(), its episodes accounted; the result
+        unchanged."""
+        return self._rollout_call("rollout_policy", args, kwargs)
 
     # ------------------------------------------------------------------ video
     def _host(self, x):

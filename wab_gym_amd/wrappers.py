@@ -81,7 +81,7 @@ class PragmaticObsWrapper:
         return r["features"], r["reward"], r["done"].view(self.env._torch.bool), r["returns"]
 
     def rollout_policy(self, policy, T, gamma=0.99, store_planes=False, store_features=True, return_probs=False,
-                       fused=None):
+                       fused=None, normalize=False):
         """T closed-loop steps of actor_critic.main's loop (actor_critic.py:185-200) on the env's
         stream: step t's action is sampled by `policy` (a DevicePolicy) from step t's features, then
         the env steps.  No host synchronisation, so the whole call can be captured in a graph.  It
@@ -89,8 +89,9 @@ class PragmaticObsWrapper:
         when they are valid, else the wrapper's own `features` as its last reset()/step()/rollout
         left them).  Returns a dict: features [T,B,F] f32 (features[t] is what actions[t] was chosen
         from; None with store_features=False), actions [T,B] int8, reward [T,B] f32, done [T,B] u8,
-        value [T,B] f32, returns [T,B] f32 (discounted_returns(env=...), R after the last step = 0)
-        and, with return_probs, probs [T,B,A] f32.  Afterwards the wrapper's `features` and the
+        value [T,B] f32, returns [T,B] f32 (discounted_returns(env=...), R after the last step = 0),
+        with return_probs, probs [T,B,A] f32, and with normalize=True, normalized [T,B] f32
+        (normalized_returns of the call's returns and done, actor_critic.py:145-146).  Afterwards the wrapper's `features` and the
         env's scalars, reward and done show the last step.
 
         fused=None runs the call as one launch (wab_rollout_policy: the policy between the steps of
@@ -107,8 +108,9 @@ class PragmaticObsWrapper:
         env = self.env
         if type(self) is not PragmaticObsWrapper or type(env) is not BatchedWolvesAndBushesEnv:
             raise NotImplementedError("rollout_policy() runs PragmaticObsWrapper over a plain "
-                                      "BatchedWolvesAndBushesEnv (the egocentric observation and "
-                                      "EpisodeMonitor's statistics are made per step())")
+                                      "BatchedWolvesAndBushesEnv (the egocentric observation is made per "
+                                      "step(); for episode statistics put EpisodeMonitor around the "
+                                      "wrapper, not under it)")
         if env._term is not None:
             raise NotImplementedError("rollout_policy() returns no terminal observations "
                                       "(return_terminal=True)")
@@ -143,6 +145,8 @@ class PragmaticObsWrapper:
         probs = None
         if return_probs:
             probs = out["probs"] = t.empty((T, B, policy.n_actions), dtype=t.float32, device=dev)
+        if normalize:
+            out["normalized"] = t.empty((T, B), dtype=t.float32, device=dev)
         if T == 0:
             return out
         if env._planes_valid:
@@ -166,6 +170,8 @@ class PragmaticObsWrapper:
             env._planes_valid = False
             if not in_launch:
                 discounted_returns(rew, done, gamma=gamma, out=out["returns"], env=env)
+            if normalize:
+                normalized_returns(out["returns"], done, out=out["normalized"])
             return out
         st = o if store_planes else _lib.WabObs(None, o.food_turns, o.role, o.status)
         direct = (B * F) % 4 == 0  # every step's feature slice is 16-byte aligned
@@ -190,6 +196,8 @@ class PragmaticObsWrapper:
         env.done.copy_(done[T - 1])
         env._planes_valid = bool(store_planes)
         discounted_returns(rew, done, gamma=gamma, out=out["returns"], env=env)
+        if normalize:
+            normalized_returns(out["returns"], done, out=out["normalized"])
         return out
 
     def step(self, actions):
@@ -298,3 +306,36 @@ def normalize_episode_returns(returns, done, eps=1.1920928955078125e-07):
     var = n.clone().scatter_add_(0, key, dev * dev) / (cnt - 1)
     std = torch.sqrt(var)[key]
     return ((x - mean[key]) / (std + eps)).to(returns.dtype).reshape(T, B)
+
+
+def normalized_returns(returns, done, eps=1.1920928955078125e-07, out=None):
+    """normalize_episode_returns as one HIP kernel (wab_normalize_episode_returns): (R - mean) /
+    (std + eps) per episode segment of every env's column of the [T, B] returns, a segment still
+    open at the last step normalised as it stands, a one-step segment NaN (torch.std of one
+    element).  Per segment the sum, the squared deviations and the division run in float64 in
+    step order, so the result does not vary from run to run; float32 out (`out`, which may be
+    `returns` itself, or a new tensor).  CPU tensors take normalize_episode_returns."""
+    import torch
+
+    if returns.dim() != 2 or tuple(done.shape) != tuple(returns.shape):
+        raise ValueError("returns and done must have one shape [T, B]")
+    if returns.device != done.device:
+        raise ValueError("returns is on %s, done on %s" % (returns.device, done.device))
+    T, B = returns.shape
+    if out is not None and (tuple(out.shape) != (T, B) or out.dtype != torch.float32 or not out.is_contiguous()
+                            or out.device != returns.device):
+        raise ValueError("out must be a contiguous float32 tensor of shape [T, B] on the device of returns")
+    if returns.device.type != "cuda":
+        res = normalize_episode_returns(returns, done, eps=eps)
+        if out is None:
+            return res
+        out.copy_(res)
+        return out
+    x = returns.to(torch.float32).contiguous()
+    d = (done.view(torch.uint8) if done.dtype == torch.bool else done.to(torch.uint8)).contiguous()
+    o = torch.empty_like(x) if out is None else out
+    with torch.cuda.device(x.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(_lib.load().wab_normalize_episode_returns(x.data_ptr(), d.data_ptr(), T, B, float(eps),
+                                                             o.data_ptr(), stream), "wab_normalize_episode_returns")
+    return o
