@@ -38,6 +38,11 @@
  *                            and lengths, over a [T][B] segment          210-224
  *   wab_normalize_episode_returns <- finish_episode's (R - mean) /       actor_critic.py:145-146
  *                            (std + eps), per episode
+ *   wab_gae               <- (no counterpart: the reference plays whole episodes and uses
+ *                            R - value, actor_critic.py:149; a fixed [T][B] segment needs the
+ *                            bootstrapped, lambda-weighted form)
+ *   wab_whiten            <- finish_episode's (x - mean) / (std + eps)  actor_critic.py:145-146
+ *                            over a whole tensor instead of one episode
  *   wab_snapshot_save / wab_snapshot_restore <- (no counterpart: the reference has no
  *                            checkpoint, resume or rewind of an env)
  *   wab_policy_act        <- Policy.forward + select_action's sample  actor_critic.py:76-125
@@ -54,7 +59,7 @@
 extern "C" {
 #endif
 
-#define WAB_ABI_VERSION 10
+#define WAB_ABI_VERSION 11
 #define WAB_MAX_WOLF_SLOTS 32 /* largest per-env live-wolf slot count (wab_config.wolf_slots) */
 #define WAB_MAX_VIEW 63       /* largest odd width/height accepted */
 
@@ -362,6 +367,50 @@ int wab_episode_stats_update(const wab_handle* h, const float* reward, const uin
 int wab_normalize_episode_returns(const float* returns, const uint8_t* done, int32_t T, int64_t B, double eps,
                                   float* out, void* stream);
 
+/* ---- advantages of a rollout segment ------------------------------------------------ */
+
+/* Generalised advantage estimation over the reward f32 / done u8 / value f32 [T][B] of a rollout
+ * segment, and the value targets advantage + value.  last_value [B] f32 is the critic's value of
+ * the state after step T - 1 (NULL = 0).  Numeric contract (normative).  Per env b, in float64,
+ * in this order, with no contraction:
+ *
+ *   gl = gamma * lambda                       (one double multiply, on the host)
+ *   A = 0.0;  vnext = last_value ? (double)last_value[b] : 0.0
+ *   for t = T-1 .. 0:
+ *       v = (double)value[t][b]
+ *       r = the step's exact double reward (the handle's table, as wab_discounted_returns_exact
+ *           maps it; h == NULL: (double)reward)
+ *       d = done[t][b] != 0                   (any nonzero byte)
+ *       delta = (r + (d ? 0.0 : gamma * vnext)) - v
+ *       A     = delta + (d ? 0.0 : gl * A)
+ *       advantage[t][b] = (float)A;  target[t][b] = (float)(A + v)
+ *       vnext = v
+ *
+ * The two selects are part of the contract, including what + 0.0 does to a -0.0.  NaN and
+ * infinities propagate as the arithmetic says, up to the next done.  advantage, target [T][B] f32:
+ * either may be NULL, not both.  Neither may overlap an input or the other (the scan reads
+ * value[t] again as step t - 1's vnext): the host checks the byte ranges, WAB_E_INVALID.
+ * WAB_E_INVALID too for T < 0, B < 0, a NULL required pointer, or a handle two of whose rewards
+ * round to the same float32 (as wab_discounted_returns_exact), all before anything is launched.
+ * T = 0 or B = 0 launches nothing.  All pointers device.  One launch, no allocation, no host
+ * synchronisation, safe to capture in a hipGraph. */
+int wab_gae(const wab_handle* h, const float* reward, const uint8_t* done, const float* value,
+            const float* last_value, int32_t T, int64_t B, double gamma, double lambda, float* advantage,
+            float* target, void* stream);
+
+/* (x - mean) / (std + eps) over all n elements of x, the usual advantage normalisation over a
+ * whole batch (the whole-tensor sibling of wab_normalize_episode_returns): mean = sum(x) / n,
+ * var = sum((x - mean)^2) / (n - 1) (unbiased, as torch.std), out = float32((x - mean) /
+ * (sqrt(var) + eps)), all in float64.  n = 1 gives NaN, n = 0 launches nothing.  The sums run in
+ * an order that depends on n alone (per-workgroup partial sums in the workspace, then a combining
+ * pass; no atomics): two runs on one input give the same bits.  out f32 [n] may be x itself,
+ * else must not overlap it.  workspace: wab_whiten_workspace(n) bytes of device memory, 8-byte
+ * aligned, its contents meaningless before and after; the size is WAB_E_INVALID for n < 0 or
+ * n > 2^40, which wab_whiten refuses too.  Three stream-ordered launches, no allocation, no host
+ * synchronisation, safe to capture in a hipGraph. */
+int64_t wab_whiten_workspace(int64_t n);
+int wab_whiten(const float* x, int64_t n, double eps, float* out, void* workspace, void* stream);
+
 /* ---- snapshots: save and restore env state ---------------------------------------- */
 
 /* A snapshot is one fixed-size record per env, env-major: env k of a snapshot is bytes
@@ -522,6 +571,15 @@ int wab_debug_bush_values(wab_handle* h, const uint64_t* U, int32_t* out, int64_
  * the handle. */
 int wab_debug_returns_plan(const wab_handle* h, const float* reward, const uint8_t* done, const float* returns,
                            int64_t B, int32_t out[2]);
+
+/* Test hook: which instance of the GAE scan wab_gae launches for these pointers (advantage or
+ * target may be NULL as in the call) and this B: out = {VEC, NE}.  VEC, the envs per thread, is 2
+ * when B % 2 == 0, B / 2 >= 65536, reward, value and the outputs are 8-byte aligned and done is
+ * 2-byte aligned, else 1.  NE as in wab_debug_returns_plan.  The launch takes its instance from
+ * the same host function.  Host only: launches nothing, reads no device memory.  WAB_E_INVALID
+ * where wab_gae refuses the handle. */
+int wab_debug_gae_plan(const wab_handle* h, const float* reward, const uint8_t* done, const float* value,
+                       const float* advantage, const float* target, int64_t B, int32_t out[2]);
 
 /* Test hook: how wab_policy_act runs this policy: out = {input chunks of layer 1, columns per
  * chunk, columns of the last chunk, LDS bytes per workgroup, 1 for the instance with two

@@ -20,6 +20,7 @@
 #include "wab_feat.h"
 #include "wab_policy.h"
 #include "wab_episodes.h"
+#include "wab_advantage.h"
 
 namespace wab {
 template <int MODE, int SLOTS, bool SMALL>
@@ -46,6 +47,15 @@ __global__ void wab_episode_walk_kernel(EpisodeParams p);
 __global__ void wab_normalize_kernel(const float* x, const uint8_t* done, int32_t T, int64_t B, double eps, float* out);
 __global__ void wab_normalize_lds_kernel(const float* x, const uint8_t* done, int32_t T, int64_t B, double eps,
                                          float* out);
+template <int VEC, int NE>
+__global__ void wab_gae_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                               const float* __restrict__ value, const float* __restrict__ last_value, int32_t T,
+                               int64_t B, double gamma, double gl, float* __restrict__ advantage,
+                               float* __restrict__ target, RewardTable tab);
+__global__ void wab_whiten_sum_kernel(const float* x, int64_t n, double* psum);
+__global__ void wab_whiten_dev_kernel(const float* x, int64_t n, const double* psum, double* pss);
+__global__ void wab_whiten_out_kernel(const float* x, int64_t n, double eps, const double* psum, const double* pss,
+                                      float* out);
 __global__ void wab_snapshot_pack(SnapParams p);
 __global__ void wab_snapshot_unpack(SnapParams p);
 __global__ void wab_policy_pack(PolicyPackParams p);
@@ -588,6 +598,54 @@ int launch_returns(const float* reward, const uint8_t* done, int32_t T, int64_t 
 #undef WAB_RET
   HIP_TRY(hipGetLastError());
   return WAB_OK;
+}
+
+// the GAE scan (wab_gae_kernel<vec, ne>, wab_advantage.hip): 2 envs per thread where B is even,
+// B / 2 still gives each of the 1024 SIMDs a 64-thread wave, every float row is 8-byte aligned
+// and done 2-byte aligned, else 1 (there is no VEC 4: a chunk's registers would not fit); the
+// table as in returns_plan.  launch_gae runs what this returns, wab_debug_gae_plan reports it.
+ReturnsPlan gae_plan(const float* reward, const uint8_t* done, const float* value, const float* advantage,
+                     const float* target, int64_t B, const wab::RewardTable& tab) {
+  ReturnsPlan plan;
+  plan.inexact = inexact_rewards(tab, &plan.ne);
+  const uintptr_t rows = (uintptr_t)reward | (uintptr_t)value | (uintptr_t)advantage | (uintptr_t)target;  // (NULL: 0)
+  plan.vec = B % 2 == 0 && B / 2 >= 64 * 1024 && (rows & 7u) == 0 && ((uintptr_t)done & 1u) == 0 ? 2 : 1;
+  return plan;
+}
+
+int launch_gae(const float* reward, const uint8_t* done, const float* value, const float* last_value, int32_t T,
+               int64_t B, double gamma, double lambda, float* advantage, float* target, const wab::RewardTable& tab,
+               void* stream) {
+  const ReturnsPlan plan = gae_plan(reward, done, value, advantage, target, B, tab);
+  const int vec = plan.vec, ne = plan.ne;
+  const wab::RewardTable& inexact = plan.inexact;
+  const double gl = gamma * lambda;
+  const dim3 grid((unsigned)((B / vec + 63) / 64));
+  hipStream_t s = (hipStream_t)stream;
+#define WAB_GAE(V, N)                                                                                              \
+  hipLaunchKernelGGL((wab::wab_gae_kernel<V, N>), grid, dim3(64), 0, s, reward, done, value, last_value, T, B, gamma, \
+                     gl, advantage, target, inexact)
+#define WAB_GAE_NE(V)            \
+  switch (ne) {                  \
+    case 0: WAB_GAE(V, 0); break; \
+    case 1: WAB_GAE(V, 1); break; \
+    case 2: WAB_GAE(V, 2); break; \
+    case 3: WAB_GAE(V, 3); break; \
+    case 4: WAB_GAE(V, 4); break; \
+    default: WAB_GAE(V, 8);       \
+  }
+  if (vec == 2) { WAB_GAE_NE(2) }
+  else { WAB_GAE_NE(1) }
+#undef WAB_GAE_NE
+#undef WAB_GAE
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+// [a, a + na) and [b, b + nb) share a byte (a NULL range shares none)
+bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return a && b && na && nb && pa < pb + nb && pb < pa + na;
 }
 
 // a handle-owned [B] obs planes buffer (16-byte aligned), allocated by the first call that needs it
@@ -1513,6 +1571,69 @@ int wab_normalize_episode_returns(const float* returns, const uint8_t* done, int
   return WAB_OK;
 }
 
+int wab_gae(const wab_handle* h, const float* reward, const uint8_t* done, const float* value,
+            const float* last_value, int32_t T, int64_t B, double gamma, double lambda, float* advantage,
+            float* target, void* stream) {
+  g_err.clear();
+  if (!reward || !done || !value || (!advantage && !target) || T < 0 || B < 0)
+    return fail(WAB_E_INVALID, "wab_gae: bad argument (reward, done, value and one of advantage, target are "
+                               "required; T >= 0, B >= 0)");
+  if (h && h->rewards.n < 0)
+    return fail(WAB_E_INVALID, "wab_gae: two of the options' rewards round to the same float32; the double rewards "
+                               "are not recoverable");
+  if (T == 0 || B == 0) return WAB_OK;
+  if ((B + 63) / 64 > 0x7FFFFFFF || (uint64_t)B > (~(uint64_t)0 >> 3) / (uint64_t)T)
+    return fail(WAB_E_INVALID, "wab_gae: B too large");
+  {
+    const uint64_t n = (uint64_t)T * (uint64_t)B;
+    const void* in[4] = {reward, done, value, last_value};
+    const uint64_t in_bytes[4] = {4 * n, n, 4 * n, 4 * (uint64_t)B};
+    for (const float* o : {advantage, target})
+      for (int k = 0; k < 4; ++k)
+        if (ranges_overlap(o, 4 * n, in[k], in_bytes[k]))
+          return fail(WAB_E_INVALID, "wab_gae: an output overlaps an input (the scan reads value[t] again as step "
+                                     "t - 1's next value)");
+    if (ranges_overlap(advantage, 4 * n, target, 4 * n))
+      return fail(WAB_E_INVALID, "wab_gae: advantage and target overlap");
+  }
+  wab::RewardTable none;
+  std::memset(&none, 0, sizeof(none));
+  int device = 0;
+  if (h) device = h->device;
+  else HIP_TRY(hipGetDevice(&device));
+  DeviceGuard guard(device);
+  return launch_gae(reward, done, value, last_value, T, B, gamma, lambda, advantage, target, h ? h->rewards : none,
+                    stream);
+}
+
+int64_t wab_whiten_workspace(int64_t n) {
+  g_err.clear();
+  if (n < 0 || n > wab::kWhitenMaxN) return fail(WAB_E_INVALID, "wab_whiten_workspace: 0 <= n <= 2^40");
+  return 2 * (int64_t)wab::kWhitenMaxGroups * 8;  // the partial sums of x, then of the squared deviations
+}
+
+int wab_whiten(const float* x, int64_t n, double eps, float* out, void* workspace, void* stream) {
+  g_err.clear();
+  if (n < 0 || n > wab::kWhitenMaxN) return fail(WAB_E_INVALID, "wab_whiten: 0 <= n <= 2^40");
+  if (n == 0) return WAB_OK;
+  if (!x || !out || !workspace || ((uintptr_t)workspace & 7u) != 0)
+    return fail(WAB_E_INVALID, "wab_whiten: x, out and an 8-byte aligned workspace of wab_whiten_workspace(n) bytes "
+                               "are required");
+  if (out != x && ranges_overlap(x, 4 * (uint64_t)n, out, 4 * (uint64_t)n))
+    return fail(WAB_E_INVALID, "wab_whiten: out must be x itself or not overlap it");
+  const int64_t tiles = (n + wab::kWhitenTile - 1) / wab::kWhitenTile;
+  const dim3 grid((unsigned)std::min<int64_t>(tiles, wab::kWhitenMaxGroups)), block(wab::kWhitenThreads);
+  double* psum = static_cast<double*>(workspace);
+  double* pss = psum + wab::kWhitenMaxGroups;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(wab::wab_whiten_sum_kernel, grid, block, 0, s, x, n, psum);
+  hipLaunchKernelGGL(wab::wab_whiten_dev_kernel, grid, block, 0, s, x, n, (const double*)psum, pss);
+  hipLaunchKernelGGL(wab::wab_whiten_out_kernel, grid, block, 0, s, x, n, eps, (const double*)psum, (const double*)pss,
+                     out);
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
 namespace {
 // SnapParams of envs [env0, env0 + n) of h against `records` (the record of env0), and the LDS of
 // the launch: 64 envs per pass, halved until the pass fits 40 KB, a quarter of a CU's 160 KB, so
@@ -1925,6 +2046,22 @@ int wab_debug_returns_plan(const wab_handle* h, const float* reward, const uint8
   wab::RewardTable none;
   std::memset(&none, 0, sizeof(none));
   const ReturnsPlan plan = returns_plan(reward, done, returns, B, h ? h->rewards : none);
+  out[0] = plan.vec;
+  out[1] = plan.ne;
+  return WAB_OK;
+}
+
+int wab_debug_gae_plan(const wab_handle* h, const float* reward, const uint8_t* done, const float* value,
+                       const float* advantage, const float* target, int64_t B, int32_t out[2]) {
+  g_err.clear();
+  if (!reward || !done || !value || (!advantage && !target) || B < 0 || !out)
+    return fail(WAB_E_INVALID, "wab_debug_gae_plan: bad argument");
+  if (h && h->rewards.n < 0)
+    return fail(WAB_E_INVALID, "wab_debug_gae_plan: two of the options' rewards round to the same float32; wab_gae "
+                               "refuses this handle");
+  wab::RewardTable none;
+  std::memset(&none, 0, sizeof(none));
+  const ReturnsPlan plan = gae_plan(reward, done, value, advantage, target, B, h ? h->rewards : none);
   out[0] = plan.vec;
   out[1] = plan.ne;
   return WAB_OK;

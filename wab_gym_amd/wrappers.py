@@ -81,7 +81,7 @@ class PragmaticObsWrapper:
         return r["features"], r["reward"], r["done"].view(self.env._torch.bool), r["returns"]
 
     def rollout_policy(self, policy, T, gamma=0.99, store_planes=False, store_features=True, return_probs=False,
-                       fused=None, normalize=False):
+                       fused=None, normalize=False, bootstrap_value=False, gae_lambda=None, whiten=False):
         """T closed-loop steps of actor_critic.main's loop (actor_critic.py:185-200) on the env's
         stream: step t's action is sampled by `policy` (a DevicePolicy) from step t's features, then
         the env steps.  No host synchronisation, so the whole call can be captured in a graph.  It
@@ -102,7 +102,25 @@ class PragmaticObsWrapper:
         give the same bits (with T > 128 the returns of the one-launch path are made by
         discounted_returns after it, as in the loop).  fused=False forces the loop; fused=True
         raises NotImplementedError where the one launch does not apply.  store_features=False
-        stores no intermediate feature rows (the loop then alternates between two rows)."""
+        stores no intermediate feature rows (the loop then alternates between two rows).
+
+        bootstrap_value=True adds last_value [B] f32, the policy's value of the features the call
+        leaves in the wrapper's `features` (one more wab_policy_act after the steps; its sampled
+        actions go to the policy's own scratch `actions`, and the draw is a keyed function of
+        (seed, env, episode, turn), so nothing is consumed), and returns is then
+        discounted_returns(reward, done, bootstrap=last_value, env=env): an episode still open at
+        step T - 1 continues with the critic's estimate instead of 0.  The scan then runs after
+        the launch, as it does for T > 128; normalize=True normalises those returns.
+        gae_lambda=l (needs bootstrap_value=True) adds advantage and target [T,B] f32 from
+        gae(reward, done, value, last_value, gamma, l, env=env); whiten=True (needs gae_lambda)
+        whitens advantage in place (whitened).  With T = 0 last_value is the value of the current
+        features and the [0, B] outputs are empty.  The one launch and the loop feed the same
+        kernels the same inputs: the new outputs have the same bits on both paths."""
+        if gae_lambda is not None and not bootstrap_value:
+            raise ValueError("gae_lambda needs bootstrap_value=True (the advantages of an open episode need "
+                             "the value of the state after the last step)")
+        if whiten and gae_lambda is None:
+            raise ValueError("whiten=True whitens the advantages: pass gae_lambda")
         from .env import BatchedWolvesAndBushesEnv
 
         env = self.env
@@ -147,8 +165,37 @@ class PragmaticObsWrapper:
             probs = out["probs"] = t.empty((T, B, policy.n_actions), dtype=t.float32, device=dev)
         if normalize:
             out["normalized"] = t.empty((T, B), dtype=t.float32, device=dev)
-        if T == 0:
+        if bootstrap_value:
+            out["last_value"] = t.empty((B,), dtype=t.float32, device=dev)
+        if gae_lambda is not None:
+            out["advantage"] = t.empty((T, B), dtype=t.float32, device=dev)
+            out["target"] = t.empty((T, B), dtype=t.float32, device=dev)
+
+        def finish(returns_made):
+            """What follows the steps: the value of the state they left, the returns scan where
+            the launch did not make it, the normalisation and the advantages."""
+            if bootstrap_value:
+                policy.act(self.features, value=out["last_value"])
+            if T == 0:  # (empty outputs: nothing to scan)
+                return out
+            if not returns_made:
+                discounted_returns(rew, done, gamma=gamma, bootstrap=out.get("last_value"), out=out["returns"],
+                                   env=env)
+            if normalize:
+                normalized_returns(out["returns"], done, out=out["normalized"])
+            if gae_lambda is not None:
+                gae(rew, done, value, out["last_value"], gamma=gamma, lam=gae_lambda, env=env,
+                    advantage=out["advantage"], target=out["target"])
+                if whiten:
+                    whitened(out["advantage"], out=out["advantage"])
             return out
+
+        if T == 0:
+            if not bootstrap_value:
+                return out
+            if env._planes_valid:
+                self.observation()
+            return finish(False)
         if env._planes_valid:
             self.observation()
         if feats is not None:
@@ -157,7 +204,9 @@ class PragmaticObsWrapper:
         if one_launch:
             scal = t.empty((3, T, B), dtype=t.uint8, device=dev)
             st = _lib.WabObs(None, scal[0].data_ptr(), scal[1].data_ptr(), scal[2].data_ptr())
-            in_launch = T <= 128  # (the launch's returns scan; longer segments: the kernel of the loop)
+            # (the launch's returns scan; longer segments, and returns that continue with
+            # last_value, which exists only after the launch: the kernel of the loop)
+            in_launch = T <= 128 and not bootstrap_value
             first = self.features if feats is None else feats
             _lib.check(L.wab_rollout_policy(env._h, policy._p, first.data_ptr(), T, ctypes.addressof(st),
                                             actions.data_ptr(), value.data_ptr(),
@@ -168,11 +217,7 @@ class PragmaticObsWrapper:
                        "wab_rollout_policy")
             env._sync_last_step(scal[:, T - 1], rew[T - 1], done[T - 1])
             env._planes_valid = False
-            if not in_launch:
-                discounted_returns(rew, done, gamma=gamma, out=out["returns"], env=env)
-            if normalize:
-                normalized_returns(out["returns"], done, out=out["normalized"])
-            return out
+            return finish(in_launch)
         st = o if store_planes else _lib.WabObs(None, o.food_turns, o.role, o.status)
         direct = (B * F) % 4 == 0  # every step's feature slice is 16-byte aligned
         cur = self.features
@@ -195,10 +240,7 @@ class PragmaticObsWrapper:
         env.reward.copy_(rew[T - 1])
         env.done.copy_(done[T - 1])
         env._planes_valid = bool(store_planes)
-        discounted_returns(rew, done, gamma=gamma, out=out["returns"], env=env)
-        if normalize:
-            normalized_returns(out["returns"], done, out=out["normalized"])
-        return out
+        return finish(False)
 
     def step(self, actions):
         if self.env._term is None and type(self) is PragmaticObsWrapper:
@@ -338,4 +380,143 @@ def normalized_returns(returns, done, eps=1.1920928955078125e-07, out=None):
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         _lib.check(_lib.load().wab_normalize_episode_returns(x.data_ptr(), d.data_ptr(), T, B, float(eps),
                                                              o.data_ptr(), stream), "wab_normalize_episode_returns")
+    return o
+
+
+def _exact_rewards(reward, env):
+    """float64 rewards of the float32 `reward` (a CPU tensor): with `env`, each float32 that is one
+    of the options' step rewards (0 + r_x or 0 + r_eat + r_x, wab_env.py:251-340) becomes that
+    double, as wab_discounted_returns_exact maps it; other floats, and all of them without `env`
+    or when two of the rewards round to one float32 (with a warning), convert as they are."""
+    import numpy as np
+    import torch
+
+    r64 = reward.to(torch.float64)
+    if env is None:
+        return r64
+    o = env.game_options
+    rx = [o[k] for k in ("reward_per_turn", "reward_for_finishing", "reward_for_starving", "reward_for_being_killed")]
+    table = {}
+    for v in [0 + r for r in rx] + [0 + o["reward_for_eating"] + r for r in rx]:
+        v = float(v)
+        if table.setdefault(int(np.float32(v).view(np.int32)), v) != v:
+            warnings.warn("gae(env=...): two of the options' rewards round to the same float32; using the "
+                          "float32 rewards")
+            return r64
+    bits = reward.contiguous().view(torch.int32)
+    for b, v in table.items():
+        r64 = torch.where(bits == b, torch.full((), v, dtype=torch.float64), r64)
+    return r64
+
+
+def gae(reward, done, value, last_value=None, gamma=0.99, lam=0.95, env=None, advantage=None, target=None):
+    """Generalised advantage estimation over the [T, B] reward, done and value of a rollout
+    segment: (advantage, target), both float32 [T, B].  Per env, in float64, from t = T - 1 down:
+    delta = (r + (done ? 0 : gamma * v_next)) - v, A = delta + (done ? 0 : gamma * lam * A),
+    advantage = float32(A), target = float32(A + v), v_next starting at last_value [B] (None = 0),
+    the critic's value of the state after the last step (wab_gae, include/wab.h: the contract in
+    full).  One HIP kernel for device tensors.  With `env` (the env whose steps returned `reward`)
+    each float32 reward is first mapped back to the exact double the reference's step() returns, as
+    discounted_returns(env=...) does, with the same fallback and warning where the options make
+    that ambiguous.  `advantage` and `target` may be given (contiguous float32 [T, B], not
+    overlapping an input).  CPU tensors take the same arithmetic in torch."""
+    import torch
+
+    if reward.dim() != 2 or tuple(done.shape) != tuple(reward.shape) or tuple(value.shape) != tuple(reward.shape):
+        raise ValueError("reward, done and value must have one shape [T, B]")
+    T, B = reward.shape
+    dev = reward.device
+    if last_value is not None and tuple(last_value.shape) != (B,):
+        raise ValueError("last_value must have the shape [B]")
+    for name, x in (("done", done), ("value", value), ("last_value", last_value), ("advantage", advantage),
+                    ("target", target)):
+        if x is not None and x.device != dev:
+            raise ValueError("%s is on %s, reward on %s" % (name, x.device, dev))
+    for name, x in (("advantage", advantage), ("target", target)):
+        if x is not None and (tuple(x.shape) != (T, B) or x.dtype != torch.float32 or not x.is_contiguous()):
+            raise ValueError("%s must be a contiguous float32 tensor of shape [T, B]" % name)
+    r = reward.to(torch.float32).contiguous()
+    d = (done.view(torch.uint8) if done.dtype == torch.bool else done.to(torch.uint8)).contiguous()
+    v = value.to(torch.float32).contiguous()
+    lv = None if last_value is None else last_value.to(torch.float32).contiguous()
+    adv = torch.empty_like(r) if advantage is None else advantage
+    tgt = torch.empty_like(r) if target is None else target
+    if dev.type != "cuda":
+        r64, v64 = _exact_rewards(r, env), v.to(torch.float64)
+        zero = torch.zeros((), dtype=torch.float64)
+        gl = float(gamma) * float(lam)
+        A = torch.zeros(B, dtype=torch.float64)
+        vnext = A.clone() if lv is None else lv.to(torch.float64)
+        for k in range(T - 1, -1, -1):
+            dk = d[k] != 0
+            delta = (r64[k] + torch.where(dk, zero, float(gamma) * vnext)) - v64[k]
+            A = delta + torch.where(dk, zero, gl * A)
+            adv[k] = A.to(torch.float32)
+            tgt[k] = (A + v64[k]).to(torch.float32)
+            vnext = v64[k]
+        return adv, tgt
+    if env is not None and dev != env.device:
+        raise ValueError("reward is on %s, the env on %s" % (dev, env.device))
+    if T == 0 or B == 0:
+        return adv, tgt
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        args = (r.data_ptr(), d.data_ptr(), v.data_ptr(), None if lv is None else lv.data_ptr(), T, B, float(gamma),
+                float(lam), adv.data_ptr(), tgt.data_ptr(), stream)
+        if env is not None:
+            try:
+                _lib.check(L.wab_gae(env._h, *args), "wab_gae")
+                return adv, tgt
+            except ValueError as e:
+                if "round to the same" not in str(e):
+                    raise
+                # two of the options' rewards are one float32: the doubles are not recoverable
+                warnings.warn("gae(env=...): %s; using the float32 rewards" % e)
+        _lib.check(L.wab_gae(None, *args), "wab_gae")
+    return adv, tgt
+
+
+_whiten_workspaces = {}
+
+
+def whitened(x, eps=1.1920928955078125e-07, out=None):
+    """(x - mean) / (std + eps) over all elements of a contiguous float32 tensor, the usual
+    normalisation of a batch of advantages (wab_whiten): std unbiased as torch.std, everything in
+    float64, float32 out (`out`, which may be `x` itself, or a new tensor); one element gives NaN.
+    The sums run in a fixed order, so two runs on one input give the same bits, and the call can
+    be captured in a graph (its workspace is kept per device; a call made during a capture takes
+    one from torch's allocator, which the capture owns).  CPU tensors take torch in float64."""
+    import torch
+
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous float32 tensor")
+    if out is not None and (tuple(out.shape) != tuple(x.shape) or out.dtype != torch.float32
+                            or not out.is_contiguous() or out.device != x.device):
+        raise ValueError("out must be a contiguous float32 tensor of the shape and on the device of x")
+    o = torch.empty_like(x) if out is None else out
+    n = x.numel()
+    if x.device.type != "cuda":
+        if n > 0:
+            xd = x.to(torch.float64)
+            dev = xd - xd.mean()
+            var = (dev * dev).sum() / (n - 1) if n > 1 else torch.full((), float("nan"), dtype=torch.float64)
+            o.copy_((dev / (torch.sqrt(var) + eps)).to(torch.float32))
+        return o
+    if n == 0:
+        return o
+    L = _lib.load()
+    size = int(L.wab_whiten_workspace(n))
+    if size < 0:
+        _lib.check(-1, "wab_whiten_workspace")
+    with torch.cuda.device(x.device):
+        if torch.cuda.is_current_stream_capturing():
+            ws = torch.empty(size // 8, dtype=torch.float64, device=x.device)
+        else:
+            key = (x.device.index, size)
+            ws = _whiten_workspaces.get(key)
+            if ws is None:
+                ws = _whiten_workspaces[key] = torch.empty(size // 8, dtype=torch.float64, device=x.device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(L.wab_whiten(x.data_ptr(), n, float(eps), o.data_ptr(), ws.data_ptr(), stream), "wab_whiten")
     return o
