@@ -59,7 +59,7 @@
 extern "C" {
 #endif
 
-#define WAB_ABI_VERSION 11
+#define WAB_ABI_VERSION 12
 #define WAB_MAX_WOLF_SLOTS 32 /* largest per-env live-wolf slot count (wab_config.wolf_slots) */
 #define WAB_MAX_VIEW 63       /* largest odd width/height accepted */
 
@@ -510,6 +510,60 @@ int wab_policy_act(wab_handle* h, wab_policy* p, const float* features, int8_t* 
 /* Free the policy (synchronises its device). */
 int wab_policy_destroy(wab_policy* p);
 
+/* ---- device policy: the loss and its parameter gradients (actor_critic.py:148-165) ------ */
+
+/* finish_episode()'s loss and loss.backward() over N stored rows, for the network wab_policy_load
+ * last packed.  Per row i, with p = softmax(logits), H = -sum_k p_k log p_k:
+ *   loss_policy  = -sum_i weight_i log p_i[a_i]     (weight: R - value.item(), or an advantage; a constant)
+ *   loss_value   =  sum_i l(v_i - target_i)         (l: smooth_l1 with beta 1, or 0.5 d^2)
+ *   loss_entropy =  sum_i H_i
+ *   total        =  scale (loss_policy + value_coef loss_value - entropy_coef loss_entropy)
+ * and the gradients of `total` with respect to the ten parameter tensors.
+ * Numeric contract: the forward is wab_policy_act's (value has its bits).  The head is fp32.  The
+ * backward pass is straight-through: every bf16 rounding of a weight, a feature or an activation
+ * has derivative 1, so the gradient of the fp32 parameter is that of its rounded value.  Every
+ * matrix product is bf16 x bf16 with fp32 accumulation: the gradient G_l of each layer's
+ * pre-activation is rounded to bf16 before dW_l = G_l^T x_{l-1}, db_l = sum of the same rounded
+ * rows, and dx_{l-1} = G_l bf16(W_l); leaky_relu passes 1 or float32(0.01) (z >= 0), the clamp 1
+ * where -4 <= leaky_relu(z_3) <= 4 and 0 elsewhere.  Sums over rows have one fixed order that
+ * does not depend on chunk_rows; no float atomics; results are bitwise reproducible. */
+#define WAB_VALUE_LOSS_SMOOTH_L1 0
+#define WAB_VALUE_LOSS_MSE 1
+typedef struct wab_policy_loss {
+  float value_coef;     /* 1 in the reference */
+  float entropy_coef;   /* 0 in the reference */
+  int32_t value_loss;   /* WAB_VALUE_LOSS_* */
+  float scale;          /* multiplies `total` and every gradient, once, at the end (1 / N: a mean) */
+  int32_t accumulate;   /* nonzero: add to grads_out and loss_out instead of overwriting them */
+  int32_t chunk_rows;   /* rows per pass through the workspace: 0 = 32768, else a multiple of 128 */
+} wab_policy_loss;
+
+/* Bytes of workspace wab_policy_grad needs with this chunk_rows (it depends on the policy's shape
+ * and chunk_rows, not on N); 0 with wab_last_error set for NULL, N outside [0, 2^31) or a
+ * chunk_rows that is negative or no multiple of 128. */
+size_t wab_policy_grad_workspace(const wab_policy* p, int64_t N, int32_t chunk_rows);
+
+/* features [N][in_features] float32, actions [N] int8, weight [N] and target [N] float32;
+ * grads_out: ten device arrays in wab_policy_weights' layout, written (or added to);
+ * loss_out: device float[4] = {loss_policy, loss_value, loss_entropy, total} (the three parts
+ * unscaled) or NULL; logp [N] (log p_i[a_i]), value [N], entropy [N] float32 or NULL.
+ * workspace: device memory, 256-byte aligned, contents meaningless before and after.
+ * Stream-ordered launches only (per chunk two, plus two): no allocation, no synchronisation,
+ * safe to capture in a hipGraph.  N = 0 gives zero gradients and losses.
+ * A row whose action is outside [0, n_actions) is left out of the losses and the gradients (its
+ * logp is 0) and counted on the device; wab_policy_grad_bad_actions reports the count.
+ * WAB_E_STATE before the first wab_policy_load; WAB_E_INVALID for a NULL required argument, N
+ * outside [0, 2^31), a workspace smaller than wab_policy_grad_workspace's answer or misaligned,
+ * a chunk_rows that is negative or no multiple of 128, or an unknown value_loss. */
+int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions, const float* weight,
+                    const float* target, int64_t N, const wab_policy_loss* loss,
+                    const wab_policy_weights* grads_out, float loss_out[4], float* logp, float* value,
+                    float* entropy, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The number of rows the latest wab_policy_grad on this workspace left out for their action
+ * (synchronises `stream`).  WAB_E_INVALID, with the count in the message, when it is not 0. */
+int wab_policy_grad_bad_actions(const wab_policy* p, const void* workspace, void* stream, uint64_t* out);
+
 /* ---- closed-loop rollout: policy and env step, T steps (actor_critic.py:108-125, 185-200) -- */
 
 /* 1 when wab_rollout_policy(h, p, ...) runs as one launch, 0 when it runs as 2 T launches;
@@ -585,6 +639,11 @@ int wab_debug_gae_plan(const wab_handle* h, const float* reward, const uint8_t* 
  * chunk, columns of the last chunk, LDS bytes per workgroup, 1 for the instance with two
  * layer-1 tiles per wave (h1 > 128) or 0}.  Host only. */
 int wab_debug_policy_plan(const wab_policy* p, int32_t out[5]);
+
+/* Test hook: how wab_policy_grad runs this policy with this chunk_rows: out = {rows per row block,
+ * slabs, rows per chunk, LDS bytes per workgroup of wab_policy_bwd_kernel, of
+ * wab_policy_wgrad_kernel}.  Host only. */
+int wab_debug_policy_grad_plan(const wab_policy* p, int32_t chunk_rows, int32_t out[5]);
 
 #ifdef __cplusplus
 }

@@ -9,9 +9,12 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
+#include <climits>
 #include <cstring>
+#include <mutex>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/wab.h"
@@ -19,6 +22,7 @@
 #include "wab_device.h"
 #include "wab_feat.h"
 #include "wab_policy.h"
+#include "wab_policy_grad.h"
 #include "wab_episodes.h"
 #include "wab_advantage.h"
 
@@ -61,6 +65,11 @@ __global__ void wab_snapshot_unpack(SnapParams p);
 __global__ void wab_policy_pack(PolicyPackParams p);
 template <bool TWO>
 __global__ void wab_policy_kernel(PolicyParams p);
+__global__ void wab_policy_grad_pack(GradPackParams p);
+template <bool TWO>
+__global__ void wab_policy_bwd_kernel(GradBwdParams p);
+__global__ void wab_policy_wgrad_kernel(GradWgradParams p);
+__global__ void wab_policy_grad_reduce_kernel(GradReduceParams p);
 }
 
 using wab::Params;
@@ -1883,6 +1892,197 @@ int wab_policy_act(wab_handle* h, wab_policy* p, const float* features, int8_t* 
   else
     hipLaunchKernelGGL(wab::wab_policy_kernel<false>, grid, dim3(256), p->lds.total, (hipStream_t)stream, pp);
   HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+// ---- device policy: loss and parameter gradients (wab_policy_grad.hip) ---------------------
+
+namespace {
+
+// rows per chunk a call runs with: 0 = the default; a positive multiple of 128 otherwise
+int64_t grad_chunk_rows(int32_t chunk_rows) {
+  if (chunk_rows == 0) return wab::kGradDefaultChunk;
+  if (chunk_rows < 0 || chunk_rows % wab::kGradRows != 0) return -1;
+  return chunk_rows;
+}
+
+// wab_policy_bwd_kernel's dynamic LDS can exceed the 64 KB default: the attribute is a maximum
+// per (device, kernel), set once for each pair to the device's limit
+hipError_t grad_raise_lds(int device, bool two) {
+  static std::mutex mu;
+  static std::vector<std::pair<int, bool>> done;
+  std::lock_guard<std::mutex> lock(mu);
+  if (std::find(done.begin(), done.end(), std::make_pair(device, two)) != done.end()) return hipSuccess;
+  int lds_max = 0;
+  hipError_t e = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(two ? reinterpret_cast<void*>(&wab::wab_policy_bwd_kernel<true>)
+                                : reinterpret_cast<void*>(&wab::wab_policy_bwd_kernel<false>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+  if (e == hipSuccess) done.emplace_back(device, two);
+  return e;
+}
+
+}  // namespace
+
+size_t wab_policy_grad_workspace(const wab_policy* p, int64_t N, int32_t chunk_rows) {
+  g_err.clear();
+  const int64_t cr = grad_chunk_rows(chunk_rows);
+  if (!p || N < 0 || N > INT32_MAX || cr < 0) {
+    g_err = "wab_policy_grad_workspace: NULL policy, N outside [0, 2^31) or chunk_rows not a multiple of 128";
+    return 0;
+  }
+  // (the size does not shrink with N: a cached workspace serves every call of the policy)
+  return wab::grad_workspace(wab::grad_plan(p->dims), cr).total;
+}
+
+int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions, const float* weight,
+                    const float* target, int64_t N, const wab_policy_loss* loss, const wab_policy_weights* grads_out,
+                    float loss_out[4], float* logp, float* value, float* entropy, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  g_err.clear();
+  if (!p || !loss || !grads_out || !workspace) return fail(WAB_E_INVALID, "wab_policy_grad: NULL argument");
+  if (N < 0 || N > INT32_MAX) return fail(WAB_E_INVALID, "wab_policy_grad: N outside [0, 2^31)");
+  if (N > 0 && (!features || !actions || !weight || !target))
+    return fail(WAB_E_INVALID, "wab_policy_grad: NULL argument (features, actions, weight and target are required)");
+  const wab_policy_weights& go = *grads_out;
+  if (!go.w1 || !go.b1 || !go.w2 || !go.b2 || !go.w3 || !go.b3 || !go.wa || !go.ba || !go.wv || !go.bv)
+    return fail(WAB_E_INVALID, "wab_policy_grad: every gradient pointer must be set");
+  if (loss->value_loss != WAB_VALUE_LOSS_SMOOTH_L1 && loss->value_loss != WAB_VALUE_LOSS_MSE)
+    return fail(WAB_E_INVALID, "wab_policy_grad: value_loss must be WAB_VALUE_LOSS_SMOOTH_L1 or WAB_VALUE_LOSS_MSE");
+  const int64_t cr = grad_chunk_rows(loss->chunk_rows);
+  if (cr < 0) return fail(WAB_E_INVALID, "wab_policy_grad: chunk_rows must be 0 or a positive multiple of 128");
+  if (!p->loaded) return fail(WAB_E_STATE, "wab_policy_grad: call wab_policy_load first");
+  const wab::GradPlan g = wab::grad_plan(p->dims);
+  const wab::GradWorkspace lay = wab::grad_workspace(g, cr);
+  if (workspace_bytes < lay.total)
+    return fail(WAB_E_INVALID, "wab_policy_grad: the workspace has " + std::to_string(workspace_bytes) +
+                                   " bytes, wab_policy_grad_workspace asks for " + std::to_string(lay.total));
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
+    return fail(WAB_E_INVALID, "wab_policy_grad: the workspace must be 256-byte aligned");
+  const void* f32s[] = {features, weight, target, loss_out, logp, value, entropy, go.w1, go.b1, go.w2, go.b2,
+                        go.w3, go.b3, go.wa, go.ba, go.wv, go.bv};
+  for (const void* q : f32s)
+    if ((reinterpret_cast<uintptr_t>(q) & 3u) != 0)
+      return fail(WAB_E_INVALID, "wab_policy_grad: float arrays must be 4-byte aligned");
+  DeviceGuard guard(p->device);
+  const bool two = policy_two_tiles(p->dims);
+  HIP_TRY(grad_raise_lds(p->device, two));
+  unsigned char* const base = static_cast<unsigned char*>(workspace);
+  uint32_t* const bad = reinterpret_cast<uint32_t*>(base + lay.bad);
+  uint16_t* const wt = reinterpret_cast<uint16_t*>(base + lay.wt);
+  uint16_t* const ws = reinterpret_cast<uint16_t*>(base + lay.ws);
+  float* const slab = reinterpret_cast<float*>(base + lay.slab);
+  double* const part = reinterpret_cast<double*>(base + lay.part);
+  double* const lsum = reinterpret_cast<double*>(base + lay.loss);
+  hipStream_t st = (hipStream_t)stream;
+
+  // the transposed image, from the packed weights as they are at this point of the stream (every
+  // call: a flag on the host would go stale under graph replay)
+  wab::GradPackParams kp;
+  kp.g = g;
+  kp.w = p->w;
+  kp.wt = wt;
+  kp.bad = bad;
+  hipLaunchKernelGGL(wab::wab_policy_grad_pack, dim3(std::min<uint32_t>((g.wt_total + 255u) / 256u, 1024u)), dim3(256),
+                     0, st, kp);
+  HIP_TRY(hipGetLastError());
+
+  wab::GradBwdParams bp;
+  bp.g = g;
+  bp.N = N;
+  bp.chunk_rows = cr;
+  bp.features = features;
+  bp.actions = actions;
+  bp.weight = weight;
+  bp.target = target;
+  bp.w = p->w;
+  bp.b = p->b;
+  bp.wt = wt;
+  bp.value_coef = loss->value_coef;
+  bp.entropy_coef = loss->entropy_coef;
+  bp.mse = loss->value_loss == WAB_VALUE_LOSS_MSE ? 1 : 0;
+  bp.logp = logp;
+  bp.value = value;
+  bp.entropy = entropy;
+  bp.ws = ws;
+  bp.part = part;
+  bp.bad = bad;
+  wab::GradWgradParams wp;
+  wp.g = g;
+  wp.N = N;
+  wp.chunk_rows = cr;
+  wp.features = features;
+  wp.ws = ws;
+  wp.part = part;
+  wp.slab = slab;
+  wp.loss = lsum;
+  for (int64_t row0 = 0; row0 < N; row0 += cr) {
+    const int64_t rows = std::min<int64_t>(cr, N - row0);
+    const unsigned blocks = (unsigned)((rows + wab::kGradRows - 1) / wab::kGradRows);
+    bp.row0 = row0;
+    if (two)
+      hipLaunchKernelGGL(wab::wab_policy_bwd_kernel<true>, dim3(blocks), dim3(256), g.lds_total, st, bp);
+    else
+      hipLaunchKernelGGL(wab::wab_policy_bwd_kernel<false>, dim3(blocks), dim3(256), g.lds_total, st, bp);
+    HIP_TRY(hipGetLastError());
+    wp.row0 = row0;
+    wp.n_blocks = (int32_t)blocks;
+    wp.first = row0 == 0 ? 1 : 0;
+    hipLaunchKernelGGL(wab::wab_policy_wgrad_kernel, dim3((unsigned)g.n_tasks + 1u, (unsigned)g.slabs), dim3(64), 0,
+                       st, wp);
+    HIP_TRY(hipGetLastError());
+  }
+
+  wab::GradReduceParams rp;
+  rp.g = g;
+  rp.empty = N == 0 ? 1 : 0;
+  rp.accumulate = loss->accumulate ? 1 : 0;
+  rp.scale = loss->scale;
+  rp.value_coef = loss->value_coef;
+  rp.entropy_coef = loss->entropy_coef;
+  rp.slab = slab;
+  rp.loss = lsum;
+  rp.w1 = const_cast<float*>(go.w1); rp.b1 = const_cast<float*>(go.b1);
+  rp.w2 = const_cast<float*>(go.w2); rp.b2 = const_cast<float*>(go.b2);
+  rp.w3 = const_cast<float*>(go.w3); rp.b3 = const_cast<float*>(go.b3);
+  rp.wa = const_cast<float*>(go.wa); rp.ba = const_cast<float*>(go.ba);
+  rp.wv = const_cast<float*>(go.wv); rp.bv = const_cast<float*>(go.bv);
+  rp.loss_out = loss_out;
+  const wab::PolicyDims& d = p->dims;
+  const int64_t elems = (int64_t)d.h1 * (d.F + 1) + (int64_t)d.h2 * (d.h1 + 1) + (int64_t)d.h3 * (d.h2 + 1) +
+                        (int64_t)(d.A + 1) * (d.h3 + 1);
+  hipLaunchKernelGGL(wab::wab_policy_grad_reduce_kernel, dim3((unsigned)std::min<int64_t>((elems + 255) / 256, 4096)),
+                     dim3(256), 0, st, rp);
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+int wab_policy_grad_bad_actions(const wab_policy* p, const void* workspace, void* stream, uint64_t* out) {
+  g_err.clear();
+  if (!p || !workspace || !out) return fail(WAB_E_INVALID, "wab_policy_grad_bad_actions: NULL argument");
+  DeviceGuard guard(p->device);
+  uint32_t v = 0;
+  HIP_TRY(hipMemcpyAsync(&v, workspace, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  *out = v;
+  if (v != 0)
+    return fail(WAB_E_INVALID, "wab_policy_grad: " + std::to_string(v) + " rows had an action outside [0, " +
+                                   std::to_string(p->dims.A) + "); they were left out of the loss and the gradients");
+  return WAB_OK;
+}
+
+int wab_debug_policy_grad_plan(const wab_policy* p, int32_t chunk_rows, int32_t out[5]) {
+  g_err.clear();
+  if (!p || !out) return fail(WAB_E_INVALID, "wab_debug_policy_grad_plan: NULL argument");
+  const int64_t cr = grad_chunk_rows(chunk_rows);
+  if (cr < 0) return fail(WAB_E_INVALID, "wab_debug_policy_grad_plan: chunk_rows must be 0 or a positive multiple of 128");
+  const wab::GradPlan g = wab::grad_plan(p->dims);
+  out[0] = wab::kGradRows;
+  out[1] = g.slabs;
+  out[2] = (int32_t)cr;
+  out[3] = (int32_t)g.lds_total;
+  out[4] = 0;  // wab_policy_wgrad_kernel uses no LDS
   return WAB_OK;
 }
 

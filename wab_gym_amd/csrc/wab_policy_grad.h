@@ -1,0 +1,184 @@
+// wab_policy_grad.h — the plan, the workspace layout and the parameter blocks of the device
+// policy's loss and parameter gradients (wab_policy_grad.hip; wab_policy_grad in include/wab.h),
+// shared with the C-ABI host code.
+#pragma once
+
+#include "wab_policy.h"
+
+namespace wab {
+
+constexpr int kGradRows = kPolicyEnvs;  // rows per row block: one workgroup of wab_policy_bwd_kernel
+constexpr int kGradTiles = 4;           // 32-unit output tiles one wab_policy_wgrad_kernel wave carries
+constexpr int kGradHeadUnits = 16;      // G_4's columns: [0, 8) the action logits, [8] the value, the rest zero
+constexpr int kGradMaxSlabs = 64;
+constexpr int kGradDefaultChunk = 32768;  // rows per chunk: the bf16 workspace of the reference net is 54 MiB
+
+// The transposed packed weights the backward chain reads (the A operands of dx_l = D_{l+1} . W_{l+1}):
+// image l is pack_layer's layout of W_{l+1}^T, NT_l tiles of 32 units of layer l by KS k-steps of
+// 16 units of layer l + 1.  The head's image has one k-step: columns 0..7 the action head's rows,
+// column 8 the value head.
+//
+// The bf16 workspace of one chunk holds, for every unit u of X_1, X_2, X_3, D_1, D_2, D_3, D_4 in
+// that order (each array padded to its 32 NT units, D_4 to 16), the chunk's rows as one contiguous
+// run of chunk_rows bf16: element (u, row) at u * chunk_rows + row.  Eight consecutive rows of a unit are
+// the 16 bytes a lane of v_mfma_f32_32x32x16_bf16 holds of either operand of D^T . X.
+//
+// wab_policy_wgrad_kernel's tasks: for layer l (1, 2, 3, head) the pairs (group of up to 4 output
+// tiles of D_l, 32-column tile of [X_{l-1} | 1]); column K_in of a layer is the column of ones
+// whose product is the bias gradient.  Task t of slab s keeps its 4 accumulators, as the lanes
+// hold them, at ((s * n_tasks + t) * 4 + tile) * 1024 + reg * 64 + lane floats.
+struct GradPlan {
+  PolicyDims d;
+  // wab_policy_bwd_kernel's LDS, wab_policy_kernel's two regions: region A holds the input chunk,
+  // then X_2, then D_4 [128][24], then D_2; region B X_1, X_3, then D_3
+  int32_t KC, n_chunks, pitch_in, pitch1, pitch2, pitch3, pitch4;
+  uint32_t off_b, lds_total;
+  // transposed image (uint16 units) and its k-steps
+  uint32_t wt1, wt2, wt3, wt_total;
+  int32_t KT1, KT2, KT3;  // ceil(h2 / 16), ceil(h3 / 16), 1
+  // workspace units
+  int32_t u_x[4];   // u_x[l]: X_l, l = 1..3 (u_x[0] unused)
+  int32_t u_d[5];   // u_d[l]: D_l, l = 1..4
+  int32_t n_d[5];   // units of D_l held (32 NT_l; 16 for the head)
+  int32_t u_total;
+  // wgrad tasks: layer l = 1..4 has groups[l] * ktiles[l] tasks from task0[l]
+  int32_t k_in[5], n_out[5], groups[5], ktiles[5], task0[6];
+  int32_t n_tasks, slabs;
+};
+
+__host__ __device__ inline GradPlan grad_plan(const PolicyDims& d) {
+  GradPlan g;
+  g.d = d;
+  g.pitch1 = 32 * d.NT1 + 8;
+  g.pitch2 = 32 * d.NT2 + 8;
+  g.pitch3 = 32 * d.NT3 + 8;
+  g.pitch4 = kGradHeadUnits + 8;
+  const uint32_t rows = (uint32_t)kGradRows * 2u;
+  const uint32_t region_b = rows * (uint32_t)(g.pitch1 > g.pitch3 ? g.pitch1 : g.pitch3);
+  const uint32_t a_min = rows * (uint32_t)g.pitch2;  // (>= D_4's 6 KB: pitch2 >= 40)
+  // the input chunk as wide as two workgroups per CU allow, as policy_lds chooses it
+  uint32_t budget = region_b < 80u * 1024u ? 80u * 1024u - region_b : 0u;
+  if (budget < a_min) budget = a_min;
+  int kc_max = ((int)(budget / rows) - 8) / 16 * 16;
+  if (kc_max < 16) kc_max = 16;
+  if (kc_max > kPolicyMaxChunk) kc_max = kPolicyMaxChunk;
+  const int kpad = 16 * d.KS1;
+  g.n_chunks = (kpad + kc_max - 1) / kc_max;
+  g.KC = ((kpad + g.n_chunks - 1) / g.n_chunks + 15) / 16 * 16;
+  g.pitch_in = g.KC + 8;
+  const uint32_t chunk = rows * (uint32_t)g.pitch_in;
+  g.off_b = chunk > a_min ? chunk : a_min;
+  g.lds_total = g.off_b + region_b;
+
+  g.KT1 = (d.h2 + 15) / 16;
+  g.KT2 = (d.h3 + 15) / 16;
+  g.KT3 = 1;
+  uint32_t o = 0;
+  g.wt1 = o; o += (uint32_t)(d.NT1 * g.KT1) * 512u;
+  g.wt2 = o; o += (uint32_t)(d.NT2 * g.KT2) * 512u;
+  g.wt3 = o; o += (uint32_t)(d.NT3 * g.KT3) * 512u;
+  g.wt_total = o;
+
+  const int nt[4] = {0, d.NT1, d.NT2, d.NT3};
+  int u = 0;
+  g.u_x[0] = 0;
+  for (int l = 1; l <= 3; ++l) { g.u_x[l] = u; u += 32 * nt[l]; }
+  g.u_d[0] = 0; g.n_d[0] = 0;
+  for (int l = 1; l <= 3; ++l) { g.u_d[l] = u; g.n_d[l] = 32 * nt[l]; u += 32 * nt[l]; }
+  g.u_d[4] = u; g.n_d[4] = kGradHeadUnits; u += kGradHeadUnits;
+  g.u_total = u;
+
+  g.k_in[0] = 0; g.n_out[0] = 0; g.groups[0] = 0; g.ktiles[0] = 0;
+  g.k_in[1] = d.F;  g.n_out[1] = d.h1;
+  g.k_in[2] = d.h1; g.n_out[2] = d.h2;
+  g.k_in[3] = d.h2; g.n_out[3] = d.h3;
+  g.k_in[4] = d.h3; g.n_out[4] = kPolicyMaxActions + 1;
+  int t = 0;
+  g.task0[0] = 0;
+  for (int l = 1; l <= 4; ++l) {
+    const int tiles = l < 4 ? nt[l] : 1;
+    g.groups[l] = (tiles + kGradTiles - 1) / kGradTiles;
+    g.ktiles[l] = (g.k_in[l] + 1 + 31) / 32;
+    g.task0[l] = t;
+    t += g.groups[l] * g.ktiles[l];
+  }
+  g.task0[5] = t;
+  g.n_tasks = t;
+  // slabs: about two waves per SIMD of the chip over all tasks, a function of the shape alone
+  int s = (2048 + t - 1) / t;
+  g.slabs = s < 1 ? 1 : (s > kGradMaxSlabs ? kGradMaxSlabs : s);
+  return g;
+}
+
+// byte offsets of the workspace's parts for chunks of `chunk_rows` rows
+struct GradWorkspace {
+  size_t bad, wt, ws, slab, part, loss, total;
+};
+
+inline GradWorkspace grad_workspace(const GradPlan& g, int64_t chunk_rows) {
+  auto up = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
+  GradWorkspace w;
+  size_t o = 0;
+  w.bad = o; o = up(o + 4u);  // uint32: rows of the latest call whose action was outside [0, A)
+  w.wt = o; o = up(o + (size_t)g.wt_total * 2u);
+  w.ws = o; o = up(o + (size_t)g.u_total * (size_t)chunk_rows * 2u);
+  w.slab = o; o = up(o + (size_t)g.slabs * (size_t)g.n_tasks * (size_t)(kGradTiles * 1024) * 4u);
+  w.part = o; o = up(o + (size_t)(chunk_rows / kGradRows) * 4u * 3u * 8u);  // [block][wave][3] doubles
+  w.loss = o; o = up(o + (size_t)g.slabs * 3u * 8u);                         // [slab][3] doubles
+  w.total = o;
+  return w;
+}
+
+struct GradPackParams {
+  GradPlan g;
+  const uint16_t* w;  // the forward image (PolicyDims::w*)
+  uint16_t* wt;
+  uint32_t* bad;      // zeroed for the call
+};
+
+struct GradBwdParams {
+  GradPlan g;
+  int64_t N, row0;         // all rows; the chunk's first row (a multiple of 128)
+  int64_t chunk_rows;      // the workspace's row pitch
+  const float* features;   // [N][F]
+  const int8_t* actions;   // [N]
+  const float* weight;     // [N]
+  const float* target;     // [N]
+  const uint16_t* w;       // forward image
+  const float* b;          // padded biases
+  const uint16_t* wt;      // transposed image
+  float value_coef, entropy_coef;
+  int32_t mse;             // 0: smooth_l1 (beta 1), 1: 0.5 d^2
+  float* logp;             // [N] or null
+  float* value;            // [N] or null
+  float* entropy;          // [N] or null
+  uint16_t* ws;            // bf16 workspace of the chunk
+  double* part;            // [chunk block][wave][3]: the waves' sums of the rows' loss terms
+  uint32_t* bad;           // count of rows whose action is outside [0, A)
+};
+
+struct GradWgradParams {
+  GradPlan g;
+  int64_t N, row0;
+  int64_t chunk_rows;
+  int32_t n_blocks;        // row blocks of this chunk
+  int32_t first;           // 1: the slabs start from zero (the call's first chunk)
+  const float* features;
+  const uint16_t* ws;
+  const double* part;
+  float* slab;
+  double* loss;
+};
+
+struct GradReduceParams {
+  GradPlan g;
+  int32_t empty;           // 1: N == 0, the slabs hold nothing
+  int32_t accumulate;
+  float scale, value_coef, entropy_coef;
+  const float* slab;
+  const double* loss;
+  float *w1, *b1, *w2, *b2, *w3, *b3, *wa, *ba, *wv, *bv;  // torch Linear layout, device
+  float* loss_out;         // {policy, value, entropy, total}
+};
+
+}  // namespace wab

@@ -1,0 +1,534 @@
+// wab_policy_grad.hip — finish_episode()'s loss and loss.backward() of actor_critic.py:148-165
+// for the device policy: the loss terms and the gradients of the ten parameter tensors over N
+// stored rows (features, action, weight, value target).  gfx950.
+//
+// Numeric contract (wab_gym_amd/policy.py reference_loss_and_grad states the same in torch):
+//   * forward: wab_policy_act's, through the same pol_* functions (wab_policy_dev.h); the hidden
+//     epilogue below repeats pol_store's operations in its order, so x_l and the value have
+//     wab_policy_act's bits;
+//   * head, fp32, per row: p = the forward's probabilities, log p_k = (logit_k - max) - logf(sum),
+//     H = -sum_k p_k log p_k, g_logit_k = weight (p_k - [k = a]) + entropy_coef p_k (log p_k + H),
+//     g_v = value_coef l'(v - target), l smooth_l1 (beta 1) or 0.5 d^2;
+//   * backward, straight-through: D_l = bf16(G_l); dW_l = D_l^T x_{l-1} and db_l = D_l^T 1 by
+//     v_mfma_f32_32x32x16_bf16 with the rows as the k dimension (16 rows per instruction, row
+//     blocks of 128 in ascending order per slab); dx_{l-1} = D_l bf16(W_l) by the same instruction
+//     from a transposed image of the packed weights; G_{l-1} = dx_{l-1} * (z >= 0 ? 1 : 0.01f),
+//     and 0 where layer 3's leaky_relu left [-4, 4];
+//   * sums over rows: row block b belongs to slab b % slabs, whatever the chunking; the reducer
+//     adds the slabs in ascending order in fp32 and multiplies by `scale` once.  The loss terms
+//     are summed in double (lanes by a fixed shuffle tree, waves, blocks and slabs in order).
+// No float atomics; every sum has one order, so results are bitwise reproducible.
+//
+// wab_policy_bwd_kernel: one workgroup per 128 rows, wab_policy_kernel's plan (the rows' features
+// staged as bf16 chunks, the waves splitting the 32-unit tiles).  A lane keeps the leaky_relu and
+// clamp masks of the units it produced as bits in registers: the backward pass's accumulators
+// have the forward's layout (units the MFMA's rows, envs its columns), so the same lane applies
+// them.  x_1..x_3 and D_1..D_4 go to the chunk's workspace unit-major (wab_policy_grad.h).
+// wab_policy_wgrad_kernel: one wave per (up to 4 output tiles x one 32-column tile, slab).
+// wab_policy_grad_reduce_kernel: slabs -> the ten torch-layout tensors and the four loss scalars.
+#include <hip/hip_runtime.h>
+
+#include "wab_policy_dev.h"
+#include "wab_policy_grad.h"
+
+namespace wab {
+
+// ------------------------------------------------------------------------ transposed image
+__device__ __forceinline__ uint16_t grad_wt_elem(const GradPackParams& p, int img, uint32_t i) {
+  const PolicyDims& d = p.g.d;
+  const uint32_t j = i & 7u, lane = (i >> 3) & 63u, f = i >> 9;
+  const int KT = img == 1 ? p.g.KT1 : (img == 2 ? p.g.KT2 : p.g.KT3);
+  const int nt = (int)(f / (uint32_t)KT), ks = (int)(f % (uint32_t)KT);
+  const int n = 32 * nt + (int)(lane & 31u);                      // unit of layer img
+  const int k = 16 * ks + 8 * (int)(lane >> 5) + (int)j;          // unit of layer img + 1
+  // element (k, n) of the forward image of layer img + 1: tile k / 32, k-step n / 16
+  const int KSf = img == 1 ? d.KS2 : (img == 2 ? d.KS3 : d.KS4);
+  const int NTf = img == 1 ? d.NT2 : (img == 2 ? d.NT3 : 1);
+  const uint32_t base = img == 1 ? d.w2 : (img == 2 ? d.w3 : d.wh);
+  if (n >= 16 * KSf || k >= 32 * NTf) return 0;
+  const uint32_t lanef = (uint32_t)(k & 31) + 32u * (uint32_t)((n & 15) >> 3);
+  return p.w[base + (((uint32_t)(k >> 5) * (uint32_t)KSf + (uint32_t)(n >> 4)) * 64u + lanef) * 8u + (uint32_t)(n & 7)];
+}
+
+__global__ __launch_bounds__(256) void wab_policy_grad_pack(GradPackParams p) {
+  const GradPlan& g = p.g;
+  const uint32_t stride = gridDim.x * 256u;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *p.bad = 0u;
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < g.wt_total; i += stride) {
+    if (i < g.wt2) p.wt[i] = grad_wt_elem(p, 1, i - g.wt1);
+    else if (i < g.wt3) p.wt[i] = grad_wt_elem(p, 2, i - g.wt2);
+    else p.wt[i] = grad_wt_elem(p, 3, i - g.wt3);
+  }
+}
+
+// ------------------------------------------------------------------------ epilogues
+// pol_store's value (the same operations in the same order) into the next layer's LDS image and
+// the workspace, and the masks: bit (g & 1) * 16 + 4 mt + i of sb[g >> 1] is z >= 0, of cb the
+// same for -4 <= leaky_relu(z) <= 4.  Rows past n_env go to the workspace as zeros.
+template <bool CLAMP>
+__device__ __forceinline__ void grad_fwd_store(const pol_f32x16 (&acc)[4], const float* __restrict__ bias, int tile,
+                                               uint16_t* xn, int pitch, int lane, int n_env, uint16_t* wsx,
+                                               int64_t cr, uint32_t (&sb)[2], uint32_t (&cb)[2]) {
+  const int r = lane & 31, h = lane >> 5;
+  sb[0] = sb[1] = 0u;
+  cb[0] = cb[1] = 0u;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int n = 32 * tile + 8 * g + 4 * h;
+    const float4 bv = *reinterpret_cast<const float4*>(bias + n);
+    const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      uint32_t o[4];
+      const bool row_in = mt * 32 + r < n_env;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float v = acc[mt][4 * g + i] + bb[i];
+        const uint32_t bit = 1u << ((g & 1) * 16 + 4 * mt + i);
+        if (v >= 0.0f) sb[g >> 1] |= bit;
+        v = v >= 0.0f ? v : 0.01f * v;
+        if (CLAMP) {
+          if (v >= -4.0f && v <= 4.0f) cb[g >> 1] |= bit;
+          v = fminf(fmaxf(v, -4.0f), 4.0f);
+        }
+        o[i] = pol_bf16(v);
+        wsx[(size_t)(n + i) * (size_t)cr + (size_t)(mt * 32 + r)] = (uint16_t)(row_in ? o[i] : 0u);
+      }
+      uint2 w;
+      w.x = o[0] | (o[1] << 16);
+      w.y = o[2] | (o[3] << 16);
+      *reinterpret_cast<uint2*>(xn + (size_t)(mt * 32 + r) * (size_t)pitch + (size_t)n) = w;
+    }
+  }
+}
+
+// D = bf16(dx * slope * clamp mask) of the tile's units into the LDS image the next backward
+// layer reads (TO_LDS) and the workspace
+template <bool CLAMP, bool TO_LDS>
+__device__ __forceinline__ void grad_bwd_store(const pol_f32x16 (&acc)[4], int tile, uint16_t* dn, int pitch, int lane,
+                                               uint16_t* wsd, int64_t cr, const uint32_t (&sb)[2],
+                                               const uint32_t (&cb)[2]) {
+  const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int n = 32 * tile + 8 * g + 4 * h;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      uint32_t o[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint32_t bit = 1u << ((g & 1) * 16 + 4 * mt + i);
+        float v = acc[mt][4 * g + i];
+        v = (sb[g >> 1] & bit) ? v : 0.01f * v;
+        if (CLAMP) v = (cb[g >> 1] & bit) ? v : 0.0f;
+        o[i] = pol_bf16(v);
+        wsd[(size_t)(n + i) * (size_t)cr + (size_t)(mt * 32 + r)] = (uint16_t)o[i];
+      }
+      if (TO_LDS) {
+        uint2 w;
+        w.x = o[0] | (o[1] << 16);
+        w.y = o[2] | (o[3] << 16);
+        *reinterpret_cast<uint2*>(dn + (size_t)(mt * 32 + r) * (size_t)pitch + (size_t)n) = w;
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ double grad_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_xor(v, o, 64);
+  return v;
+}
+
+// ------------------------------------------------------------------------ forward, head, backward chain
+template <bool TWO>
+__global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBwdParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char grad_smem[];
+  uint16_t* const regA = reinterpret_cast<uint16_t*>(grad_smem);
+  uint16_t* const regB = reinterpret_cast<uint16_t*>(grad_smem + p.g.off_b);
+  uint16_t* const regC = regA;  // D_4, once X_2 has been read
+  const GradPlan& g = p.g;
+  const PolicyDims& d = g.d;
+  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+  const int r = lane & 31, h = lane >> 5;
+  const int64_t env0 = p.row0 + (int64_t)blockIdx.x * kGradRows;  // (global row; < N by the grid)
+  const int n_env = (int)(p.N - env0 < kGradRows ? p.N - env0 : kGradRows);
+  const int64_t cr = p.chunk_rows;
+  uint16_t* const ws = p.ws + (size_t)blockIdx.x * kGradRows;  // this block's rows of every unit
+  const uint4* const wimg = reinterpret_cast<const uint4*>(p.w);
+  const uint4* const wtimg = reinterpret_cast<const uint4*>(p.wt);
+
+  uint32_t s1[2][2] = {}, s2[2][2] = {}, s3[2][2] = {}, c3[2][2] = {}, cx[2] = {};
+
+  // ---- layer 1: as wab_policy_kernel
+  pol_f32x16 acc0[4], acc1[4];
+  pol_zero(acc0);
+  if (TWO) pol_zero(acc1);
+  const int KC = g.KC, pitch_in = g.pitch_in;
+  const int kpad = 16 * d.KS1;
+  uint4 wf[kPolicyMaxKs];
+  const uint4* const w1t = wimg + (d.w1 >> 3) + (size_t)wave * (size_t)d.KS1 * 64u + (size_t)lane;
+  for (int c = 0; c < g.n_chunks; ++c) {
+    const int k0 = c * KC;
+    const int kn = kpad - k0 < KC ? kpad - k0 : KC;
+    const int ks0 = k0 >> 4, nks = kn >> 4;
+    if (wave < d.NT1) pol_load_frags(wf, w1t + (size_t)ks0 * 64u, nks);
+    if (c > 0) __syncthreads();
+    for (int kl = lane; kl < kn; kl += 64) {
+      const int k = k0 + kl;
+      const bool kin = k < d.F;
+      const float* col = p.features + (size_t)env0 * (size_t)d.F + (size_t)(kin ? k : d.F - 1);
+      constexpr int kRows = 16;
+      for (int eb = 0; eb < kGradRows / 4; eb += kRows) {
+        float v[kRows];
+#pragma unroll
+        for (int i = 0; i < kRows; ++i) {
+          const int e = wave + 4 * (eb + i);
+          v[i] = col[(size_t)(e < n_env ? e : n_env - 1) * (size_t)d.F];
+        }
+#pragma unroll
+        for (int i = 0; i < kRows; ++i) {
+          const int e = wave + 4 * (eb + i);
+          regA[(size_t)e * (size_t)pitch_in + (size_t)kl] = (uint16_t)((kin && e < n_env) ? pol_bf16(v[i]) : 0u);
+        }
+      }
+    }
+    __syncthreads();
+    const uint16_t* x = regA + (size_t)r * (size_t)pitch_in + 8 * h;
+    if (wave < d.NT1) pol_mma(acc0, wf, nks, x, pitch_in);
+    if (TWO && wave + 4 < d.NT1) {
+      pol_load_frags(wf, w1t + ((size_t)4 * (size_t)d.KS1 + (size_t)ks0) * 64u, nks);
+      pol_mma(acc1, wf, nks, x, pitch_in);
+    }
+  }
+  uint16_t* const wsx1 = ws + (size_t)g.u_x[1] * (size_t)cr;
+  if (wave < d.NT1) grad_fwd_store<false>(acc0, p.b + d.b1, wave, regB, g.pitch1, lane, n_env, wsx1, cr, s1[0], cx);
+  if (TWO && wave + 4 < d.NT1)
+    grad_fwd_store<false>(acc1, p.b + d.b1, wave + 4, regB, g.pitch1, lane, n_env, wsx1, cr, s1[1], cx);
+  __syncthreads();  // X1 complete; region A free
+
+  // ---- layer 2: X1 (region B) -> X2 (region A); layer 3: X2 -> X3 (region B), clamped
+  {
+    const uint4* const w2 = wimg + (d.w2 >> 3);
+    uint16_t* const wsx = ws + (size_t)g.u_x[2] * (size_t)cr;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int t = wave + 4 * j;
+      if (t < d.NT2) {
+        pol_load_frags(wf, w2 + (size_t)t * (size_t)d.KS2 * 64u + (size_t)lane, d.KS2);
+        pol_zero(acc0);
+        pol_mma(acc0, wf, d.KS2, regB + (size_t)r * (size_t)g.pitch1 + 8 * h, g.pitch1);
+        grad_fwd_store<false>(acc0, p.b + d.b2, t, regA, g.pitch2, lane, n_env, wsx, cr, s2[j], cx);
+      }
+    }
+  }
+  __syncthreads();
+  {
+    const uint4* const w3 = wimg + (d.w3 >> 3);
+    uint16_t* const wsx = ws + (size_t)g.u_x[3] * (size_t)cr;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int t = wave + 4 * j;
+      if (t < d.NT3) {
+        pol_load_frags(wf, w3 + (size_t)t * (size_t)d.KS3 * 64u + (size_t)lane, d.KS3);
+        pol_zero(acc0);
+        pol_mma(acc0, wf, d.KS3, regA + (size_t)r * (size_t)g.pitch2 + 8 * h, g.pitch2);
+        grad_fwd_store<true>(acc0, p.b + d.b3, t, regB, g.pitch3, lane, n_env, wsx, cr, s3[j], c3[j]);
+      }
+    }
+  }
+  pol_load_frags(wf, wimg + (d.wh >> 3) + (size_t)lane, d.KS4);
+  __syncthreads();
+
+  // ---- heads: wave w on rows 32 w .., lanes 0..31 finish (pol_sample's softmax, in its order)
+  {
+    const pol_f32x16 acc = pol_head_mma(wf, d.KS4, regB + (size_t)(32 * wave + r) * (size_t)g.pitch3 + 8 * h);
+    float lg[kPolicyMaxActions];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      lg[i] = acc[i];
+      lg[4 + i] = __shfl(acc[i], (lane + 32) & 63, 64);
+    }
+    const int my = 32 * wave + r;
+    const int64_t row = env0 + my;
+    const bool live = h == 0 && my < n_env;
+    double part[3] = {0.0, 0.0, 0.0};
+    if (h == 0) {
+      const float* bh = p.b + d.bh;
+      const int A = d.A;
+      const float val = acc[4] + bh[kPolicyMaxActions];
+      float z[kPolicyMaxActions], pk[kPolicyMaxActions], gk[kPolicyMaxActions];
+      float m = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < kPolicyMaxActions; ++k) {
+        lg[k] = lg[k] + bh[k];
+        if (k < A) m = fmaxf(m, lg[k]);
+      }
+      float s = 0.0f;
+#pragma unroll
+      for (int k = 0; k < kPolicyMaxActions; ++k) {
+        z[k] = lg[k] - m;
+        lg[k] = k < A ? expf(z[k]) : 0.0f;
+        if (k < A) s = s + lg[k];
+      }
+      const float inv = 1.0f / s;
+      const float ls = logf(s);
+      float H = 0.0f;
+#pragma unroll
+      for (int k = 0; k < kPolicyMaxActions; ++k) {
+        pk[k] = lg[k] * inv;
+        z[k] = z[k] - ls;  // log p_k
+        if (k < A) H = H - pk[k] * z[k];
+      }
+      int a = 0;
+      float wgt = 0.0f, tgt = 0.0f;
+      if (live) {
+        a = (int)p.actions[row];
+        wgt = p.weight[row];
+        tgt = p.target[row];
+      }
+      const bool bad = a < 0 || a >= A;
+      const bool use = live && !bad;
+      if (live && bad) atomicAdd(p.bad, 1u);
+      float la = 0.0f;
+#pragma unroll
+      for (int k = 0; k < kPolicyMaxActions; ++k) {
+        if (k == a) la = z[k];
+        const float g1 = wgt * (pk[k] - (k == a ? 1.0f : 0.0f));
+        const float g2 = p.entropy_coef * (pk[k] * (z[k] + H));
+        gk[k] = (use && k < A) ? g1 + g2 : 0.0f;
+      }
+      const float dl = val - tgt, ad = fabsf(dl);
+      const bool quad = p.mse || ad < 1.0f;
+      const float lv = quad ? 0.5f * dl * dl : ad - 0.5f;
+      const float dv = quad ? dl : (dl > 0.0f ? 1.0f : -1.0f);
+      const float gv = use ? p.value_coef * dv : 0.0f;
+      if (use) {
+        part[0] = (double)(-(wgt * la));
+        part[1] = (double)lv;
+        part[2] = (double)H;
+      }
+      if (live) {
+        if (p.logp) p.logp[row] = bad ? 0.0f : la;
+        if (p.value) p.value[row] = val;
+        if (p.entropy) p.entropy[row] = H;
+      }
+      // D_4's row: [g_logit (8) | g_v | 0 x 7] as bf16, to region C and the workspace
+      uint32_t o[kGradHeadUnits];
+#pragma unroll
+      for (int k = 0; k < kGradHeadUnits; ++k)
+        o[k] = k < kPolicyMaxActions ? pol_bf16(gk[k < kPolicyMaxActions ? k : 0])
+                                     : (k == kPolicyMaxActions ? pol_bf16(gv) : 0u);
+      uint4 q0, q1;
+      q0.x = o[0] | (o[1] << 16); q0.y = o[2] | (o[3] << 16); q0.z = o[4] | (o[5] << 16); q0.w = o[6] | (o[7] << 16);
+      q1.x = o[8] | (o[9] << 16); q1.y = o[10] | (o[11] << 16); q1.z = o[12] | (o[13] << 16); q1.w = o[14] | (o[15] << 16);
+      uint4* const drow = reinterpret_cast<uint4*>(regC + (size_t)my * (size_t)g.pitch4);
+      drow[0] = q0;
+      drow[1] = q1;
+      uint16_t* const wsd = ws + (size_t)g.u_d[4] * (size_t)cr + (size_t)my;
+#pragma unroll
+      for (int k = 0; k < kGradHeadUnits; ++k) wsd[(size_t)k * (size_t)cr] = (uint16_t)o[k];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double v = grad_wave_sum(part[j]);
+      if (lane == 0) p.part[((size_t)blockIdx.x * 4u + (size_t)wave) * 3u + (size_t)j] = v;
+    }
+  }
+  __syncthreads();  // D_4 complete
+
+  // ---- dx_3 = D_4 . [Wa; Wv] -> D_3 (region B); dx_2 = D_3 . W_3 -> D_2 (region A); dx_1 -> D_1
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int t = wave + 4 * j;
+    if (t < d.NT3) {
+      pol_load_frags(wf, wtimg + (g.wt3 >> 3) + (size_t)t * (size_t)g.KT3 * 64u + (size_t)lane, g.KT3);
+      pol_zero(acc0);
+      pol_mma(acc0, wf, g.KT3, regC + (size_t)r * (size_t)g.pitch4 + 8 * h, g.pitch4);
+      grad_bwd_store<true, true>(acc0, t, regB, g.pitch3, lane, ws + (size_t)g.u_d[3] * (size_t)cr, cr, s3[j], c3[j]);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int t = wave + 4 * j;
+    if (t < d.NT2) {
+      pol_load_frags(wf, wtimg + (g.wt2 >> 3) + (size_t)t * (size_t)g.KT2 * 64u + (size_t)lane, g.KT2);
+      pol_zero(acc0);
+      pol_mma(acc0, wf, g.KT2, regB + (size_t)r * (size_t)g.pitch3 + 8 * h, g.pitch3);
+      grad_bwd_store<false, true>(acc0, t, regA, g.pitch2, lane, ws + (size_t)g.u_d[2] * (size_t)cr, cr, s2[j], cx);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int t = wave + 4 * j;
+    if (t < d.NT1) {
+      pol_load_frags(wf, wtimg + (g.wt1 >> 3) + (size_t)t * (size_t)g.KT1 * 64u + (size_t)lane, g.KT1);
+      pol_zero(acc0);
+      pol_mma(acc0, wf, g.KT1, regA + (size_t)r * (size_t)g.pitch2 + 8 * h, g.pitch2);
+      grad_bwd_store<false, false>(acc0, t, nullptr, 0, lane, ws + (size_t)g.u_d[1] * (size_t)cr, cr, s1[j], cx);
+    }
+  }
+}
+
+template __global__ void wab_policy_bwd_kernel<false>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true>(GradBwdParams p);
+
+// ------------------------------------------------------------------------ dW, db
+// the slab's row blocks of this chunk, ascending: acc[i] += D_l[rows, tile i]^T . [X_{l-1} | 1][rows, tile kt]
+template <bool FEAT>
+__device__ __forceinline__ void grad_wgrad_blocks(const GradWgradParams& p, int K, int n_d, int u_d, int u_x, int grp,
+                                                  int kt, int tiles, int slab, int lane,
+                                                  pol_f32x16 (&acc)[kGradTiles]) {
+  const GradPlan& g = p.g;
+  const int r = lane & 31, h = lane >> 5;
+  const size_t cr = (size_t)p.chunk_rows;
+  const int64_t S = g.slabs;
+  const int64_t B0 = p.row0 / kGradRows;
+  const int c = 32 * kt + r;
+  const bool c_in = c < K, c_one = c == K;
+  const uint16_t* const xcol = p.ws + (size_t)(u_x + (c_in && !FEAT ? c : 0)) * cr;
+  const float* const fcol = p.features + (size_t)(c_in ? c : 0);
+  const uint16_t* dcol[kGradTiles];
+  bool a_ok[kGradTiles];
+#pragma unroll
+  for (int i = 0; i < kGradTiles; ++i) {
+    const int m = 32 * (kGradTiles * grp + i) + r;
+    a_ok[i] = m < n_d;
+    dcol[i] = p.ws + (size_t)(u_d + (a_ok[i] ? m : 0)) * cr;
+  }
+  // operands outside the arrays as masks (a select between whole vectors goes through scratch):
+  // a column past K_in is 0, column K_in the bf16 ones; an output unit past the array is 0
+  const uint32_t b_and = c_in ? 0xFFFFFFFFu : 0u, b_or = c_one ? 0x3F803F80u : 0u;
+  uint32_t a_and[kGradTiles];
+#pragma unroll
+  for (int i = 0; i < kGradTiles; ++i) a_and[i] = a_ok[i] ? 0xFFFFFFFFu : 0u;
+  for (int64_t b = B0 + ((int64_t)slab - B0 % S + S) % S; b < B0 + p.n_blocks; b += S) {
+    const size_t rb = (size_t)(b - B0) * kGradRows;
+#pragma unroll 4
+    for (int ks = 0; ks < kGradRows / 16; ++ks) {
+      const size_t rc = rb + (size_t)(16 * ks + 8 * h);
+      uint4 bv;
+      if (FEAT) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          int64_t row = p.row0 + (int64_t)rc + j;
+          row = row < p.N ? row : p.N - 1;  // (rows past N have D = 0)
+          v[j] = fcol[(size_t)row * (size_t)K];
+        }
+        bv.x = pol_bf16(v[0]) | (pol_bf16(v[1]) << 16);
+        bv.y = pol_bf16(v[2]) | (pol_bf16(v[3]) << 16);
+        bv.z = pol_bf16(v[4]) | (pol_bf16(v[5]) << 16);
+        bv.w = pol_bf16(v[6]) | (pol_bf16(v[7]) << 16);
+      } else {
+        bv = *reinterpret_cast<const uint4*>(xcol + rc);
+      }
+      bv.x = (bv.x & b_and) | b_or; bv.y = (bv.y & b_and) | b_or;
+      bv.z = (bv.z & b_and) | b_or; bv.w = (bv.w & b_and) | b_or;
+#pragma unroll
+      for (int i = 0; i < kGradTiles; ++i) {
+        if (i < tiles) {  // (uniform)
+          uint4 av = *reinterpret_cast<const uint4*>(dcol[i] + rc);
+          av.x &= a_and[i]; av.y &= a_and[i]; av.z &= a_and[i]; av.w &= a_and[i];
+          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pol_frag(av), pol_frag(bv), acc[i], 0, 0, 0);
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void wab_policy_wgrad_kernel(GradWgradParams p) {
+  const GradPlan& g = p.g;
+  const int lane = (int)threadIdx.x, task = (int)blockIdx.x, slab = (int)blockIdx.y;
+  const int64_t S = g.slabs;
+  const int64_t B0 = p.row0 / kGradRows;
+  if (task == g.n_tasks) {
+    // the loss terms of the slab's row blocks, ascending, waves in order
+    if (lane < 3) {
+      double* const dst = p.loss + (size_t)slab * 3u + (size_t)lane;
+      double v = p.first ? 0.0 : *dst;
+      for (int64_t b = B0 + ((int64_t)slab - B0 % S + S) % S; b < B0 + p.n_blocks; b += S)
+        for (int w = 0; w < 4; ++w) v = v + p.part[((size_t)(b - B0) * 4u + (size_t)w) * 3u + (size_t)lane];
+      *dst = v;
+    }
+    return;
+  }
+  // the task's layer and its constants (static indices: the plan stays in scalar registers)
+  int layer = 1, t0 = 0, K = g.k_in[1], n_d = g.n_d[1], u_d = g.u_d[1], u_x = 0, kts = g.ktiles[1];
+#pragma unroll
+  for (int l = 2; l <= 4; ++l)
+    if (task >= g.task0[l]) {
+      layer = l; t0 = g.task0[l]; K = g.k_in[l]; n_d = g.n_d[l]; u_d = g.u_d[l]; u_x = g.u_x[l - 1]; kts = g.ktiles[l];
+    }
+  const int local = task - t0;
+  const int grp = local / kts, kt = local % kts;
+  const int all = layer < 4 ? n_d / 32 : 1;
+  const int tiles = all - kGradTiles * grp < kGradTiles ? all - kGradTiles * grp : kGradTiles;
+  float* const sl = p.slab + ((size_t)slab * (size_t)g.n_tasks + (size_t)task) * (size_t)(kGradTiles * 1024) + (size_t)lane;
+  pol_f32x16 acc[kGradTiles];
+  pol_zero(acc);
+  if (!p.first) {
+#pragma unroll
+    for (int i = 0; i < kGradTiles; ++i)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[i][q] = sl[(size_t)((i * 16 + q) * 64)];
+  }
+  if (layer == 1) grad_wgrad_blocks<true>(p, K, n_d, u_d, u_x, grp, kt, tiles, slab, lane, acc);
+  else grad_wgrad_blocks<false>(p, K, n_d, u_d, u_x, grp, kt, tiles, slab, lane, acc);
+#pragma unroll
+  for (int i = 0; i < kGradTiles; ++i)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sl[(size_t)((i * 16 + q) * 64)] = acc[i][q];
+}
+
+// ------------------------------------------------------------------------ slabs -> gradients
+__global__ __launch_bounds__(256) void wab_policy_grad_reduce_kernel(GradReduceParams p) {
+  const GradPlan& g = p.g;
+  const PolicyDims& d = g.d;
+  const int64_t n1 = (int64_t)d.h1 * (d.F + 1), n2 = (int64_t)d.h2 * (d.h1 + 1), n3 = (int64_t)d.h3 * (d.h2 + 1);
+  const int64_t n4 = (int64_t)(d.A + 1) * (d.h3 + 1);
+  const int64_t total = n1 + n2 + n3 + n4;
+  const size_t slab_stride = (size_t)g.n_tasks * (size_t)(kGradTiles * 1024);
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    int layer;
+    int64_t o = e;
+    if (o < n1) layer = 1;
+    else if ((o -= n1) < n2) layer = 2;
+    else if ((o -= n2) < n3) layer = 3;
+    else { o -= n3; layer = 4; }
+    const int K = layer == 1 ? d.F : (layer == 2 ? d.h1 : (layer == 3 ? d.h2 : d.h3));
+    const int t0 = layer == 1 ? g.task0[1] : (layer == 2 ? g.task0[2] : (layer == 3 ? g.task0[3] : g.task0[4]));
+    const int kts = layer == 1 ? g.ktiles[1] : (layer == 2 ? g.ktiles[2] : (layer == 3 ? g.ktiles[3] : g.ktiles[4]));
+    const int n = (int)(o / (K + 1)), k = (int)(o % (K + 1));
+    // the MFMA row of the unit: the value head is row 8 of the head tile
+    const int nm = (layer == 4 && n == d.A) ? kPolicyMaxActions : n;
+    const int tile = nm >> 5, m = nm & 31;
+    const int task = t0 + (tile / kGradTiles) * kts + (k >> 5);
+    const int q = 4 * (m >> 3) + (m & 3), ln = (k & 31) + 32 * ((m >> 2) & 1);
+    const size_t idx = ((size_t)task * kGradTiles + (size_t)(tile % kGradTiles)) * 1024u + (size_t)(q * 64 + ln);
+    float v = 0.0f;
+    if (!p.empty)
+      for (int s = 0; s < g.slabs; ++s) v = v + p.slab[(size_t)s * slab_stride + idx];
+    v = v * p.scale;
+    float* dst;
+    if (layer == 1) dst = k < K ? p.w1 + (size_t)n * (size_t)K + k : p.b1 + n;
+    else if (layer == 2) dst = k < K ? p.w2 + (size_t)n * (size_t)K + k : p.b2 + n;
+    else if (layer == 3) dst = k < K ? p.w3 + (size_t)n * (size_t)K + k : p.b3 + n;
+    else if (n < d.A) dst = k < K ? p.wa + (size_t)n * (size_t)K + k : p.ba + n;
+    else dst = k < K ? p.wv + k : p.bv;
+    *dst = p.accumulate ? *dst + v : v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && p.loss_out) {
+    double l[3] = {0.0, 0.0, 0.0};
+    if (!p.empty)
+      for (int s = 0; s < g.slabs; ++s)
+        for (int j = 0; j < 3; ++j) l[j] = l[j] + p.loss[(size_t)s * 3u + (size_t)j];
+    const double tot = (double)p.scale * (l[0] + (double)p.value_coef * l[1] - (double)p.entropy_coef * l[2]);
+    const float out[4] = {(float)l[0], (float)l[1], (float)l[2], (float)tot};
+    for (int j = 0; j < 4; ++j) p.loss_out[j] = p.accumulate ? p.loss_out[j] + out[j] : out[j];
+  }
+}
+
+}  // namespace wab

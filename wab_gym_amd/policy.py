@@ -4,11 +4,15 @@ action sampled in the same launch (wab_policy_act, wab_gym_amd/csrc/wab_policy.h
     policy = DevicePolicy(model, env)            # model: the five Linears by the reference's names
     actions = policy.act(features)               # int8 [B]; probs=/value= tensors are filled too
     ...optimizer.step()...; policy.load(model)   # stream-ordered re-pack, no host sync
+    policy.loss_and_grad(features, actions, weight, target, into=model)   # finish_episode's loss
+                                                 # and loss.backward() (wab_policy_grad)
 
-Training stays in torch (backward, Adam, the batched re-forward over the stored features).
+The optimizer stays in torch: loss_and_grad fills each parameter's .grad, the caller steps and
+reloads.
 
-What the kernel computes is `reference_forward` below (the numeric contract, in torch on the CPU)
-and `sample_reference` (the sampling rule, in numpy); the tests check the kernel against them.
+What the kernels compute is `reference_forward` and `reference_loss_and_grad` below (the numeric
+contracts, in torch on the CPU) and `sample_reference` (the sampling rule, in numpy); the tests
+check the kernels against them.
 The reference's `+ U(0, 1) / 100` input noise (actor_critic.py:189) is not reproduced.
 """
 from __future__ import annotations
@@ -86,6 +90,111 @@ def reference_forward(state_dict, features, hidden=None):
     return e / e.sum(dim=-1, keepdim=True), linear(x, "value_head")[:, 0]
 
 
+def reference_loss_and_grad(state_dict, features, actions, weight, target, value_coef=1.0, entropy_coef=0.0,
+                            value_loss="smooth_l1", scale=1.0, round_grads=True):
+    """wab_policy_grad's numeric contract in torch on the CPU, float64, written out by hand (no
+    autograd).  The forward is reference_forward.  Per row, p = softmax(logits), H = -sum p log p:
+
+        loss_policy = -sum_i weight_i log p_i[a_i];  loss_value = sum_i l(v_i - target_i), l
+        smooth_l1 (beta 1) or "mse" = d^2 / 2;  loss_entropy = sum_i H_i;
+        total = scale (loss_policy + value_coef loss_value - entropy_coef loss_entropy)
+
+    and the gradients of `total`, straight-through: every bf16 rounding has derivative 1.  With
+    G_4 = [weight (p - onehot) + entropy_coef p (log p + H) | value_coef l'] and D_l = bf16(G_l)
+    (G_l itself without round_grads): dW_l = D_l^T x_{l-1}, db_l = sum_i D_l[i], dx_{l-1} = D_l
+    bf16(W_l), G_{l-1} = dx_{l-1} * (z >= 0 ? 1 : float32(0.01)) * (layer 3: -4 <= leaky_relu(z) <= 4).
+    Returns {"loss": (policy, value, entropy, total), "logp", "value", "entropy": [N] rows,
+    "grads": the ten tensors in torch Linear layout}, all float64."""
+    import torch
+
+    if value_loss not in ("smooth_l1", "mse"):
+        raise ValueError("value_loss must be 'smooth_l1' or 'mse'")
+    sd = {k: v.detach().to("cpu", torch.float32) for k, v in _state_dict(state_dict).items()}
+
+    def bf(x):
+        return x.to(torch.float32).to(torch.bfloat16).to(torch.float64)
+
+    def rd(g):
+        return bf(g) if round_grads else g
+
+    x0 = bf(torch.as_tensor(features).detach().to("cpu", torch.float32))
+    a = torch.as_tensor(actions).detach().to("cpu", torch.int64)
+    w = torch.as_tensor(weight).detach().to("cpu", torch.float64)
+    tg = torch.as_tensor(target).detach().to("cpu", torch.float64)
+    hidden = []
+    _, v = reference_forward(sd, features, hidden=hidden)
+    xs = [x0] + [h[1] for h in hidden]
+    wq = {n: bf(sd[n + ".weight"]) for n in LAYERS}
+    logits = xs[3] @ wq["action_head"].T + sd["action_head.bias"].to(torch.float64)
+    zc = logits - logits.max(dim=-1, keepdim=True).values
+    logp_all = zc - torch.log(torch.exp(zc).sum(dim=-1, keepdim=True))
+    p = torch.exp(logp_all)
+    H = -(p * logp_all).sum(dim=-1)
+    onehot = torch.zeros_like(p)
+    onehot[torch.arange(len(a)), a] = 1.0
+    logp = (logp_all * onehot).sum(dim=-1)
+    d = v - tg
+    if value_loss == "mse":
+        lv, dv = 0.5 * d * d, d
+    else:
+        lv = torch.where(d.abs() < 1.0, 0.5 * d * d, d.abs() - 0.5)
+        dv = torch.where(d.abs() < 1.0, d, torch.sign(d))
+    loss_policy, loss_value, loss_entropy = -(w * logp).sum(), lv.sum(), H.sum()
+    total = scale * (loss_policy + value_coef * loss_value - entropy_coef * loss_entropy)
+
+    Da = rd(w[:, None] * (p - onehot) + entropy_coef * p * (logp_all + H[:, None]))
+    Dv = rd(value_coef * dv)[:, None]
+    grads = {"action_head.weight": Da.T @ xs[3], "action_head.bias": Da.sum(dim=0),
+             "value_head.weight": Dv.T @ xs[3], "value_head.bias": Dv.sum(dim=0)}
+    dx = Da @ wq["action_head"] + Dv @ wq["value_head"]
+    slope = float(np.float32(0.01))
+    for i in (2, 1, 0):
+        z = hidden[i][0]
+        G = dx * torch.where(z >= 0, 1.0, slope)
+        if i == 2:
+            y = torch.where(z >= 0, z, z * slope)
+            G = G * ((y >= -4.0) & (y <= 4.0)).to(torch.float64)
+        D = rd(G)
+        grads[LAYERS[i] + ".weight"] = D.T @ xs[i]
+        grads[LAYERS[i] + ".bias"] = D.sum(dim=0)
+        dx = D @ wq[LAYERS[i]]
+    grads = {k: g * scale for k, g in grads.items()}
+    return {"loss": (loss_policy, loss_value, loss_entropy, total), "logp": logp, "value": v, "entropy": H,
+            "grads": grads}
+
+
+def check_loss_args(shape, features, actions, weight, target, value_loss="smooth_l1", reduction="sum", into=None,
+                    accumulate=False):
+    """loss_and_grad's checks that need no device: returns N, the row count.  features [N, F] or
+    [T, B, F] float32, actions int8, weight and target float32 of the leading shape, all
+    contiguous and on one device."""
+    import torch
+
+    F = shape[0]
+    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() not in (2, 3) \
+            or features.shape[-1] != F or not features.is_contiguous():
+        raise ValueError("features must be a contiguous float32 tensor of shape [N, %d] or [T, B, %d]" % (F, F))
+    lead = tuple(features.shape[:-1])
+    for name, x, dt in (("actions", actions, torch.int8), ("weight", weight, torch.float32),
+                        ("target", target, torch.float32)):
+        if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != lead or not x.is_contiguous() \
+                or x.device != features.device:
+            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s"
+                             % (name, str(dt).replace("torch.", ""), lead, features.device))
+    if value_loss not in _lib.VALUE_LOSS:
+        raise ValueError("value_loss must be 'smooth_l1' or 'mse', not %r" % (value_loss,))
+    if reduction not in ("sum", "mean"):
+        raise ValueError("reduction must be 'sum' or 'mean', not %r" % (reduction,))
+    if accumulate and into is None:
+        raise ValueError("accumulate=True needs into=: there is no earlier gradient to add to")
+    n = 1
+    for k in lead:
+        n *= int(k)
+    if n >= 1 << 31:
+        raise ValueError("loss_and_grad takes fewer than 2^31 rows")
+    return n
+
+
 def keyed_u(seed, env_ids, episode, turn):
     """The 53-bit keyed uniform of the action draw: (seed, global env id, episode, site 11, turn,
     tile (0, 0), k = 0) under the definition of oracle/keyed_rng.py, restated here so that the
@@ -155,6 +264,7 @@ class DevicePolicy:
                    "wab_policy_create")
         self._p = p
         self._keep = None
+        self._grad_ws = None  # loss_and_grad's workspace, allocated by its first call
         B = base.num_envs
         self.actions = torch.zeros(B, dtype=torch.int8, device=base.device)
         self.load(module_or_state_dict)
@@ -198,6 +308,89 @@ class DevicePolicy:
                                               None if value is None else value.data_ptr(),
                                               self.env._stream()), "wab_policy_act")
         return dst
+
+    def _grad_targets(self, into, accumulate):
+        """The ten gradient tensors in LAYERS order (weight, bias): `into`'s .grad fields
+        (allocated where missing), or fresh ones."""
+        t = self._torch
+        F, h1, h2, h3, A = self.shape
+        shapes = [(h1, F), (h1,), (h2, h1), (h2,), (h3, h2), (h3,), (A, h3), (A,), (1, h3), (1,)]
+        names = ["%s.%s" % (n, part) for n in LAYERS for part in ("weight", "bias")]
+        if into is None:
+            return {k: t.empty(shp, dtype=t.float32, device=self.env.device) for k, shp in zip(names, shapes)}
+        out = {}
+        for k, shp in zip(names, shapes):
+            layer, part = k.split(".")
+            prm = getattr(getattr(into, layer, None), part, None)
+            if not isinstance(prm, t.Tensor) or tuple(prm.shape) != shp:
+                raise ValueError("into.%s must be a tensor of shape %s" % (k, shp))
+            if prm.dtype != t.float32 or prm.device != self.env.device:
+                raise ValueError("into.%s must be float32 on %s" % (k, self.env.device))
+            if prm.grad is None:
+                prm.grad = t.zeros_like(prm, memory_format=t.contiguous_format)
+            g = prm.grad
+            if g.dtype != t.float32 or g.device != self.env.device or not g.is_contiguous() or tuple(g.shape) != shp:
+                raise ValueError("into.%s.grad must be a contiguous float32 tensor of shape %s on %s"
+                                 % (k, shp, self.env.device))
+            out[k] = g
+        return out
+
+    def loss_and_grad(self, features, actions, weight, target, *, value_coef=1.0, entropy_coef=0.0,
+                      value_loss="smooth_l1", reduction="sum", into=None, accumulate=False, return_rows=False,
+                      chunk_rows=0, scale=None):
+        """finish_episode()'s loss and loss.backward() (actor_critic.py:148-165) on the env's stream,
+        no host synchronisation: features [N, F] or [T, B, F] (viewed, not copied), actions int8,
+        weight (the reference's R - value.item(), or an advantage; a constant) and target float32
+        of the leading shape.  loss = scale (loss_policy + value_coef loss_value - entropy_coef
+        entropy), scale 1 ("sum") or 1 / N ("mean") unless `scale` gives it; the three parts are
+        returned unscaled.  chunk_rows: rows per pass through the workspace (0: the default).
+        into=model writes (accumulate=True: adds to) each parameter's .grad; otherwise the result
+        holds "grads", the ten tensors by name.  Returns 0-d device tensors "loss", "loss_policy",
+        "loss_value", "entropy", and with return_rows "logp", "value", "entropy_rows" [N].
+        Rows whose action is out of range are left out and counted: check() raises for them."""
+        t = self._torch
+        n = check_loss_args(self.shape, features, actions, weight, target, value_loss, reduction, into, accumulate)
+        if features.device != self.env.device:
+            raise ValueError("features must be on %s" % (self.env.device,))
+        grads = self._grad_targets(into, accumulate)
+        L = _lib.load()
+        cfg = _lib.WabPolicyLoss(float(value_coef), float(entropy_coef), _lib.VALUE_LOSS[value_loss],
+                                 float(scale) if scale is not None else (1.0 / n if reduction == "mean" and n > 0
+                                                                         else 1.0), 1 if accumulate else 0,
+                                 int(chunk_rows))
+        need = L.wab_policy_grad_workspace(self._p, n, int(chunk_rows))
+        if need == 0:
+            _lib.check(-1, "wab_policy_grad_workspace")
+        if self._grad_ws is None or self._grad_ws.numel() < need:
+            self._grad_ws = t.empty(need, dtype=t.uint8, device=self.env.device)
+        loss = t.zeros(4, dtype=t.float32, device=self.env.device)
+        rows = [t.empty(n, dtype=t.float32, device=self.env.device) for _ in range(3)] if return_rows else [None] * 3
+        gw = _lib.WabPolicyWeights(*[grads["%s.%s" % (nm, part)].data_ptr() for nm in LAYERS
+                                     for part in ("weight", "bias")])
+        _lib.check(L.wab_policy_grad(self._p, features.data_ptr(), actions.data_ptr(), weight.data_ptr(),
+                                     target.data_ptr(), n, ctypes.addressof(cfg), ctypes.addressof(gw),
+                                     loss.data_ptr(), *[None if r is None else r.data_ptr() for r in rows],
+                                     self._grad_ws.data_ptr(), self._grad_ws.numel(), self.env._stream()),
+                   "wab_policy_grad")
+        out = {"loss": loss[3], "loss_policy": loss[0], "loss_value": loss[1], "entropy": loss[2]}
+        if into is None:
+            out["grads"] = grads
+        if return_rows:
+            lead = tuple(features.shape[:-1])
+            out["logp"], out["value"], out["entropy_rows"] = [r.view(lead) for r in rows]
+        return out
+
+    def check(self):
+        """Synchronises; raises IndexError if the latest loss_and_grad left rows out because their
+        action was outside [0, n_actions)."""
+        if self._grad_ws is None:
+            return
+        bad = ctypes.c_uint64(0)
+        rc = _lib.load().wab_policy_grad_bad_actions(self._p, self._grad_ws.data_ptr(), self.env._stream(),
+                                                     ctypes.byref(bad))
+        if bad.value:
+            raise IndexError(_lib.load().wab_last_error().decode(errors="replace"))
+        _lib.check(rc, "wab_policy_grad_bad_actions")
 
     def close(self):
         if getattr(self, "_p", None) is not None and self._p.value:
