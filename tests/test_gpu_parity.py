@@ -175,6 +175,47 @@ def test_wide_kernel_width_limit(width, height, kernel):
     assert env.step_kernel == kernel
 
 
+def test_block_kernel_lds_limit_survives_a_smaller_handle():
+    """Two live block-kernel handles of the same wolf_slots share wab_kernel<.., 8, false>: a
+    45x45 one (about 97 KB of dynamic LDS, above the 64 KB every kernel may use unasked) and a
+    13x13 one in 13-byte rows (a few KB), created second.  The per-kernel LDS limit the first was
+    created with must still hold when it steps and resets after the second's create (raise_lds
+    only raises): 8 steps, a masked reset and one more step, all against the oracle."""
+    import torch
+
+    n = 64
+    big, orc = _lockstep({"width": 45, "height": 45}, n, 0, wolf_slots=8)  # (created and reset)
+    small, _ = _lockstep({"width": 13, "height": 13}, n, 1, wolf_slots=8)
+    assert big.step_kernel == "block" and small.step_kernel == "block"
+    rng = np.random.RandomState(5)
+
+    def same_obs(obs, what):
+        assert np.array_equal(big._obs["planes"].cpu().numpy(), orc.planes), what
+        assert np.array_equal(obs[3].cpu().numpy(), orc.food_turns), what
+        assert np.array_equal(obs[4].cpu().numpy(), orc.role), what
+        assert np.array_equal(obs[5].cpu().numpy(), orc.status), what
+
+    def step(t):
+        a = rng.randint(big.n_actions, size=n)
+        obs, rew, done, _ = big.step(torch.as_tensor(a))
+        orc.step(a)
+        assert np.array_equal(done.cpu().numpy(), orc.done.astype(bool)), t
+        assert np.array_equal(rew.cpu().numpy(), orc.reward), t
+        same_obs(obs, t)
+
+    for t in range(8):
+        step(t)
+    mask = (rng.random_sample(n) < 0.3).astype(np.uint8)
+    obs = big.reset(torch.as_tensor(mask))
+    orc.reset(mask)
+    same_obs(obs, "masked reset")
+    step(8)
+    gs, os_ = big.state(), orc.state()
+    for k in ("x", "y", "turn", "n_wolves", "episode"):
+        assert np.array_equal(gs[k], os_[k]), k
+    assert np.array_equal(gs["food"].view(np.uint64), os_["food"].view(np.uint64))
+
+
 def test_wide_kernel_reset_mask():
     import torch
 

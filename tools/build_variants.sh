@@ -8,7 +8,7 @@ O=/tmp/wab_variants
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Werror -DWAB_DIAGNOSTIC_BUILD"  # never the product library (wab_build_guard.h)
 mkdir -p $O $REPO/wab_gym_amd/_lib/var
 VAR=${VARIANT_SRC:-wab_step_small}   # the source compiled per variant; the others once
-ALL="wab_step wab_step_small wab_step_wide wab_features wab_render wab_egocentric wab_torus wab_snapshot wab_policy wab_capi"
+ALL=$(cd $C && for s in *.hip; do echo ${s%.hip}; done)   # every source of the library (HIP_SOURCES)
 COMMON=$(for x in $ALL; do [ $x = $VAR ] || echo $x; done)
 for x in $COMMON; do
   fresh=1

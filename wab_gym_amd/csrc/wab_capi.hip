@@ -11,122 +11,35 @@
 #include <cstdio>
 #include <climits>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <new>
 #include <string>
 #include <utility>
 #include <vector>
 
-#include "../../include/wab.h"
-#include "wab_params.h"
+#include "wab_host.h"
 #include "wab_device.h"
 #include "wab_feat.h"
-#include "wab_policy.h"
-#include "wab_policy_grad.h"
-#include "wab_episodes.h"
-#include "wab_advantage.h"
 
-namespace wab {
-template <int MODE, int SLOTS, bool SMALL>
-__global__ void wab_kernel(Params p);
-template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES = false, bool POLICY = false>
-__global__ void wab_step_small(Params p);
-template <int MODE, int SLOTS>
-__global__ void wab_step_wide(Params p);
-template <int SLOTS, int FIXW>
-__global__ void wab_rollout_wide(Params p);
+using namespace wab_host;
 
-__global__ void wab_featurize_kernel(FeatParams p);
-__global__ void wab_featurize_small_kernel(FeatParams p);
-__global__ void wab_render_kernel(RenderParams p);
-__global__ void wab_egocentric_kernel(EgoParams p);
-template <int VEC, int NE>
-__global__ void wab_returns_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done, int32_t T,
-                                   int64_t B, double gamma, const float* __restrict__ bootstrap,
-                                   float* __restrict__ out, RewardTable tab);
-__global__ void wab_episode_count_kernel(EpisodeParams p);
-__global__ void wab_episode_scan_kernel(EpisodeParams p);
-template <int NE>
-__global__ void wab_episode_walk_kernel(EpisodeParams p);
-__global__ void wab_normalize_kernel(const float* x, const uint8_t* done, int32_t T, int64_t B, double eps, float* out);
-__global__ void wab_normalize_lds_kernel(const float* x, const uint8_t* done, int32_t T, int64_t B, double eps,
-                                         float* out);
-template <int VEC, int NE>
-__global__ void wab_gae_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done,
-                               const float* __restrict__ value, const float* __restrict__ last_value, int32_t T,
-                               int64_t B, double gamma, double gl, float* __restrict__ advantage,
-                               float* __restrict__ target, RewardTable tab);
-__global__ void wab_whiten_sum_kernel(const float* x, int64_t n, double* psum);
-__global__ void wab_whiten_dev_kernel(const float* x, int64_t n, const double* psum, double* pss);
-__global__ void wab_whiten_out_kernel(const float* x, int64_t n, double eps, const double* psum, const double* pss,
-                                      float* out);
-__global__ void wab_snapshot_pack(SnapParams p);
-__global__ void wab_snapshot_unpack(SnapParams p);
-__global__ void wab_policy_pack(PolicyPackParams p);
-template <bool TWO>
-__global__ void wab_policy_kernel(PolicyParams p);
-__global__ void wab_policy_grad_pack(GradPackParams p);
-template <bool TWO>
-__global__ void wab_policy_bwd_kernel(GradBwdParams p);
-__global__ void wab_policy_wgrad_kernel(GradWgradParams p);
-__global__ void wab_policy_grad_reduce_kernel(GradReduceParams p);
+thread_local std::string wab_host::g_err;
+
+hipError_t wab_host::raise_lds(int device, const void* kernel, size_t bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void*>, size_t> raised;
+  if (bytes <= 64u * 1024u) return hipSuccess;
+  std::lock_guard<std::mutex> lock(mu);
+  size_t& cur = raised[{device, kernel}];
+  if (bytes <= cur) return hipSuccess;
+  DeviceGuard guard(device);
+  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess) cur = bytes;
+  return e;
 }
-
-using wab::Params;
-
-struct wab_handle {
-  Params p;
-  int device = 0;
-  int slots = 8;
-  int n_blocks = 0;
-  size_t lds_bytes = 0;
-  int step_kernel = 0;         // KERNEL_BLOCK / KERNEL_SMALL
-  size_t small_lds_bytes = 0;  // LDS of the small-view kernel
-  size_t small_feat_lds_bytes = 0;  // ... with the fused featurizer (wab_step_features), 0: not fusable
-  bool reset_done = false;
-  std::vector<void*> allocs;
-  uint8_t* scratch_planes = nullptr;  // wab_step_features without planes, not fusable (lazy)
-  float* bounce_rows = nullptr;       // wab_rollout_policy's 2 T launches: two [B][F] feature rows (lazy)
-  size_t lds_max = 0;                 // the device's LDS limit per workgroup (wab_rollout_policy_fused)
-  // egocentric observation (allocated by the first wab_egocentric call)
-  uint4* ego_path = nullptr;
-  uint32_t* ego_diamond = nullptr;
-  int ego_cap = 0, ego_n_diamond = 0;
-  bool small_g11 = false;    // the small kernel's 11x11 specialisation (geometry_11)
-  bool small_rules = false;  // ... with the default options' rules as constants too (default_rules)
-  wab::RewardTable rewards;  // exact doubles of the rewards a step returns (n = 0: ambiguous)
-  size_t wide_lds_bytes = 0;  // LDS per workgroup of the wide kernel (see wab_create)
-  size_t wide_roll_lds_bytes = 0;  // ... of its multi-step build (wab_rollout_wide)
-  int32_t obs_placement = WAB_OBS_SAME_BUFFER;  // wab_set_obs_placement: which wide per-step build
-  uint64_t rollout_launches = 0, rollout_step_calls = 0;  // wab_counters' host tallies
-  uint64_t snapshot_hash = 0;  // wab_snapshot_hash of the options the handle was created with
-};
-
-// wab_policy_*: the packed weights of one network on one device (wab_policy.h)
-struct wab_policy {
-  int device = 0;
-  wab::PolicyDims dims;
-  wab::PolicyLds lds;
-  uint16_t* w = nullptr;  // bf16 image, dims.w_total elements
-  float* b = nullptr;     // padded biases, dims.b_total floats
-  bool loaded = false;
-};
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess)                                                          \
-      return fail(WAB_E_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-  } while (0)
 
 int n_actions_of(const wab_config* c) { return (c->gatherer_only || c->lookout_only) ? 5 : 6; }
 
@@ -190,20 +103,25 @@ uint64_t snapshot_hash_of(const wab_config* c, const uint64_t* table) {
   return f.h;
 }
 
+// What wab_create and the snapshot queries both ask of the options (wab_env.py:147-148 and the
+// limits of this implementation), with the resolved wolf_slots and eaten_capacity.
+int check_dims(const wab_config* c, int* slots, int* cap) {
+  if (c->width % 2 == 0 || c->height % 2 == 0) return fail(WAB_E_INVALID, "width and height must be odd numbers");
+  if (c->width < 1 || c->height < 1 || c->width > WAB_MAX_VIEW || c->height > WAB_MAX_VIEW)
+    return fail(WAB_E_INVALID, "width/height out of range [1, 63]");
+  if (c->max_berries_per_bush < 0 || c->max_berries_per_bush > 255)
+    return fail(WAB_E_INVALID, "max_berries_per_bush must be in [0, 255]");
+  *slots = resolved_wolf_slots(c);
+  if (*slots != 8 && *slots != 16 && *slots != 32) return fail(WAB_E_INVALID, "wolf_slots must be 8, 16 or 32");
+  *cap = resolved_eaten_capacity(c);
+  if (*cap > 255) return fail(WAB_E_INVALID, "eaten_capacity must be <= 255");
+  return WAB_OK;
+}
+
 // the geometry a record depends on; false (with the message set) for options wab_create refuses
 bool snapshot_dims(const wab_config* c, int* slots, int* cap, int* whw) {
   if (!c) return fail(WAB_E_INVALID, "wab_snapshot: NULL config"), false;
-  if (c->width % 2 == 0 || c->height % 2 == 0)
-    return fail(WAB_E_INVALID, "width and height must be odd numbers"), false;
-  if (c->width < 1 || c->height < 1 || c->width > WAB_MAX_VIEW || c->height > WAB_MAX_VIEW)
-    return fail(WAB_E_INVALID, "width/height out of range [1, 63]"), false;
-  *slots = resolved_wolf_slots(c);
-  if (*slots != 8 && *slots != 16 && *slots != 32)
-    return fail(WAB_E_INVALID, "wolf_slots must be 8, 16 or 32"), false;
-  *cap = resolved_eaten_capacity(c);
-  if (*cap > 255) return fail(WAB_E_INVALID, "eaten_capacity must be <= 255"), false;
-  if (c->max_berries_per_bush < 0 || c->max_berries_per_bush > 255)
-    return fail(WAB_E_INVALID, "max_berries_per_bush must be in [0, 255]"), false;
+  if (check_dims(c, slots, cap) != WAB_OK) return false;
   *whw = (c->width * c->height + 31) / 32;
   return true;
 }
@@ -223,37 +141,6 @@ uint32_t row_mask(const char* s) {
   return m;
 }
 
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-template <int MODE, bool SMALL>
-void* kernel_ptr(int slots) {
-  switch (slots) {
-    case 8: return reinterpret_cast<void*>(&wab::wab_kernel<MODE, 8, SMALL>);
-    case 16: return reinterpret_cast<void*>(&wab::wab_kernel<MODE, 16, SMALL>);
-    default: return reinterpret_cast<void*>(&wab::wab_kernel<MODE, 32, SMALL>);
-  }
-}
-
-template <int MODE, bool SMALL>
-void launch_as(wab_handle* h, const Params& p, hipStream_t stream) {
-  const dim3 grid(h->n_blocks), block(wab::kThreads);
-  switch (h->slots) {
-    case 8: hipLaunchKernelGGL((wab::wab_kernel<MODE, 8, SMALL>), grid, block, h->lds_bytes, stream, p); break;
-    case 16: hipLaunchKernelGGL((wab::wab_kernel<MODE, 16, SMALL>), grid, block, h->lds_bytes, stream, p); break;
-    default: hipLaunchKernelGGL((wab::wab_kernel<MODE, 32, SMALL>), grid, block, h->lds_bytes, stream, p); break;
-  }
-}
-
 // SMALL: the W*H-bit view bitmap fits 4 registers (default 11x11 = 121 bits)
 bool small_map(const Params& p) { return p.WHW <= 4; }
 
@@ -262,8 +149,7 @@ bool small_map(const Params& p) { return p.WHW <= 4; }
 // at exactly 11x11) step with the four-wave small-view kernel (wab_step_small.hip); other
 // views of width <= 31 and height <= 32 in rows of 16 or 32 bytes without restrict_view step
 // and reset with the wide-view kernel (wab_step_wide.hip, its own bitmap layout: one dword per
-// row).
-enum { KERNEL_BLOCK = 0, KERNEL_SMALL = 1, KERNEL_WIDE = 2 };
+// row).  (KERNEL_BLOCK / KERNEL_SMALL / KERNEL_WIDE, wab_host.h)
 
 // (W, H >= 3: the strip that scrolls into view, drawn on another wave, never holds the
 // ostrich's tile; W, H <= 32: its bits are one dword)
@@ -282,12 +168,29 @@ bool wide_view(const Params& p) {
          wab::wide_roll_layout(p).total * 4u <= 64u * 1024u;
 }
 
+// Which instance runs: one function per kernel family, each the only place that names the
+// family's instances.  What it returns is both raised (raise_lds, wab_create) and launched
+// (launch_params), so the two cannot disagree.
+template <int MODE, bool SMALL>
+const void* block_instance(int slots) {
+  switch (slots) {
+    case 8: return reinterpret_cast<const void*>(&wab::wab_kernel<MODE, 8, SMALL>);
+    case 16: return reinterpret_cast<const void*>(&wab::wab_kernel<MODE, 16, SMALL>);
+    default: return reinterpret_cast<const void*>(&wab::wab_kernel<MODE, 32, SMALL>);
+  }
+}
+// the block kernel: mode 0 steps, 1 resets
+const void* block_kernel(int mode, int slots, bool small) {
+  if (mode) return small ? block_instance<1, true>(slots) : block_instance<1, false>(slots);
+  return small ? block_instance<0, true>(slots) : block_instance<0, false>(slots);
+}
+
 // the wide kernel holds kWideRegSlots wolves per env in registers whatever wolf_slots is; a lane
 // with more works on the rest (rows kWideRegSlots..wolf_slots-1) from HBM (a rare path)
 constexpr int kWideRegSlots = 8;
-template <int MODE>
-void* wide_kernel_ptr(int) {
-  return reinterpret_cast<void*>(&wab::wab_step_wide<MODE, kWideRegSlots>);
+const void* wide_kernel(int mode) {
+  return mode ? reinterpret_cast<const void*>(&wab::wab_step_wide<1, kWideRegSlots>)
+              : reinterpret_cast<const void*>(&wab::wab_step_wide<0, kWideRegSlots>);
 }
 
 // the wide rollout build: C3's geometry (31 x 31 in 32-byte rows) has an instance with it as
@@ -296,68 +199,65 @@ bool wide_fixed31(const Params& p) {
   return p.W == 31 && p.H == 31 && p.S == 32 && p.cw == 15 && p.ch == 15 && p.OB == 3 * 31 * 32 && p.WH == 961 &&
          p.SL == 31;
 }
-void* wide_roll_kernel(const Params& p) {
-  return wide_fixed31(p) ? reinterpret_cast<void*>(&wab::wab_rollout_wide<kWideRegSlots, 31>)
-                         : reinterpret_cast<void*>(&wab::wab_rollout_wide<kWideRegSlots, 0>);
-}
-void launch_rollout_wide(int n_blocks, size_t lds, const Params& p, hipStream_t stream) {
-  if (wide_fixed31(p))
-    hipLaunchKernelGGL((wab::wab_rollout_wide<kWideRegSlots, 31>), dim3(n_blocks), dim3(256), lds, stream, p);
-  else
-    hipLaunchKernelGGL((wab::wab_rollout_wide<kWideRegSlots, 0>), dim3(n_blocks), dim3(256), lds, stream, p);
+const void* wide_roll_kernel(const Params& p) {
+  return wide_fixed31(p) ? reinterpret_cast<const void*>(&wab::wab_rollout_wide<kWideRegSlots, 31>)
+                         : reinterpret_cast<const void*>(&wab::wab_rollout_wide<kWideRegSlots, 0>);
 }
 
-template <int G, bool ROLL = false>
-void* small_kernel_ptr(int slots, bool rules = false) {
+// FEAT: the featurizer fused in (wab_step_features); ROLL: the multi-step build (Params::n_steps
+// steps per launch, wab_rollout); POLICY: the device policy between the steps (wab_rollout_policy)
+template <int SLOTS, int G, bool RULES>
+const void* small_instance(bool feat, bool roll, bool policy) {
+  if constexpr (SLOTS == 8 && G == 11)
+    if (policy) return reinterpret_cast<const void*>(&wab::wab_step_small<8, 11, true, true, RULES, true>);
+  if (feat)
+    return roll ? reinterpret_cast<const void*>(&wab::wab_step_small<SLOTS, G, true, true, RULES>)
+                : reinterpret_cast<const void*>(&wab::wab_step_small<SLOTS, G, true, false, RULES>);
+  return roll ? reinterpret_cast<const void*>(&wab::wab_step_small<SLOTS, G, false, true, RULES>)
+              : reinterpret_cast<const void*>(&wab::wab_step_small<SLOTS, G, false, false, RULES>);
+}
+
+}  // namespace
+
+const void* wab_host::small_kernel(int slots, bool g11, bool rules, bool feat, bool roll, bool policy) {
 #if WAB_RULES_INSTANCE
-  if constexpr (G == 11)
-    if (slots == 8 && rules) return reinterpret_cast<void*>(&wab::wab_step_small<8, 11, false, ROLL, true>);
+  if (g11 && slots == 8 && rules) return small_instance<8, 11, true>(feat, roll, policy);
 #endif
   switch (slots) {
-    case 8: return reinterpret_cast<void*>(&wab::wab_step_small<8, G, false, ROLL>);
-    case 16: return reinterpret_cast<void*>(&wab::wab_step_small<16, G, false, ROLL>);
-    default: return reinterpret_cast<void*>(&wab::wab_step_small<32, G, false, ROLL>);
+    case 8: return g11 ? small_instance<8, 11, false>(feat, roll, policy) : small_instance<8, 0, false>(feat, roll, policy);
+    case 16: return g11 ? small_instance<16, 11, false>(feat, roll, policy) : small_instance<16, 0, false>(feat, roll, policy);
+    default: return g11 ? small_instance<32, 11, false>(feat, roll, policy) : small_instance<32, 0, false>(feat, roll, policy);
   }
 }
 
-// ROLL: the multi-step build (Params::n_steps steps per launch, wab_rollout)
-template <int G, bool FEAT = false, bool ROLL = false>
-void launch_small(wab_handle* h, const Params& p, hipStream_t stream, size_t lds_bytes = 0) {
-  const dim3 grid(h->n_blocks), block(256);  // one 64-env group per workgroup, four waves
-  const size_t lds = lds_bytes ? lds_bytes : FEAT ? h->small_feat_lds_bytes : h->small_lds_bytes;
-#if WAB_RULES_INSTANCE
-  if constexpr (G == 11) {
-    if (h->small_rules) {  // (8 slots, default_rules)
-      hipLaunchKernelGGL((wab::wab_step_small<8, 11, FEAT, ROLL, true>), grid, block, lds, stream, p);
-      return;
-    }
-  }
-#endif
-  switch (h->slots) {
-    case 8: hipLaunchKernelGGL((wab::wab_step_small<8, G, FEAT, ROLL>), grid, block, lds, stream, p); break;
-    case 16: hipLaunchKernelGGL((wab::wab_step_small<16, G, FEAT, ROLL>), grid, block, lds, stream, p); break;
-    default: hipLaunchKernelGGL((wab::wab_step_small<32, G, FEAT, ROLL>), grid, block, lds, stream, p); break;
-  }
-}
+namespace {
 
-template <int MODE>
-int launch(wab_handle* h, const Params& p, hipStream_t stream) {
+// The step (mode 0; p.n_steps of them in one launch) or reset (mode 1) of a handle.
+int launch(wab_handle* h, int mode, const Params& p, hipStream_t stream) {
   if (h->n_blocks == 0) return WAB_OK;
-  if (h->step_kernel == KERNEL_WIDE) {
-    const dim3 grid(h->n_blocks), block(256);  // one 64-env group per workgroup, four waves
-    const size_t lds = h->wide_lds_bytes;
-    hipLaunchKernelGGL((wab::wab_step_wide<MODE, kWideRegSlots>), grid, block, lds, stream, p);
-  } else if (MODE == 0 && h->step_kernel == KERNEL_SMALL) {
-    if (p.n_steps > 1) {
-      if (h->small_g11) launch_small<11, false, true>(h, p, stream);
-      else launch_small<0, false, true>(h, p, stream);
-    } else if (h->small_g11) {
-      launch_small<11>(h, p, stream);
-    } else {
-      launch_small<0>(h, p, stream);
-    }
-  } else if (small_map(p)) launch_as<MODE, true>(h, p, stream);
-  else launch_as<MODE, false>(h, p, stream);
+  // (every family: one 64-env group per workgroup, four waves)
+  static_assert(wab::kThreads == 256, "launch_params launches workgroups of 256");
+  if (h->step_kernel == KERNEL_WIDE)
+    launch_params(wide_kernel(mode), (unsigned)h->n_blocks, h->wide_lds_bytes, stream, p);
+  else if (mode == 0 && h->step_kernel == KERNEL_SMALL)
+    launch_params(small_kernel(h, false, p.n_steps > 1), (unsigned)h->n_blocks, h->small_lds_bytes, stream, p);
+  else
+    launch_params(block_kernel(mode, h->slots, small_map(p)), (unsigned)h->n_blocks, h->lds_bytes, stream, p);
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+// the wide kernel's rollout build: p.n_steps steps in one launch
+int launch_wide_roll(wab_handle* h, const Params& p, hipStream_t stream) {
+  if (h->n_blocks == 0) return WAB_OK;
+  launch_params(wide_roll_kernel(p), (unsigned)h->n_blocks, h->wide_roll_lds_bytes, stream, p);
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+// the small kernel with the featurizer fused in: one step, or p.n_steps of them with `lds` bytes
+int launch_small_features(wab_handle* h, const Params& p, bool roll, size_t lds, hipStream_t stream) {
+  launch_params(small_kernel(h, true, roll), (unsigned)h->n_blocks, lds, stream, p);
   HIP_TRY(hipGetLastError());
   return WAB_OK;
 }
@@ -516,8 +416,6 @@ bool default_rules(const Params& p) {
 #undef WAB_SAME
 }
 
-bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
-
 // flattened PragmaticObsWrapper length, or WAB_E_INVALID when bushes[md//2, md//2] (wab_env.py:742)
 // is outside the grid
 int feature_dim_of(const Params& p) {
@@ -537,126 +435,6 @@ bool feat_small_ok(const Params& p) {
   return p.W * p.H <= 128 && p.S == p.H && max_dist < md;
 }
 
-// the discounted-return scan: VEC envs per thread, the widest whose grid still gives each of
-// the 1024 SIMDs a 64-thread wave and whose rows stay aligned; the reward table reduced to the
-// entries whose float32 is not the double itself (the others convert exactly)
-// The choice is made here alone, on the host, and launches nothing: launch_returns runs what
-// this returns and wab_debug_returns_plan reports it.
-struct ReturnsPlan {
-  int vec, ne;               // the instance wab_returns_kernel<vec, ne>
-  wab::RewardTable inexact;  // its table: the inexact entries, padded to ne
-};
-
-// the entries of `tab` whose float32 is not the double itself, and the NE instance that holds
-// them (0..4, or 8), padded to it with copies of entry 0 (same key, same value)
-wab::RewardTable inexact_rewards(const wab::RewardTable& tab, int* ne) {
-  wab::RewardTable inexact;
-  std::memset(&inexact, 0, sizeof(inexact));
-  for (int k = 0; k < tab.n; ++k) {
-    float f;
-    std::memcpy(&f, &tab.f32[k], 4);
-    if ((double)f != tab.f64[k]) {
-      inexact.f32[inexact.n] = tab.f32[k];
-      inexact.f64[inexact.n] = tab.f64[k];
-      inexact.n++;
-    }
-  }
-  *ne = inexact.n <= 4 ? inexact.n : 8;
-  for (int k = inexact.n; k < *ne; ++k) {
-    inexact.f32[k] = inexact.f32[0];
-    inexact.f64[k] = inexact.f64[0];
-  }
-  return inexact;
-}
-
-ReturnsPlan returns_plan(const float* reward, const uint8_t* done, const float* returns, int64_t B,
-                         const wab::RewardTable& tab) {
-  ReturnsPlan plan;
-  plan.inexact = inexact_rewards(tab, &plan.ne);
-  const auto fits = [&](int v) {
-    const uintptr_t a = 4u * (uintptr_t)v - 1u;
-    return B % v == 0 && B / v >= 64 * 1024 && ((uintptr_t)reward & a) == 0 && ((uintptr_t)returns & a) == 0 &&
-           ((uintptr_t)done & (uintptr_t)(v - 1)) == 0;
-  };
-  plan.vec = fits(4) ? 4 : fits(2) ? 2 : 1;
-  return plan;
-}
-
-int launch_returns(const float* reward, const uint8_t* done, int32_t T, int64_t B, double gamma,
-                   const float* bootstrap, float* returns, const wab::RewardTable& tab, void* stream) {
-  const ReturnsPlan plan = returns_plan(reward, done, returns, B, tab);
-  const int vec = plan.vec, ne = plan.ne;
-  const wab::RewardTable& inexact = plan.inexact;
-  const dim3 grid((unsigned)((B / vec + 63) / 64));
-  hipStream_t s = (hipStream_t)stream;
-#define WAB_RET(V, N) \
-  hipLaunchKernelGGL((wab::wab_returns_kernel<V, N>), grid, dim3(64), 0, s, reward, done, T, B, gamma, bootstrap, returns, inexact)
-#define WAB_RET_NE(V) \
-  switch (ne) {                                                                                                   \
-    case 0: WAB_RET(V, 0); break;                                                                                 \
-    case 1: WAB_RET(V, 1); break;                                                                                 \
-    case 2: WAB_RET(V, 2); break;                                                                                 \
-    case 3: WAB_RET(V, 3); break;                                                                                 \
-    case 4: WAB_RET(V, 4); break;                                                                                 \
-    default: WAB_RET(V, 8);                                                                                       \
-  }
-  if (vec == 4) { WAB_RET_NE(4) }
-  else if (vec == 2) { WAB_RET_NE(2) }
-  else { WAB_RET_NE(1) }
-#undef WAB_RET_NE
-#undef WAB_RET
-  HIP_TRY(hipGetLastError());
-  return WAB_OK;
-}
-
-// the GAE scan (wab_gae_kernel<vec, ne>, wab_advantage.hip): 2 envs per thread where B is even,
-// B / 2 still gives each of the 1024 SIMDs a 64-thread wave, every float row is 8-byte aligned
-// and done 2-byte aligned, else 1 (there is no VEC 4: a chunk's registers would not fit); the
-// table as in returns_plan.  launch_gae runs what this returns, wab_debug_gae_plan reports it.
-ReturnsPlan gae_plan(const float* reward, const uint8_t* done, const float* value, const float* advantage,
-                     const float* target, int64_t B, const wab::RewardTable& tab) {
-  ReturnsPlan plan;
-  plan.inexact = inexact_rewards(tab, &plan.ne);
-  const uintptr_t rows = (uintptr_t)reward | (uintptr_t)value | (uintptr_t)advantage | (uintptr_t)target;  // (NULL: 0)
-  plan.vec = B % 2 == 0 && B / 2 >= 64 * 1024 && (rows & 7u) == 0 && ((uintptr_t)done & 1u) == 0 ? 2 : 1;
-  return plan;
-}
-
-int launch_gae(const float* reward, const uint8_t* done, const float* value, const float* last_value, int32_t T,
-               int64_t B, double gamma, double lambda, float* advantage, float* target, const wab::RewardTable& tab,
-               void* stream) {
-  const ReturnsPlan plan = gae_plan(reward, done, value, advantage, target, B, tab);
-  const int vec = plan.vec, ne = plan.ne;
-  const wab::RewardTable& inexact = plan.inexact;
-  const double gl = gamma * lambda;
-  const dim3 grid((unsigned)((B / vec + 63) / 64));
-  hipStream_t s = (hipStream_t)stream;
-#define WAB_GAE(V, N)                                                                                              \
-  hipLaunchKernelGGL((wab::wab_gae_kernel<V, N>), grid, dim3(64), 0, s, reward, done, value, last_value, T, B, gamma, \
-                     gl, advantage, target, inexact)
-#define WAB_GAE_NE(V)            \
-  switch (ne) {                  \
-    case 0: WAB_GAE(V, 0); break; \
-    case 1: WAB_GAE(V, 1); break; \
-    case 2: WAB_GAE(V, 2); break; \
-    case 3: WAB_GAE(V, 3); break; \
-    case 4: WAB_GAE(V, 4); break; \
-    default: WAB_GAE(V, 8);       \
-  }
-  if (vec == 2) { WAB_GAE_NE(2) }
-  else { WAB_GAE_NE(1) }
-#undef WAB_GAE_NE
-#undef WAB_GAE
-  HIP_TRY(hipGetLastError());
-  return WAB_OK;
-}
-
-// [a, a + na) and [b, b + nb) share a byte (a NULL range shares none)
-bool ranges_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return a && b && na && nb && pa < pb + nb && pb < pa + na;
-}
-
 // a handle-owned [B] obs planes buffer (16-byte aligned), allocated by the first call that needs it
 uint8_t* scratch_planes(wab_handle* h) {
   if (!h->scratch_planes) {
@@ -670,58 +448,6 @@ uint8_t* scratch_planes(wab_handle* h) {
   return h->scratch_planes;
 }
 
-// a handle-owned pair of [B][F] feature rows (16-byte aligned), allocated by the first call that needs it
-float* bounce_rows(wab_handle* h, size_t row_floats) {
-  if (!h->bounce_rows) {
-    DeviceGuard guard(h->device);
-    void* ptr = nullptr;
-    if (hipMalloc(&ptr, std::max<size_t>(16, 2u * ((row_floats + 3u) & ~(size_t)3u) * 4u)) != hipSuccess) return nullptr;
-    h->allocs.push_back(ptr);
-    h->bounce_rows = static_cast<float*>(ptr);
-  }
-  return h->bounce_rows;
-}
-
-// which wab_policy_kernel instance a net takes: <true> for h1 > 128, two layer-1 tiles per wave
-bool policy_two_tiles(const wab::PolicyDims& d) { return d.NT1 > 4; }
-
-// wab_rollout_policy as one launch: the POLICY instances of the small kernel (8 slots, 11x11)
-void* roll_policy_kernel(bool rules) {
-#if WAB_RULES_INSTANCE
-  if (rules) return reinterpret_cast<void*>(&wab::wab_step_small<8, 11, true, true, true, true>);
-#endif
-  return reinterpret_cast<void*>(&wab::wab_step_small<8, 11, true, true, false, true>);
-}
-
-// Whether (h, p) takes the one-launch path, and its LDS for T steps (returns scanned in the
-// launch or not).  The answer does not depend on T: the limit is tested with the longest
-// in-launch returns scan's reward codes.
-bool roll_policy_plan(const wab_handle* h, const wab_policy* p, int32_t T, bool fused_returns, wab::RollPolicy* out,
-                      std::string* why) {
-  const auto no = [&](const char* msg) {
-    if (why) *why = msg;
-    return false;
-  };
-  if (h->step_kernel != KERNEL_SMALL || !h->small_g11 || h->slots != 8 || !h->small_feat_lds_bytes)
-    return no("the one-launch kernel is built for the 11x11 small-view kernel with 8 wolf slots and the fused "
-              "featurizer");
-  const int F = wab_feature_dim(h);
-  if (F < 0 || p->dims.F != F) return no("the policy's in_features is not the handle's feature length");
-  if (((size_t)h->p.B * (size_t)F) % 4u != 0) return no("batch * feature_dim is not a multiple of 4");
-  Params q = h->p;
-  q.features = reinterpret_cast<float*>(16);  // (layout only)
-  q.returns = reinterpret_cast<float*>(16);
-  q.n_steps = wab::kMaxFusedReturnSteps;
-  if (wab::roll_policy_lds(p->dims, wab::small_layout(q).total * 4u).total > h->lds_max)
-    return no("the kernel's LDS exceeds the device's limit per workgroup");
-  if (out) {
-    q.n_steps = T;
-    if (!fused_returns) q.returns = nullptr;
-    *out = wab::roll_policy_lds(p->dims, wab::small_layout(q).total * 4u);
-  }
-  return true;
-}
-
 int check_obs(const wab_obs* o, const char* what) {
   if (!o || !o->planes || !o->food_turns || !o->role || !o->status)
     return fail(WAB_E_INVALID, std::string(what) + ": every wab_obs pointer must be set");
@@ -730,6 +456,25 @@ int check_obs(const wab_obs* o, const char* what) {
 }
 
 }  // namespace
+
+int wab_host::obs_slice(wab_handle* h, const wab_obs* obs_seq, int32_t t, const char* what, ObsSlice* s) {
+  const size_t tb = (size_t)t * (size_t)h->p.B;
+  s->dst = obs_seq->planes ? obs_seq->planes + tb * (size_t)h->p.OB : nullptr;
+  s->o.planes = !s->dst || aligned16(s->dst) ? s->dst : scratch_planes(h);
+  if (s->dst && !s->o.planes) return fail(WAB_E_NOMEM, std::string(what) + ": hipMalloc");
+  s->o.food_turns = obs_seq->food_turns + tb;
+  s->o.role = obs_seq->role + tb;
+  s->o.status = obs_seq->status + tb;
+  return WAB_OK;
+}
+
+int wab_host::obs_slice_done(wab_handle* h, const ObsSlice& s, void* stream) {
+  if (s.o.planes == s.dst) return WAB_OK;
+  DeviceGuard guard(h->device);
+  HIP_TRY(hipMemcpyAsync(s.dst, s.o.planes, (size_t)h->p.B * (size_t)h->p.OB, hipMemcpyDeviceToDevice,
+                         (hipStream_t)stream));
+  return WAB_OK;
+}
 
 extern "C" {
 
@@ -787,15 +532,11 @@ int wab_create(const wab_config* c, int64_t batch, uint64_t seed, int64_t env_id
   g_err.clear();
   if (!c || !out) return fail(WAB_E_INVALID, "wab_create: NULL argument");
   *out = nullptr;
-  // --- validation (wab_env.py:147-148 and the limits of this implementation)
-  if (c->width % 2 == 0 || c->height % 2 == 0)
-    return fail(WAB_E_INVALID, "width and height must be odd numbers");
-  if (c->width < 1 || c->height < 1 || c->width > WAB_MAX_VIEW || c->height > WAB_MAX_VIEW)
-    return fail(WAB_E_INVALID, "width/height out of range [1, 63]");
+  // --- validation (check_dims, and what only a handle is refused for)
+  int slots, cap;
+  if (int rc = check_dims(c, &slots, &cap)) return rc;
   if (c->restrict_view && (c->width < 11 || c->height < 11))
     return fail(WAB_E_INVALID, "restrict_view needs width, height >= 11 (11x11 masks, wab_env.py:354)");
-  if (c->max_berries_per_bush < 0 || c->max_berries_per_bush > 255)
-    return fail(WAB_E_INVALID, "max_berries_per_bush must be in [0, 255]");
   if (!(c->bush_power >= 0.0) || !std::isfinite(c->bush_power))
     return fail(WAB_E_INVALID, "bush_power must be a finite number >= 0");
   if (c->turns_to_fill_food <= 0 || c->turns_to_empty_food <= 0)
@@ -804,12 +545,8 @@ int wab_create(const wab_config* c, int64_t batch, uint64_t seed, int64_t env_id
   if (c->wolf_spawn_margin < 0 || c->width / 2 + c->wolf_spawn_margin > 120 ||
       c->height / 2 + c->wolf_spawn_margin > 120)
     return fail(WAB_E_INVALID, "wolf_spawn_margin out of range");
-  const int slots = resolved_wolf_slots(c);
-  if (slots != 8 && slots != 16 && slots != 32) return fail(WAB_E_INVALID, "wolf_slots must be 8, 16 or 32");
   const int S = c->plane_stride > 0 ? c->plane_stride : c->height;
   if (S < c->height || S > 64) return fail(WAB_E_INVALID, "plane_stride must be in [height, 64]");
-  const int cap = resolved_eaten_capacity(c);
-  if (cap > 255) return fail(WAB_E_INVALID, "eaten_capacity must be <= 255");
   if (batch < 0) return fail(WAB_E_INVALID, "batch must be >= 0");
 
   wab_handle* h = new wab_handle();
@@ -966,25 +703,19 @@ int wab_create(const wab_config* c, int64_t batch, uint64_t seed, int64_t env_id
   }
   if (e == hipSuccess) e = hipMemset(p.counters, 0, wab::kNumCounters * 8);
   if (e == hipSuccess) e = hipMemset(p.block_resets, 0, (size_t)(h->n_blocks > 0 ? h->n_blocks : 1) * 8);
-  for (void* k : {kernel_ptr<0, true>(slots), kernel_ptr<1, true>(slots), kernel_ptr<0, false>(slots),
-                  kernel_ptr<1, false>(slots)})
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
+  // the dynamic LDS of the instances launch() takes for this handle (raise_lds: where above 64 KB)
+  const auto raise = [&](const void* kernel, size_t bytes) {
+    if (e == hipSuccess) e = raise_lds(device, kernel, bytes);
+  };
+  for (int mode : {0, 1}) raise(block_kernel(mode, slots, small_map(p)), h->lds_bytes);
   if (h->step_kernel == KERNEL_WIDE) {
     h->wide_lds_bytes = (size_t)wab::wide_layout(p).total * 4u;
     h->wide_roll_lds_bytes = (size_t)wab::wide_roll_layout(p).total * 4u;
-    for (void* k : {wide_kernel_ptr<0>(slots), wide_kernel_ptr<1>(slots)})
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->wide_lds_bytes);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(wide_roll_kernel(p), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)h->wide_roll_lds_bytes);
+    for (int mode : {0, 1}) raise(wide_kernel(mode), h->wide_lds_bytes);
+    raise(wide_roll_kernel(p), h->wide_roll_lds_bytes);
   }
-  if (e == hipSuccess && h->step_kernel == KERNEL_SMALL)
-    for (void* k : {h->small_g11 ? small_kernel_ptr<11>(slots, h->small_rules) : small_kernel_ptr<0>(slots),
-                    h->small_g11 ? small_kernel_ptr<11, true>(slots, h->small_rules) : small_kernel_ptr<0, true>(slots)})
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->small_lds_bytes);
+  if (h->step_kernel == KERNEL_SMALL)
+    for (bool roll : {false, true}) raise(small_kernel(h, false, roll), h->small_lds_bytes);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
     std::string msg = std::string("wab_create: ") + hipGetErrorString(e);
@@ -1014,12 +745,9 @@ int wab_reset(wab_handle* h, const uint8_t* mask, const wab_obs* obs, void* stre
     return fail(WAB_E_STATE, "wab_reset: the first reset must cover every env (mask = NULL)");
   Params p = h->p;
   p.reset_mask = mask;
-  p.planes = obs->planes;
-  p.food_turns = obs->food_turns;
-  p.role = obs->role;
-  p.status = obs->status;
+  bind_obs(p, obs);
   DeviceGuard guard(h->device);
-  int rc = launch<1>(h, p, (hipStream_t)stream);
+  int rc = launch(h, 1, p, (hipStream_t)stream);
   if (rc == WAB_OK && !mask) h->reset_done = true;
   return rc;
 }
@@ -1033,13 +761,8 @@ int wab_step(wab_handle* h, const int8_t* actions, const wab_obs* obs, float* re
   if (!actions || !reward || !done) return fail(WAB_E_INVALID, "wab_step: NULL actions/reward/done");
   if (int rc = check_obs(obs, "wab_step")) return rc;
   Params p = h->p;
-  p.actions = actions;
-  p.planes = obs->planes;
-  p.food_turns = obs->food_turns;
-  p.role = obs->role;
-  p.status = obs->status;
-  p.reward = reward;
-  p.done = done;
+  bind_obs(p, obs);
+  bind_step(p, actions, reward, done);
   if (terminal && terminal->planes) {
     if (int rc = check_obs(terminal, "wab_step(terminal)")) return rc;
     p.t_planes = terminal->planes;
@@ -1058,13 +781,10 @@ int wab_step(wab_handle* h, const int8_t* actions, const wab_obs* obs, float* re
     // is final (a line at a plane or env boundary in two parts, merged on die).  Measured at
     // B = 65536 (C3): into a 32-slot ring 52.0 against 73.1 us (round 3's per-step kernel), into
     // one buffer 62.5 against 45.9 us.  The results are the same either way.
-    if (h->n_blocks == 0) return WAB_OK;
     p.n_steps = 1;
-    launch_rollout_wide(h->n_blocks, h->wide_roll_lds_bytes, p, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return WAB_OK;
+    return launch_wide_roll(h, p, (hipStream_t)stream);
   }
-  return launch<0>(h, p, (hipStream_t)stream);
+  return launch(h, 0, p, (hipStream_t)stream);
 }
 
 int wab_rollout(wab_handle* h, const int8_t* actions, int32_t T, const wab_obs* obs_seq, float* reward,
@@ -1080,42 +800,20 @@ int wab_rollout(wab_handle* h, const int8_t* actions, int32_t T, const wab_obs* 
       ((size_t)B * OB) % 16u == 0) {  // (every step's planes 16-byte aligned)
     // one launch: each workgroup runs its 64 envs through the T steps (Params::n_steps)
     Params p = h->p;
-    p.actions = actions;
-    p.planes = obs_seq->planes;
-    p.food_turns = obs_seq->food_turns;
-    p.role = obs_seq->role;
-    p.status = obs_seq->status;
-    p.reward = reward;
-    p.done = done;
+    bind_obs(p, obs_seq);
+    bind_step(p, actions, reward, done);
     p.n_steps = T;
     DeviceGuard guard(h->device);
     ++h->rollout_launches;
-    if (h->step_kernel == KERNEL_WIDE) {
-      if (h->n_blocks == 0) return WAB_OK;
-      launch_rollout_wide(h->n_blocks, h->wide_roll_lds_bytes, p, (hipStream_t)stream);
-      HIP_TRY(hipGetLastError());
-      return WAB_OK;
-    }
-    return launch<0>(h, p, (hipStream_t)stream);
+    return wide_roll ? launch_wide_roll(h, p, (hipStream_t)stream) : launch(h, 0, p, (hipStream_t)stream);
   }
   if (T > 0) ++h->rollout_step_calls;
   for (int32_t t = 0; t < T; ++t) {
-    wab_obs o;
-    uint8_t* dst = obs_seq->planes + (size_t)t * (size_t)B * OB;
-    // (a step slice that is not 16-byte aligned, B * OB % 16 != 0: the step writes a handle-owned
-    // buffer, copied to the slice on the stream; the first such call allocates it)
-    o.planes = aligned16(dst) ? dst : scratch_planes(h);
-    if (!o.planes) return fail(WAB_E_NOMEM, "wab_rollout: hipMalloc");
-    o.food_turns = obs_seq->food_turns + (size_t)t * (size_t)B;
-    o.role = obs_seq->role + (size_t)t * (size_t)B;
-    o.status = obs_seq->status + (size_t)t * (size_t)B;
-    int rc = wab_step(h, actions + (size_t)t * (size_t)B, &o, reward + (size_t)t * (size_t)B,
-                      done + (size_t)t * (size_t)B, nullptr, stream);
-    if (rc != WAB_OK) return rc;
-    if (o.planes != dst) {
-      DeviceGuard guard(h->device);
-      HIP_TRY(hipMemcpyAsync(dst, o.planes, (size_t)B * OB, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    }
+    const size_t tb = (size_t)t * (size_t)B;
+    ObsSlice s;
+    if (int rc = obs_slice(h, obs_seq, t, "wab_rollout", &s)) return rc;
+    if (int rc = wab_step(h, actions + tb, &s.o, reward + tb, done + tb, nullptr, stream)) return rc;
+    if (int rc = obs_slice_done(h, s, stream)) return rc;
   }
   return WAB_OK;
 }
@@ -1216,9 +914,7 @@ int featurize(wab_handle* h, int kind, const wab_obs* obs, const uint8_t* view_m
     return WAB_OK;
   }
   const size_t lds = (size_t)(((inW + 3) & ~3u) + outW) * 4;
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<void*>(&wab::wab_featurize_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(raise_lds(h->device, reinterpret_cast<const void*>(&wab::wab_featurize_kernel), lds));
   hipLaunchKernelGGL(wab::wab_featurize_kernel, dim3(h->n_blocks), dim3(256), lds, (hipStream_t)stream, fp);
   HIP_TRY(hipGetLastError());
   return WAB_OK;
@@ -1253,20 +949,12 @@ int wab_step_features(wab_handle* h, const int8_t* actions, const wab_obs* obs, 
     return wab_featurize(h, &o, nullptr, features, stream);
   }
   Params p = h->p;
-  p.actions = actions;
-  p.planes = obs->planes;
-  p.food_turns = obs->food_turns;
-  p.role = obs->role;
-  p.status = obs->status;
-  p.reward = reward;
-  p.done = done;
+  bind_obs(p, obs);
+  bind_step(p, actions, reward, done);
   p.features = features;
   if (h->n_blocks == 0) return WAB_OK;
   DeviceGuard guard(h->device);
-  if (h->small_g11) launch_small<11, true>(h, p, (hipStream_t)stream);
-  else launch_small<0, true>(h, p, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return WAB_OK;
+  return launch_small_features(h, p, false, h->small_feat_lds_bytes, (hipStream_t)stream);
 }
 
 int wab_rollout_features(wab_handle* h, const int8_t* actions, int32_t T, const wab_obs* obs_seq, float* reward,
@@ -1307,13 +995,8 @@ int wab_rollout_features(wab_handle* h, const int8_t* actions, int32_t T, const 
     // one launch: each workgroup runs its 64 envs through the T steps with the featurizer fused
     // (wab_step_small<.., FEAT, ROLL>), the returns of the segment at its end
     Params p = h->p;
-    p.actions = actions;
-    p.planes = obs_seq->planes;
-    p.food_turns = obs_seq->food_turns;
-    p.role = obs_seq->role;
-    p.status = obs_seq->status;
-    p.reward = reward;
-    p.done = done;
+    bind_obs(p, obs_seq);
+    bind_step(p, actions, reward, done);
     p.features = features;
     p.n_steps = T;
     if (fused_returns) {
@@ -1323,31 +1006,17 @@ int wab_rollout_features(wab_handle* h, const int8_t* actions, int32_t T, const 
     }
     DeviceGuard guard(h->device);
     ++h->rollout_launches;
-    if (h->small_g11) launch_small<11, true, true>(h, p, (hipStream_t)stream, roll_lds);
-    else launch_small<0, true, true>(h, p, (hipStream_t)stream, roll_lds);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_small_features(h, p, true, roll_lds, (hipStream_t)stream)) return rc;
     if (fused_returns) return WAB_OK;
   } else {
     ++h->rollout_step_calls;
     for (int32_t t = 0; t < T; ++t) {  // (no fused kernel for these options: T fused-or-not steps)
-      wab_obs o;
-      o.planes = obs_seq->planes ? obs_seq->planes + (size_t)t * (size_t)B * OB : nullptr;
-      uint8_t* dst = o.planes;
-      if (dst && !aligned16(dst)) {  // (as in wab_rollout: through the handle's buffer)
-        o.planes = scratch_planes(h);
-        if (!o.planes) return fail(WAB_E_NOMEM, "wab_rollout_features: hipMalloc");
-      }
-      o.food_turns = obs_seq->food_turns + (size_t)t * (size_t)B;
-      o.role = obs_seq->role + (size_t)t * (size_t)B;
-      o.status = obs_seq->status + (size_t)t * (size_t)B;
-      int rc = wab_step_features(h, actions + (size_t)t * (size_t)B, &o, reward + (size_t)t * (size_t)B,
-                                 done + (size_t)t * (size_t)B, features + (size_t)t * (size_t)B * (size_t)F,
-                                 stream);
-      if (rc != WAB_OK) return rc;
-      if (dst && o.planes != dst) {
-        DeviceGuard guard(h->device);
-        HIP_TRY(hipMemcpyAsync(dst, o.planes, (size_t)B * OB, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-      }
+      const size_t tb = (size_t)t * (size_t)B;
+      ObsSlice s;
+      if (int rc = obs_slice(h, obs_seq, t, "wab_rollout_features", &s)) return rc;
+      if (int rc = wab_step_features(h, actions + tb, &s.o, reward + tb, done + tb, features + tb * (size_t)F, stream))
+        return rc;
+      if (int rc = obs_slice_done(h, s, stream)) return rc;
     }
   }
   if (!returns) return WAB_OK;
@@ -1457,188 +1126,6 @@ int wab_egocentric(wab_handle* h, const uint8_t* mask, uint8_t* proximity, void*
   ep.out = proximity;
   ep.counters = p.counters;
   hipLaunchKernelGGL(wab::wab_egocentric_kernel, dim3((unsigned)p.B), dim3(64), 0, (hipStream_t)stream, ep);
-  HIP_TRY(hipGetLastError());
-  return WAB_OK;
-}
-
-int wab_discounted_returns(const float* reward, const uint8_t* done, int32_t T, int64_t B, double gamma,
-                           const float* bootstrap, float* returns, void* stream) {
-  g_err.clear();
-  if (!reward || !done || !returns || T < 0 || B < 0)
-    return fail(WAB_E_INVALID, "wab_discounted_returns: bad argument");
-  if (T == 0 || B == 0) return WAB_OK;
-  wab::RewardTable none;
-  std::memset(&none, 0, sizeof(none));
-  return launch_returns(reward, done, T, B, gamma, bootstrap, returns, none, stream);
-}
-
-int wab_discounted_returns_exact(const wab_handle* h, const float* reward, const uint8_t* done, int32_t T,
-                                 int64_t B, double gamma, const float* bootstrap, float* returns, void* stream) {
-  g_err.clear();
-  if (!h || !reward || !done || !returns || T < 0 || B < 0)
-    return fail(WAB_E_INVALID, "wab_discounted_returns_exact: bad argument");
-  if (h->rewards.n < 0)
-    return fail(WAB_E_INVALID, "wab_discounted_returns_exact: two of the options' rewards round to the same "
-                               "float32; the double rewards are not recoverable");
-  if (T == 0 || B == 0) return WAB_OK;
-  DeviceGuard guard(h->device);
-  return launch_returns(reward, done, T, B, gamma, bootstrap, returns, h->rewards, stream);
-}
-
-namespace {
-// the count table of wab_episode_stats_update (wab_episodes.h): W waves per step, N entries,
-// n_tiles tiles; false where the table is larger than a grid can cover
-bool episode_table(int32_t T, int64_t B, int64_t* W, int64_t* N, int64_t* n_tiles) {
-  *W = (B + 63) / 64;
-  *N = (int64_t)T * *W;
-  *n_tiles = (*N + wab::kEpTile - 1) / wab::kEpTile;
-  return *n_tiles <= 0x7FFFFFFF;
-}
-}  // namespace
-
-int64_t wab_episode_stats_workspace(int32_t T, int64_t B) {
-  g_err.clear();
-  int64_t W, N, n_tiles;
-  if (T < 0 || B < 1 || B > 0x7FFFFFFF || !episode_table(T, B, &W, &N, &n_tiles))
-    return fail(WAB_E_INVALID, "wab_episode_stats_workspace: T >= 0, 1 <= B < 2^31 and T * ceil(B / 64) < 2^39");
-  return n_tiles * 8 + N * 4;  // tile_off i64 [n_tiles], then local u32 [N]
-}
-
-int wab_episode_stats_update(const wab_handle* h, const float* reward, const uint8_t* done, int32_t T, int64_t B,
-                             double* ret, int64_t* length, double* ep_return, int32_t* ep_length, int32_t* ep_env,
-                             int32_t* ep_step, int64_t capacity, int64_t* count, void* workspace, void* stream) {
-  g_err.clear();
-  wab::EpisodeParams q;
-  std::memset(&q, 0, sizeof(q));
-  if (T < 0 || B < 1 || B > 0x7FFFFFFF || !episode_table(T, B, &q.W, &q.N, &q.n_tiles))
-    return fail(WAB_E_INVALID, "wab_episode_stats_update: T >= 0, 1 <= B < 2^31 and T * ceil(B / 64) < 2^39");
-  if (!ret || !length || !count || capacity < 0 || (T > 0 && (!reward || !done)))
-    return fail(WAB_E_INVALID, "wab_episode_stats_update: bad argument");
-  if (capacity > 0 && (!ep_return || !ep_length || !ep_env || !ep_step))
-    return fail(WAB_E_INVALID, "wab_episode_stats_update: the record arrays may be NULL with capacity 0 only");
-  if (T > 0 && (!workspace || ((uintptr_t)workspace & 7u) != 0))
-    return fail(WAB_E_INVALID, "wab_episode_stats_update: workspace must be 8-byte aligned and hold "
-                               "wab_episode_stats_workspace(T, B) bytes");
-  if (h && h->rewards.n < 0)
-    return fail(WAB_E_INVALID, "wab_episode_stats_update: two of the options' rewards round to the same "
-                               "float32; the double rewards are not recoverable");
-  int ne = 0;
-  if (h) q.tab = inexact_rewards(h->rewards, &ne);
-  q.reward = reward;
-  q.done = done;
-  q.T = T;
-  q.B = B;
-  q.ret = ret;
-  q.length = length;
-  q.ep_return = ep_return;
-  q.ep_length = ep_length;
-  q.ep_env = ep_env;
-  q.ep_step = ep_step;
-  q.capacity = capacity;
-  q.count = count;
-  q.tile_off = static_cast<int64_t*>(workspace);
-  q.local = reinterpret_cast<uint32_t*>(q.tile_off + q.n_tiles);
-  int device = 0;
-  if (h) device = h->device;
-  else HIP_TRY(hipGetDevice(&device));
-  DeviceGuard guard(device);
-  hipStream_t s = (hipStream_t)stream;
-  if (T > 0) hipLaunchKernelGGL(wab::wab_episode_count_kernel, dim3((unsigned)q.n_tiles), dim3(256), 0, s, q);
-  hipLaunchKernelGGL(wab::wab_episode_scan_kernel, dim3(1), dim3(256), 0, s, q);  // (T = 0: count = {0, 0})
-  if (T > 0) {
-    const dim3 grid((unsigned)q.W);
-#define WAB_WALK(N) hipLaunchKernelGGL((wab::wab_episode_walk_kernel<N>), grid, dim3(64), 0, s, q)
-    switch (ne) {
-      case 0: WAB_WALK(0); break;
-      case 1: WAB_WALK(1); break;
-      case 2: WAB_WALK(2); break;
-      case 3: WAB_WALK(3); break;
-      case 4: WAB_WALK(4); break;
-      default: WAB_WALK(8);
-    }
-#undef WAB_WALK
-  }
-  HIP_TRY(hipGetLastError());
-  return WAB_OK;
-}
-
-int wab_normalize_episode_returns(const float* returns, const uint8_t* done, int32_t T, int64_t B, double eps,
-                                  float* out, void* stream) {
-  g_err.clear();
-  if (!returns || !done || !out || T < 0 || B < 0)
-    return fail(WAB_E_INVALID, "wab_normalize_episode_returns: bad argument");
-  if (T == 0 || B == 0) return WAB_OK;
-  if ((B + 63) / 64 > 0x7FFFFFFF) return fail(WAB_E_INVALID, "wab_normalize_episode_returns: B too large");
-  const dim3 grid((unsigned)((B + 63) / 64));
-  if (T <= wab::kNormLdsSteps)  // the wave's columns in LDS, T x 64 floats
-    hipLaunchKernelGGL(wab::wab_normalize_lds_kernel, grid, dim3(64), (size_t)T * 256u, (hipStream_t)stream, returns,
-                       done, T, B, eps, out);
-  else
-    hipLaunchKernelGGL(wab::wab_normalize_kernel, grid, dim3(64), 0, (hipStream_t)stream, returns, done, T, B, eps,
-                       out);
-  HIP_TRY(hipGetLastError());
-  return WAB_OK;
-}
-
-int wab_gae(const wab_handle* h, const float* reward, const uint8_t* done, const float* value,
-            const float* last_value, int32_t T, int64_t B, double gamma, double lambda, float* advantage,
-            float* target, void* stream) {
-  g_err.clear();
-  if (!reward || !done || !value || (!advantage && !target) || T < 0 || B < 0)
-    return fail(WAB_E_INVALID, "wab_gae: bad argument (reward, done, value and one of advantage, target are "
-                               "required; T >= 0, B >= 0)");
-  if (h && h->rewards.n < 0)
-    return fail(WAB_E_INVALID, "wab_gae: two of the options' rewards round to the same float32; the double rewards "
-                               "are not recoverable");
-  if (T == 0 || B == 0) return WAB_OK;
-  if ((B + 63) / 64 > 0x7FFFFFFF || (uint64_t)B > (~(uint64_t)0 >> 3) / (uint64_t)T)
-    return fail(WAB_E_INVALID, "wab_gae: B too large");
-  {
-    const uint64_t n = (uint64_t)T * (uint64_t)B;
-    const void* in[4] = {reward, done, value, last_value};
-    const uint64_t in_bytes[4] = {4 * n, n, 4 * n, 4 * (uint64_t)B};
-    for (const float* o : {advantage, target})
-      for (int k = 0; k < 4; ++k)
-        if (ranges_overlap(o, 4 * n, in[k], in_bytes[k]))
-          return fail(WAB_E_INVALID, "wab_gae: an output overlaps an input (the scan reads value[t] again as step "
-                                     "t - 1's next value)");
-    if (ranges_overlap(advantage, 4 * n, target, 4 * n))
-      return fail(WAB_E_INVALID, "wab_gae: advantage and target overlap");
-  }
-  wab::RewardTable none;
-  std::memset(&none, 0, sizeof(none));
-  int device = 0;
-  if (h) device = h->device;
-  else HIP_TRY(hipGetDevice(&device));
-  DeviceGuard guard(device);
-  return launch_gae(reward, done, value, last_value, T, B, gamma, lambda, advantage, target, h ? h->rewards : none,
-                    stream);
-}
-
-int64_t wab_whiten_workspace(int64_t n) {
-  g_err.clear();
-  if (n < 0 || n > wab::kWhitenMaxN) return fail(WAB_E_INVALID, "wab_whiten_workspace: 0 <= n <= 2^40");
-  return 2 * (int64_t)wab::kWhitenMaxGroups * 8;  // the partial sums of x, then of the squared deviations
-}
-
-int wab_whiten(const float* x, int64_t n, double eps, float* out, void* workspace, void* stream) {
-  g_err.clear();
-  if (n < 0 || n > wab::kWhitenMaxN) return fail(WAB_E_INVALID, "wab_whiten: 0 <= n <= 2^40");
-  if (n == 0) return WAB_OK;
-  if (!x || !out || !workspace || ((uintptr_t)workspace & 7u) != 0)
-    return fail(WAB_E_INVALID, "wab_whiten: x, out and an 8-byte aligned workspace of wab_whiten_workspace(n) bytes "
-                               "are required");
-  if (out != x && ranges_overlap(x, 4 * (uint64_t)n, out, 4 * (uint64_t)n))
-    return fail(WAB_E_INVALID, "wab_whiten: out must be x itself or not overlap it");
-  const int64_t tiles = (n + wab::kWhitenTile - 1) / wab::kWhitenTile;
-  const dim3 grid((unsigned)std::min<int64_t>(tiles, wab::kWhitenMaxGroups)), block(wab::kWhitenThreads);
-  double* psum = static_cast<double*>(workspace);
-  double* pss = psum + wab::kWhitenMaxGroups;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(wab::wab_whiten_sum_kernel, grid, block, 0, s, x, n, psum);
-  hipLaunchKernelGGL(wab::wab_whiten_dev_kernel, grid, block, 0, s, x, n, (const double*)psum, pss);
-  hipLaunchKernelGGL(wab::wab_whiten_out_kernel, grid, block, 0, s, x, n, eps, (const double*)psum, (const double*)pss,
-                     out);
   HIP_TRY(hipGetLastError());
   return WAB_OK;
 }
@@ -1767,464 +1254,6 @@ int wab_snapshot_restore(wab_handle* h, const wab_snapshot_info* info, const voi
   return WAB_OK;
 }
 
-// ---- device policy (wab_policy.hip) -------------------------------------------------------
-
-int wab_policy_create(const wab_policy_shape* shape, int device, wab_policy** out) {
-  g_err.clear();
-  if (!shape || !out) return fail(WAB_E_INVALID, "wab_policy_create: NULL argument");
-  *out = nullptr;
-  if (shape->in_features < 1) return fail(WAB_E_INVALID, "wab_policy_create: in_features must be >= 1");
-  const int32_t hs[3] = {shape->h1, shape->h2, shape->h3};
-  for (int i = 0; i < 3; ++i)
-    if (hs[i] < 1 || hs[i] > wab::kPolicyMaxWidth)
-      return fail(WAB_E_INVALID, "wab_policy_create: h" + std::to_string(i + 1) + " = " + std::to_string(hs[i]) +
-                                     " outside [1, 256]");
-  if (shape->n_actions < 2 || shape->n_actions > wab::kPolicyMaxActions)
-    return fail(WAB_E_INVALID, "wab_policy_create: n_actions must be in [2, 8]");
-  if (shape->in_features > (1 << 20)) return fail(WAB_E_INVALID, "wab_policy_create: in_features above 2^20");
-  int n_dev = 0;
-  HIP_TRY(hipGetDeviceCount(&n_dev));
-  if (device < 0 || device >= n_dev) return fail(WAB_E_INVALID, "wab_policy_create: no such device");
-  wab_policy* p = new (std::nothrow) wab_policy();
-  if (!p) return fail(WAB_E_NOMEM, "wab_policy_create: out of host memory");
-  p->device = device;
-  p->dims = wab::policy_dims(shape->in_features, shape->h1, shape->h2, shape->h3, shape->n_actions);
-  p->lds = wab::policy_lds(p->dims);
-  DeviceGuard guard(device);
-  // the kernel's dynamic LDS can exceed the 64 KB default: raised for this device at every
-  // create, to what this policy needs or more (the attribute is a maximum per device and kernel,
-  // so it is set to the device's limit, whatever other policies on the device need)
-  int lds_max = 0;
-  hipError_t e = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
-  if (e == hipSuccess && (size_t)lds_max < p->lds.total) {
-    delete p;
-    return fail(WAB_E_INVALID, "wab_policy_create: the device's LDS is smaller than the kernel needs");
-  }
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(policy_two_tiles(p->dims) ? reinterpret_cast<void*>(&wab::wab_policy_kernel<true>)
-                                                      : reinterpret_cast<void*>(&wab::wab_policy_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-  // the same for wab_rollout_policy's one-launch instances on this device (both: which one a
-  // handle takes depends on its options)
-  for (bool rules : {false, true})
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(roll_policy_kernel(rules), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-  void *w = nullptr, *b = nullptr;
-  if (e == hipSuccess) e = hipMalloc(&w, (size_t)p->dims.w_total * 2u);
-  if (e == hipSuccess) e = hipMalloc(&b, (size_t)p->dims.b_total * 4u);
-  if (e != hipSuccess) {
-    if (w) (void)hipFree(w);
-    delete p;
-    return fail(e == hipErrorOutOfMemory ? WAB_E_NOMEM : WAB_E_HIP,
-                std::string("wab_policy_create: ") + hipGetErrorString(e));
-  }
-  p->w = static_cast<uint16_t*>(w);
-  p->b = static_cast<float*>(b);
-  *out = p;
-  return WAB_OK;
-}
-
-int wab_policy_destroy(wab_policy* p) {
-  if (!p) return WAB_OK;
-  {
-    DeviceGuard guard(p->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(p->w);
-    (void)hipFree(p->b);
-  }
-  delete p;
-  return WAB_OK;
-}
-
-int wab_policy_load(wab_policy* p, const wab_policy_weights* wts, void* stream) {
-  g_err.clear();
-  if (!p || !wts) return fail(WAB_E_INVALID, "wab_policy_load: NULL argument");
-  if (!wts->w1 || !wts->b1 || !wts->w2 || !wts->b2 || !wts->w3 || !wts->b3 || !wts->wa || !wts->ba || !wts->wv ||
-      !wts->bv)
-    return fail(WAB_E_INVALID, "wab_policy_load: every weight and bias pointer must be set");
-  wab::PolicyPackParams pp;
-  pp.d = p->dims;
-  pp.w1 = wts->w1; pp.b1 = wts->b1; pp.w2 = wts->w2; pp.b2 = wts->b2; pp.w3 = wts->w3; pp.b3 = wts->b3;
-  pp.wa = wts->wa; pp.ba = wts->ba; pp.wv = wts->wv; pp.bv = wts->bv;
-  pp.w = p->w;
-  pp.b = p->b;
-  DeviceGuard guard(p->device);
-  const unsigned blocks = (unsigned)std::min<uint32_t>((p->dims.w_total + 255u) / 256u, 1024u);
-  hipLaunchKernelGGL(wab::wab_policy_pack, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pp);
-  HIP_TRY(hipGetLastError());
-  p->loaded = true;
-  return WAB_OK;
-}
-
-int wab_policy_act(wab_handle* h, wab_policy* p, const float* features, int8_t* actions, float* probs,
-                   float* value, void* stream) {
-  g_err.clear();
-  if (!h || !p || !features || !actions) return fail(WAB_E_INVALID, "wab_policy_act: NULL argument");
-  if (p->device != h->device)
-    return fail(WAB_E_INVALID, "wab_policy_act: the policy is on device " + std::to_string(p->device) +
-                                   ", the handle on device " + std::to_string(h->device));
-  if (p->dims.A != h->p.n_actions)
-    return fail(WAB_E_INVALID, "wab_policy_act: the policy has " + std::to_string(p->dims.A) +
-                                   " actions, the handle's options " + std::to_string(h->p.n_actions));
-  if (!p->loaded) return fail(WAB_E_STATE, "wab_policy_act: call wab_policy_load first");
-  if (!h->reset_done) return fail(WAB_E_STATE, "wab_policy_act: call wab_reset first (no env has an episode yet)");
-  if ((reinterpret_cast<uintptr_t>(features) & 3u) != 0 || (probs && (reinterpret_cast<uintptr_t>(probs) & 3u) != 0) ||
-      (value && (reinterpret_cast<uintptr_t>(value) & 3u) != 0))
-    return fail(WAB_E_INVALID, "wab_policy_act: features, probs and value must be 4-byte aligned");
-  if (h->p.B == 0) return WAB_OK;
-  wab::PolicyParams pp;
-  pp.d = p->dims;
-  pp.lds = p->lds;
-  pp.seed = h->p.seed;
-  pp.env_base = h->p.env_base;
-  pp.B = h->p.B;
-  pp.hdr = h->p.hdr;
-  pp.features = features;
-  pp.actions = actions;
-  pp.probs = probs;
-  pp.value = value;
-  pp.w = p->w;
-  pp.b = p->b;
-  DeviceGuard guard(h->device);
-  const dim3 grid((unsigned)((h->p.B + wab::kPolicyEnvs - 1) / wab::kPolicyEnvs));
-  if (policy_two_tiles(p->dims))
-    hipLaunchKernelGGL(wab::wab_policy_kernel<true>, grid, dim3(256), p->lds.total, (hipStream_t)stream, pp);
-  else
-    hipLaunchKernelGGL(wab::wab_policy_kernel<false>, grid, dim3(256), p->lds.total, (hipStream_t)stream, pp);
-  HIP_TRY(hipGetLastError());
-  return WAB_OK;
-}
-
-// ---- device policy: loss and parameter gradients (wab_policy_grad.hip) ---------------------
-
-namespace {
-
-// rows per chunk a call runs with: 0 = the default; a positive multiple of 128 otherwise
-int64_t grad_chunk_rows(int32_t chunk_rows) {
-  if (chunk_rows == 0) return wab::kGradDefaultChunk;
-  if (chunk_rows < 0 || chunk_rows % wab::kGradRows != 0) return -1;
-  return chunk_rows;
-}
-
-// wab_policy_bwd_kernel's dynamic LDS can exceed the 64 KB default: the attribute is a maximum
-// per (device, kernel), set once for each pair to the device's limit
-hipError_t grad_raise_lds(int device, bool two) {
-  static std::mutex mu;
-  static std::vector<std::pair<int, bool>> done;
-  std::lock_guard<std::mutex> lock(mu);
-  if (std::find(done.begin(), done.end(), std::make_pair(device, two)) != done.end()) return hipSuccess;
-  int lds_max = 0;
-  hipError_t e = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(two ? reinterpret_cast<void*>(&wab::wab_policy_bwd_kernel<true>)
-                                : reinterpret_cast<void*>(&wab::wab_policy_bwd_kernel<false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-  if (e == hipSuccess) done.emplace_back(device, two);
-  return e;
-}
-
-}  // namespace
-
-size_t wab_policy_grad_workspace(const wab_policy* p, int64_t N, int32_t chunk_rows) {
-  g_err.clear();
-  const int64_t cr = grad_chunk_rows(chunk_rows);
-  if (!p || N < 0 || N > INT32_MAX || cr < 0) {
-    g_err = "wab_policy_grad_workspace: NULL policy, N outside [0, 2^31) or chunk_rows not a multiple of 128";
-    return 0;
-  }
-  // (the size does not shrink with N: a cached workspace serves every call of the policy)
-  return wab::grad_workspace(wab::grad_plan(p->dims), cr).total;
-}
-
-int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions, const float* weight,
-                    const float* target, int64_t N, const wab_policy_loss* loss, const wab_policy_weights* grads_out,
-                    float loss_out[4], float* logp, float* value, float* entropy, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-  g_err.clear();
-  if (!p || !loss || !grads_out || !workspace) return fail(WAB_E_INVALID, "wab_policy_grad: NULL argument");
-  if (N < 0 || N > INT32_MAX) return fail(WAB_E_INVALID, "wab_policy_grad: N outside [0, 2^31)");
-  if (N > 0 && (!features || !actions || !weight || !target))
-    return fail(WAB_E_INVALID, "wab_policy_grad: NULL argument (features, actions, weight and target are required)");
-  const wab_policy_weights& go = *grads_out;
-  if (!go.w1 || !go.b1 || !go.w2 || !go.b2 || !go.w3 || !go.b3 || !go.wa || !go.ba || !go.wv || !go.bv)
-    return fail(WAB_E_INVALID, "wab_policy_grad: every gradient pointer must be set");
-  if (loss->value_loss != WAB_VALUE_LOSS_SMOOTH_L1 && loss->value_loss != WAB_VALUE_LOSS_MSE)
-    return fail(WAB_E_INVALID, "wab_policy_grad: value_loss must be WAB_VALUE_LOSS_SMOOTH_L1 or WAB_VALUE_LOSS_MSE");
-  const int64_t cr = grad_chunk_rows(loss->chunk_rows);
-  if (cr < 0) return fail(WAB_E_INVALID, "wab_policy_grad: chunk_rows must be 0 or a positive multiple of 128");
-  if (!p->loaded) return fail(WAB_E_STATE, "wab_policy_grad: call wab_policy_load first");
-  const wab::GradPlan g = wab::grad_plan(p->dims);
-  const wab::GradWorkspace lay = wab::grad_workspace(g, cr);
-  if (workspace_bytes < lay.total)
-    return fail(WAB_E_INVALID, "wab_policy_grad: the workspace has " + std::to_string(workspace_bytes) +
-                                   " bytes, wab_policy_grad_workspace asks for " + std::to_string(lay.total));
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-    return fail(WAB_E_INVALID, "wab_policy_grad: the workspace must be 256-byte aligned");
-  const void* f32s[] = {features, weight, target, loss_out, logp, value, entropy, go.w1, go.b1, go.w2, go.b2,
-                        go.w3, go.b3, go.wa, go.ba, go.wv, go.bv};
-  for (const void* q : f32s)
-    if ((reinterpret_cast<uintptr_t>(q) & 3u) != 0)
-      return fail(WAB_E_INVALID, "wab_policy_grad: float arrays must be 4-byte aligned");
-  DeviceGuard guard(p->device);
-  const bool two = policy_two_tiles(p->dims);
-  HIP_TRY(grad_raise_lds(p->device, two));
-  unsigned char* const base = static_cast<unsigned char*>(workspace);
-  uint32_t* const bad = reinterpret_cast<uint32_t*>(base + lay.bad);
-  uint16_t* const wt = reinterpret_cast<uint16_t*>(base + lay.wt);
-  uint16_t* const ws = reinterpret_cast<uint16_t*>(base + lay.ws);
-  float* const slab = reinterpret_cast<float*>(base + lay.slab);
-  double* const part = reinterpret_cast<double*>(base + lay.part);
-  double* const lsum = reinterpret_cast<double*>(base + lay.loss);
-  hipStream_t st = (hipStream_t)stream;
-
-  // the transposed image, from the packed weights as they are at this point of the stream (every
-  // call: a flag on the host would go stale under graph replay)
-  wab::GradPackParams kp;
-  kp.g = g;
-  kp.w = p->w;
-  kp.wt = wt;
-  kp.bad = bad;
-  hipLaunchKernelGGL(wab::wab_policy_grad_pack, dim3(std::min<uint32_t>((g.wt_total + 255u) / 256u, 1024u)), dim3(256),
-                     0, st, kp);
-  HIP_TRY(hipGetLastError());
-
-  wab::GradBwdParams bp;
-  bp.g = g;
-  bp.N = N;
-  bp.chunk_rows = cr;
-  bp.features = features;
-  bp.actions = actions;
-  bp.weight = weight;
-  bp.target = target;
-  bp.w = p->w;
-  bp.b = p->b;
-  bp.wt = wt;
-  bp.value_coef = loss->value_coef;
-  bp.entropy_coef = loss->entropy_coef;
-  bp.mse = loss->value_loss == WAB_VALUE_LOSS_MSE ? 1 : 0;
-  bp.logp = logp;
-  bp.value = value;
-  bp.entropy = entropy;
-  bp.ws = ws;
-  bp.part = part;
-  bp.bad = bad;
-  wab::GradWgradParams wp;
-  wp.g = g;
-  wp.N = N;
-  wp.chunk_rows = cr;
-  wp.features = features;
-  wp.ws = ws;
-  wp.part = part;
-  wp.slab = slab;
-  wp.loss = lsum;
-  for (int64_t row0 = 0; row0 < N; row0 += cr) {
-    const int64_t rows = std::min<int64_t>(cr, N - row0);
-    const unsigned blocks = (unsigned)((rows + wab::kGradRows - 1) / wab::kGradRows);
-    bp.row0 = row0;
-    if (two)
-      hipLaunchKernelGGL(wab::wab_policy_bwd_kernel<true>, dim3(blocks), dim3(256), g.lds_total, st, bp);
-    else
-      hipLaunchKernelGGL(wab::wab_policy_bwd_kernel<false>, dim3(blocks), dim3(256), g.lds_total, st, bp);
-    HIP_TRY(hipGetLastError());
-    wp.row0 = row0;
-    wp.n_blocks = (int32_t)blocks;
-    wp.first = row0 == 0 ? 1 : 0;
-    hipLaunchKernelGGL(wab::wab_policy_wgrad_kernel, dim3((unsigned)g.n_tasks + 1u, (unsigned)g.slabs), dim3(64), 0,
-                       st, wp);
-    HIP_TRY(hipGetLastError());
-  }
-
-  wab::GradReduceParams rp;
-  rp.g = g;
-  rp.empty = N == 0 ? 1 : 0;
-  rp.accumulate = loss->accumulate ? 1 : 0;
-  rp.scale = loss->scale;
-  rp.value_coef = loss->value_coef;
-  rp.entropy_coef = loss->entropy_coef;
-  rp.slab = slab;
-  rp.loss = lsum;
-  rp.w1 = const_cast<float*>(go.w1); rp.b1 = const_cast<float*>(go.b1);
-  rp.w2 = const_cast<float*>(go.w2); rp.b2 = const_cast<float*>(go.b2);
-  rp.w3 = const_cast<float*>(go.w3); rp.b3 = const_cast<float*>(go.b3);
-  rp.wa = const_cast<float*>(go.wa); rp.ba = const_cast<float*>(go.ba);
-  rp.wv = const_cast<float*>(go.wv); rp.bv = const_cast<float*>(go.bv);
-  rp.loss_out = loss_out;
-  const wab::PolicyDims& d = p->dims;
-  const int64_t elems = (int64_t)d.h1 * (d.F + 1) + (int64_t)d.h2 * (d.h1 + 1) + (int64_t)d.h3 * (d.h2 + 1) +
-                        (int64_t)(d.A + 1) * (d.h3 + 1);
-  hipLaunchKernelGGL(wab::wab_policy_grad_reduce_kernel, dim3((unsigned)std::min<int64_t>((elems + 255) / 256, 4096)),
-                     dim3(256), 0, st, rp);
-  HIP_TRY(hipGetLastError());
-  return WAB_OK;
-}
-
-int wab_policy_grad_bad_actions(const wab_policy* p, const void* workspace, void* stream, uint64_t* out) {
-  g_err.clear();
-  if (!p || !workspace || !out) return fail(WAB_E_INVALID, "wab_policy_grad_bad_actions: NULL argument");
-  DeviceGuard guard(p->device);
-  uint32_t v = 0;
-  HIP_TRY(hipMemcpyAsync(&v, workspace, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  *out = v;
-  if (v != 0)
-    return fail(WAB_E_INVALID, "wab_policy_grad: " + std::to_string(v) + " rows had an action outside [0, " +
-                                   std::to_string(p->dims.A) + "); they were left out of the loss and the gradients");
-  return WAB_OK;
-}
-
-int wab_debug_policy_grad_plan(const wab_policy* p, int32_t chunk_rows, int32_t out[5]) {
-  g_err.clear();
-  if (!p || !out) return fail(WAB_E_INVALID, "wab_debug_policy_grad_plan: NULL argument");
-  const int64_t cr = grad_chunk_rows(chunk_rows);
-  if (cr < 0) return fail(WAB_E_INVALID, "wab_debug_policy_grad_plan: chunk_rows must be 0 or a positive multiple of 128");
-  const wab::GradPlan g = wab::grad_plan(p->dims);
-  out[0] = wab::kGradRows;
-  out[1] = g.slabs;
-  out[2] = (int32_t)cr;
-  out[3] = (int32_t)g.lds_total;
-  out[4] = 0;  // wab_policy_wgrad_kernel uses no LDS
-  return WAB_OK;
-}
-
-int wab_rollout_policy_fused(const wab_handle* h, const wab_policy* p) {
-  g_err.clear();
-  if (!h || !p) return fail(WAB_E_INVALID, "wab_rollout_policy_fused: NULL argument");
-  if (p->device != h->device)
-    return fail(WAB_E_INVALID, "wab_rollout_policy_fused: the policy is on device " + std::to_string(p->device) +
-                                   ", the handle on device " + std::to_string(h->device));
-  return roll_policy_plan(h, p, 1, false, nullptr, &g_err) ? 1 : 0;
-}
-
-int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int32_t T, const wab_obs* obs_seq,
-                       int8_t* actions, float* value, float* probs, float* reward, uint8_t* done, float* features,
-                       float* features_last, double gamma, const float* bootstrap, float* returns, void* stream) {
-  g_err.clear();
-  if (!h || !p) return fail(WAB_E_INVALID, "wab_rollout_policy: NULL argument");
-  if (T < 0) return fail(WAB_E_INVALID, "wab_rollout_policy: T must be >= 0");
-  if (!features0 || !actions || !reward || !done || !features_last || !obs_seq || !obs_seq->food_turns ||
-      !obs_seq->role || !obs_seq->status)
-    return fail(WAB_E_INVALID, "wab_rollout_policy: NULL argument (features0, actions, reward, done, features_last "
-                               "and the scalars of obs_seq are required)");
-  if (p->device != h->device)
-    return fail(WAB_E_INVALID, "wab_rollout_policy: the policy is on device " + std::to_string(p->device) +
-                                   ", the handle on device " + std::to_string(h->device));
-  if (p->dims.A != h->p.n_actions)
-    return fail(WAB_E_INVALID, "wab_rollout_policy: the policy has " + std::to_string(p->dims.A) +
-                                   " actions, the handle's options " + std::to_string(h->p.n_actions));
-  const int F = wab_feature_dim(h);
-  if (F < 0) return fail(WAB_E_INVALID, "wab_rollout_policy: the wrapper cannot index this viewport");
-  if (p->dims.F != F)
-    return fail(WAB_E_INVALID, "wab_rollout_policy: the policy takes " + std::to_string(p->dims.F) +
-                                   " features, the handle's rows have " + std::to_string(F));
-  if (!p->loaded) return fail(WAB_E_STATE, "wab_rollout_policy: call wab_policy_load first");
-  if (!h->reset_done) return fail(WAB_E_STATE, "wab_rollout_policy: call wab_reset first (no env has an episode yet)");
-  const auto misaligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3u) != 0; };
-  if (misaligned4(features0) || (probs && misaligned4(probs)) || (value && misaligned4(value)))
-    return fail(WAB_E_INVALID, "wab_rollout_policy: features0, probs and value must be 4-byte aligned");
-  if (!aligned16(features_last) || (features && !aligned16(features)))
-    return fail(WAB_E_INVALID, "wab_rollout_policy: features and features_last must be 16-byte aligned");
-  if (obs_seq->planes && !aligned16(obs_seq->planes))
-    return fail(WAB_E_INVALID, "wab_rollout_policy: planes must be 16-byte aligned");
-  const int64_t B = h->p.B;
-  const size_t OB = (size_t)h->p.OB, BF = (size_t)B * (size_t)F;
-  if (T == 0 || B == 0) return WAB_OK;
-  const bool fused_returns = returns && T <= wab::kMaxFusedReturnSteps;
-  wab::RollPolicy rp;
-  bool fused = roll_policy_plan(h, p, T, fused_returns, &rp, nullptr);
-  if (obs_seq->planes && ((size_t)B * OB) % 16u != 0) fused = false;  // (the launch's 16-byte obs stores)
-  if (returns && !(fused && fused_returns) && h->rewards.n < 0)  // (checked before anything runs)
-    return fail(WAB_E_INVALID, "wab_rollout_policy: returns of this segment need the exact-reward scan, and two of "
-                               "the options' rewards round to the same float32 (pass returns = NULL)");
-  if (fused) {
-    // one launch: each workgroup runs its 64 envs through the T steps, the policy between them
-    // (wab_step_small<8, 11, FEAT, ROLL, .., POLICY>), the returns of the segment at its end
-    Params q = h->p;
-    q.actions = actions;
-    q.planes = obs_seq->planes;
-    q.food_turns = obs_seq->food_turns;
-    q.role = obs_seq->role;
-    q.status = obs_seq->status;
-    q.reward = reward;
-    q.done = done;
-    q.features = features_last;  // (non-null: the featurizer is on; the rows go where q.pol says)
-    q.n_steps = T;
-    if (fused_returns) {
-      q.returns = returns;
-      q.bootstrap = bootstrap;
-      q.gamma = gamma;
-    }
-    rp.features0 = features0;
-    rp.features = features;
-    rp.features_last = features_last;
-    rp.actions = actions;
-    rp.probs = probs;
-    rp.value = value;
-    rp.w = p->w;
-    rp.b = p->b;
-    q.pol = rp;
-    DeviceGuard guard(h->device);
-    ++h->rollout_launches;
-    const dim3 grid(h->n_blocks), block(256);
-    bool launched = false;
-#if WAB_RULES_INSTANCE
-    if (h->small_rules) {
-      hipLaunchKernelGGL((wab::wab_step_small<8, 11, true, true, true, true>), grid, block, rp.total, (hipStream_t)stream, q);
-      launched = true;
-    }
-#endif
-    if (!launched)
-      hipLaunchKernelGGL((wab::wab_step_small<8, 11, true, true, false, true>), grid, block, rp.total, (hipStream_t)stream, q);
-    HIP_TRY(hipGetLastError());
-    if (fused_returns || !returns) return WAB_OK;
-    return wab_discounted_returns_exact(h, reward, done, T, B, gamma, bootstrap, returns, stream);
-  }
-  // the 2 T calls; a step's rows go straight to their slice when there is one and it is aligned,
-  // else through the handle's pair of rows (alternating: step t reads one, writes the other)
-  ++h->rollout_step_calls;
-  const bool direct = features && (BF * 4u) % 16u == 0;
-  float* bounce = nullptr;
-  if (!direct && T > 1) {
-    bounce = bounce_rows(h, BF);
-    if (!bounce) return fail(WAB_E_NOMEM, "wab_rollout_policy: hipMalloc");
-  }
-  const size_t bounce_stride = (BF + 3u) & ~(size_t)3u;
-  if (features && features != features0) {
-    DeviceGuard guard(h->device);
-    HIP_TRY(hipMemcpyAsync(features, features0, BF * 4u, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  }
-  const float* cur = features0;
-  for (int32_t t = 0; t < T; ++t) {
-    const size_t tb = (size_t)t * (size_t)B;
-    int rc = wab_policy_act(h, p, cur, actions + tb, probs ? probs + tb * (size_t)p->dims.A : nullptr,
-                            value ? value + tb : nullptr, stream);
-    if (rc != WAB_OK) return rc;
-    wab_obs o;
-    o.planes = obs_seq->planes ? obs_seq->planes + tb * OB : nullptr;
-    uint8_t* pdst = o.planes;
-    if (pdst && !aligned16(pdst)) {  // (as in wab_rollout_features: through the handle's buffer)
-      o.planes = scratch_planes(h);
-      if (!o.planes) return fail(WAB_E_NOMEM, "wab_rollout_policy: hipMalloc");
-    }
-    o.food_turns = obs_seq->food_turns + tb;
-    o.role = obs_seq->role + tb;
-    o.status = obs_seq->status + tb;
-    float* slice = features && t + 1 < T ? features + (size_t)(t + 1) * BF : nullptr;
-    float* dst = t + 1 == T ? features_last : direct ? slice : bounce + (size_t)(t & 1) * bounce_stride;
-    rc = wab_step_features(h, actions + tb, &o, reward + tb, done + tb, dst, stream);
-    if (rc != WAB_OK) return rc;
-    if ((pdst && o.planes != pdst) || (slice && dst != slice)) {
-      DeviceGuard guard(h->device);
-      if (pdst && o.planes != pdst)
-        HIP_TRY(hipMemcpyAsync(pdst, o.planes, (size_t)B * OB, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-      if (slice && dst != slice)
-        HIP_TRY(hipMemcpyAsync(slice, dst, BF * 4u, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    }
-    cur = dst;
-  }
-  if (!returns) return WAB_OK;
-  return wab_discounted_returns_exact(h, reward, done, T, B, gamma, bootstrap, returns, stream);
-}
-
 int wab_debug_bush_values(wab_handle* h, const uint64_t* U, int32_t* out, int64_t n, void* stream) {
   g_err.clear();
   if (!h || !U || !out || n < 0) return fail(WAB_E_INVALID, "wab_debug_bush_values: bad argument");
@@ -2233,48 +1262,6 @@ int wab_debug_bush_values(wab_handle* h, const uint64_t* U, int32_t* out, int64_
   hipLaunchKernelGGL(bush_values_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, h->p.thresholds,
                      h->p.max_berries, h->p.bush_power, U, out, n);
   HIP_TRY(hipGetLastError());
-  return WAB_OK;
-}
-
-int wab_debug_returns_plan(const wab_handle* h, const float* reward, const uint8_t* done, const float* returns,
-                           int64_t B, int32_t out[2]) {
-  g_err.clear();
-  if (!reward || !done || !returns || B < 0 || !out) return fail(WAB_E_INVALID, "wab_debug_returns_plan: bad argument");
-  if (h && h->rewards.n < 0)
-    return fail(WAB_E_INVALID, "wab_debug_returns_plan: two of the options' rewards round to the same float32; "
-                               "wab_discounted_returns_exact refuses this handle");
-  wab::RewardTable none;
-  std::memset(&none, 0, sizeof(none));
-  const ReturnsPlan plan = returns_plan(reward, done, returns, B, h ? h->rewards : none);
-  out[0] = plan.vec;
-  out[1] = plan.ne;
-  return WAB_OK;
-}
-
-int wab_debug_gae_plan(const wab_handle* h, const float* reward, const uint8_t* done, const float* value,
-                       const float* advantage, const float* target, int64_t B, int32_t out[2]) {
-  g_err.clear();
-  if (!reward || !done || !value || (!advantage && !target) || B < 0 || !out)
-    return fail(WAB_E_INVALID, "wab_debug_gae_plan: bad argument");
-  if (h && h->rewards.n < 0)
-    return fail(WAB_E_INVALID, "wab_debug_gae_plan: two of the options' rewards round to the same float32; wab_gae "
-                               "refuses this handle");
-  wab::RewardTable none;
-  std::memset(&none, 0, sizeof(none));
-  const ReturnsPlan plan = gae_plan(reward, done, value, advantage, target, B, h ? h->rewards : none);
-  out[0] = plan.vec;
-  out[1] = plan.ne;
-  return WAB_OK;
-}
-
-int wab_debug_policy_plan(const wab_policy* p, int32_t out[5]) {
-  g_err.clear();
-  if (!p || !out) return fail(WAB_E_INVALID, "wab_debug_policy_plan: NULL argument");
-  out[0] = p->lds.n_chunks;
-  out[1] = p->lds.KC;
-  out[2] = 16 * p->dims.KS1 - (p->lds.n_chunks - 1) * p->lds.KC;
-  out[3] = (int32_t)p->lds.total;
-  out[4] = policy_two_tiles(p->dims) ? 1 : 0;
   return WAB_OK;
 }
 

@@ -1,0 +1,496 @@
+// wab_capi_policy.hip — the C-ABI's device policy: create, load, act (wab_policy.hip), loss and
+// parameter gradients (wab_policy_grad.hip) and the closed-loop rollout wab_rollout_policy (the
+// POLICY instances of wab_step_small.hip, or act and step in turns).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <new>
+
+#include "wab_host.h"
+#include "wab_policy_grad.h"
+
+using namespace wab_host;
+
+namespace {
+
+// a handle-owned pair of [B][F] feature rows (16-byte aligned), allocated by the first call that needs it
+float* bounce_rows(wab_handle* h, size_t row_floats) {
+  if (!h->bounce_rows) {
+    DeviceGuard guard(h->device);
+    void* ptr = nullptr;
+    if (hipMalloc(&ptr, std::max<size_t>(16, 2u * ((row_floats + 3u) & ~(size_t)3u) * 4u)) != hipSuccess) return nullptr;
+    h->allocs.push_back(ptr);
+    h->bounce_rows = static_cast<float*>(ptr);
+  }
+  return h->bounce_rows;
+}
+
+// which instance of wab_policy_kernel and wab_policy_bwd_kernel a net takes: <true> for h1 > 128,
+// two layer-1 tiles per wave
+bool policy_two_tiles(const wab::PolicyDims& d) { return d.NT1 > 4; }
+const void* policy_kernel(const wab::PolicyDims& d) {
+  return policy_two_tiles(d) ? reinterpret_cast<const void*>(&wab::wab_policy_kernel<true>)
+                             : reinterpret_cast<const void*>(&wab::wab_policy_kernel<false>);
+}
+const void* policy_bwd_kernel(const wab::PolicyDims& d) {
+  return policy_two_tiles(d) ? reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<true>)
+                             : reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<false>);
+}
+
+// What a call on a handle and a policy together needs of the pair: always the same device; with
+// PAIR_RUNS the options' action count, loaded weights and a reset handle (the policy is to run on
+// the handle's envs); with PAIR_FEATURES the handle's feature rows as the policy's input.
+enum : unsigned { PAIR_RUNS = 1, PAIR_FEATURES = 2 };
+int check_pair(const wab_handle* h, const wab_policy* p, const char* what, unsigned checks) {
+  const std::string w = std::string(what) + ": ";
+  if (p->device != h->device)
+    return fail(WAB_E_INVALID, w + "the policy is on device " + std::to_string(p->device) + ", the handle on device " +
+                                   std::to_string(h->device));
+  if ((checks & PAIR_RUNS) && p->dims.A != h->p.n_actions)
+    return fail(WAB_E_INVALID, w + "the policy has " + std::to_string(p->dims.A) + " actions, the handle's options " +
+                                   std::to_string(h->p.n_actions));
+  if (checks & PAIR_FEATURES) {
+    const int F = wab_feature_dim(h);
+    if (F < 0) return fail(WAB_E_INVALID, w + "the wrapper cannot index this viewport");
+    if (p->dims.F != F)
+      return fail(WAB_E_INVALID, w + "the policy takes " + std::to_string(p->dims.F) +
+                                     " features, the handle's rows have " + std::to_string(F));
+  }
+  if ((checks & PAIR_RUNS) && !p->loaded) return fail(WAB_E_STATE, w + "call wab_policy_load first");
+  if ((checks & PAIR_RUNS) && !h->reset_done)
+    return fail(WAB_E_STATE, w + "call wab_reset first (no env has an episode yet)");
+  return WAB_OK;
+}
+
+// Whether (h, p) takes the one-launch path, and its LDS for T steps (returns scanned in the
+// launch or not).  The answer does not depend on T: the limit is tested with the longest
+// in-launch returns scan's reward codes.
+bool roll_policy_plan(const wab_handle* h, const wab_policy* p, int32_t T, bool fused_returns, wab::RollPolicy* out,
+                      std::string* why) {
+  const auto no = [&](const char* msg) {
+    if (why) *why = msg;
+    return false;
+  };
+  if (h->step_kernel != KERNEL_SMALL || !h->small_g11 || h->slots != 8 || !h->small_feat_lds_bytes)
+    return no("the one-launch kernel is built for the 11x11 small-view kernel with 8 wolf slots and the fused "
+              "featurizer");
+  const int F = wab_feature_dim(h);
+  if (F < 0 || p->dims.F != F) return no("the policy's in_features is not the handle's feature length");
+  if (((size_t)h->p.B * (size_t)F) % 4u != 0) return no("batch * feature_dim is not a multiple of 4");
+  Params q = h->p;
+  q.features = reinterpret_cast<float*>(16);  // (layout only)
+  q.returns = reinterpret_cast<float*>(16);
+  q.n_steps = wab::kMaxFusedReturnSteps;
+  if (wab::roll_policy_lds(p->dims, wab::small_layout(q).total * 4u).total > h->lds_max)
+    return no("the kernel's LDS exceeds the device's limit per workgroup");
+  if (out) {
+    q.n_steps = T;
+    if (!fused_returns) q.returns = nullptr;
+    *out = wab::roll_policy_lds(p->dims, wab::small_layout(q).total * 4u);
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wab_policy_create(const wab_policy_shape* shape, int device, wab_policy** out) {
+  g_err.clear();
+  if (!shape || !out) return fail(WAB_E_INVALID, "wab_policy_create: NULL argument");
+  *out = nullptr;
+  if (shape->in_features < 1) return fail(WAB_E_INVALID, "wab_policy_create: in_features must be >= 1");
+  const int32_t hs[3] = {shape->h1, shape->h2, shape->h3};
+  for (int i = 0; i < 3; ++i)
+    if (hs[i] < 1 || hs[i] > wab::kPolicyMaxWidth)
+      return fail(WAB_E_INVALID, "wab_policy_create: h" + std::to_string(i + 1) + " = " + std::to_string(hs[i]) +
+                                     " outside [1, 256]");
+  if (shape->n_actions < 2 || shape->n_actions > wab::kPolicyMaxActions)
+    return fail(WAB_E_INVALID, "wab_policy_create: n_actions must be in [2, 8]");
+  if (shape->in_features > (1 << 20)) return fail(WAB_E_INVALID, "wab_policy_create: in_features above 2^20");
+  int n_dev = 0;
+  HIP_TRY(hipGetDeviceCount(&n_dev));
+  if (device < 0 || device >= n_dev) return fail(WAB_E_INVALID, "wab_policy_create: no such device");
+  wab_policy* p = new (std::nothrow) wab_policy();
+  if (!p) return fail(WAB_E_NOMEM, "wab_policy_create: out of host memory");
+  p->device = device;
+  p->dims = wab::policy_dims(shape->in_features, shape->h1, shape->h2, shape->h3, shape->n_actions);
+  p->lds = wab::policy_lds(p->dims);
+  DeviceGuard guard(device);
+  // the kernel's dynamic LDS can exceed the 64 KB default (the attribute is a maximum per device
+  // and kernel, so it is set to the device's limit, whatever other policies on the device need)
+  int lds_max = 0;
+  hipError_t e = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
+  if (e == hipSuccess && (size_t)lds_max < p->lds.total) {
+    delete p;
+    return fail(WAB_E_INVALID, "wab_policy_create: the device's LDS is smaller than the kernel needs");
+  }
+  p->lds_max = (size_t)lds_max;
+  if (e == hipSuccess) e = raise_lds(device, policy_kernel(p->dims), p->lds_max);
+  // the same for wab_rollout_policy's one-launch instances on this device (both: which one a
+  // handle takes depends on its options)
+  for (bool rules : {false, true})
+    if (e == hipSuccess) e = raise_lds(device, small_kernel(8, true, rules, true, true, true), p->lds_max);
+  void *w = nullptr, *b = nullptr;
+  if (e == hipSuccess) e = hipMalloc(&w, (size_t)p->dims.w_total * 2u);
+  if (e == hipSuccess) e = hipMalloc(&b, (size_t)p->dims.b_total * 4u);
+  if (e != hipSuccess) {
+    if (w) (void)hipFree(w);
+    delete p;
+    return fail(e == hipErrorOutOfMemory ? WAB_E_NOMEM : WAB_E_HIP,
+                std::string("wab_policy_create: ") + hipGetErrorString(e));
+  }
+  p->w = static_cast<uint16_t*>(w);
+  p->b = static_cast<float*>(b);
+  *out = p;
+  return WAB_OK;
+}
+
+int wab_policy_destroy(wab_policy* p) {
+  if (!p) return WAB_OK;
+  {
+    DeviceGuard guard(p->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(p->w);
+    (void)hipFree(p->b);
+  }
+  delete p;
+  return WAB_OK;
+}
+
+int wab_policy_load(wab_policy* p, const wab_policy_weights* wts, void* stream) {
+  g_err.clear();
+  if (!p || !wts) return fail(WAB_E_INVALID, "wab_policy_load: NULL argument");
+  if (!wts->w1 || !wts->b1 || !wts->w2 || !wts->b2 || !wts->w3 || !wts->b3 || !wts->wa || !wts->ba || !wts->wv ||
+      !wts->bv)
+    return fail(WAB_E_INVALID, "wab_policy_load: every weight and bias pointer must be set");
+  wab::PolicyPackParams pp;
+  pp.d = p->dims;
+  pp.w1 = wts->w1; pp.b1 = wts->b1; pp.w2 = wts->w2; pp.b2 = wts->b2; pp.w3 = wts->w3; pp.b3 = wts->b3;
+  pp.wa = wts->wa; pp.ba = wts->ba; pp.wv = wts->wv; pp.bv = wts->bv;
+  pp.w = p->w;
+  pp.b = p->b;
+  DeviceGuard guard(p->device);
+  const unsigned blocks = (unsigned)std::min<uint32_t>((p->dims.w_total + 255u) / 256u, 1024u);
+  hipLaunchKernelGGL(wab::wab_policy_pack, dim3(blocks), dim3(256), 0, (hipStream_t)stream, pp);
+  HIP_TRY(hipGetLastError());
+  p->loaded = true;
+  return WAB_OK;
+}
+
+int wab_policy_act(wab_handle* h, wab_policy* p, const float* features, int8_t* actions, float* probs,
+                   float* value, void* stream) {
+  g_err.clear();
+  if (!h || !p || !features || !actions) return fail(WAB_E_INVALID, "wab_policy_act: NULL argument");
+  if (int rc = check_pair(h, p, "wab_policy_act", PAIR_RUNS)) return rc;
+  if ((reinterpret_cast<uintptr_t>(features) & 3u) != 0 || (probs && (reinterpret_cast<uintptr_t>(probs) & 3u) != 0) ||
+      (value && (reinterpret_cast<uintptr_t>(value) & 3u) != 0))
+    return fail(WAB_E_INVALID, "wab_policy_act: features, probs and value must be 4-byte aligned");
+  if (h->p.B == 0) return WAB_OK;
+  wab::PolicyParams pp;
+  pp.d = p->dims;
+  pp.lds = p->lds;
+  pp.seed = h->p.seed;
+  pp.env_base = h->p.env_base;
+  pp.B = h->p.B;
+  pp.hdr = h->p.hdr;
+  pp.features = features;
+  pp.actions = actions;
+  pp.probs = probs;
+  pp.value = value;
+  pp.w = p->w;
+  pp.b = p->b;
+  DeviceGuard guard(h->device);
+  launch_params(policy_kernel(p->dims), (unsigned)((h->p.B + wab::kPolicyEnvs - 1) / wab::kPolicyEnvs), p->lds.total,
+                (hipStream_t)stream, pp);
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+// ---- device policy: loss and parameter gradients (wab_policy_grad.hip) ---------------------
+
+namespace {
+
+// rows per chunk a call runs with: 0 = the default; a positive multiple of 128 otherwise
+int64_t grad_chunk_rows(int32_t chunk_rows) {
+  if (chunk_rows == 0) return wab::kGradDefaultChunk;
+  if (chunk_rows < 0 || chunk_rows % wab::kGradRows != 0) return -1;
+  return chunk_rows;
+}
+
+}  // namespace
+
+size_t wab_policy_grad_workspace(const wab_policy* p, int64_t N, int32_t chunk_rows) {
+  g_err.clear();
+  const int64_t cr = grad_chunk_rows(chunk_rows);
+  if (!p || N < 0 || N > INT32_MAX || cr < 0) {
+    g_err = "wab_policy_grad_workspace: NULL policy, N outside [0, 2^31) or chunk_rows not a multiple of 128";
+    return 0;
+  }
+  // (the size does not shrink with N: a cached workspace serves every call of the policy)
+  return wab::grad_workspace(wab::grad_plan(p->dims), cr).total;
+}
+
+int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions, const float* weight,
+                    const float* target, int64_t N, const wab_policy_loss* loss, const wab_policy_weights* grads_out,
+                    float loss_out[4], float* logp, float* value, float* entropy, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  g_err.clear();
+  if (!p || !loss || !grads_out || !workspace) return fail(WAB_E_INVALID, "wab_policy_grad: NULL argument");
+  if (N < 0 || N > INT32_MAX) return fail(WAB_E_INVALID, "wab_policy_grad: N outside [0, 2^31)");
+  if (N > 0 && (!features || !actions || !weight || !target))
+    return fail(WAB_E_INVALID, "wab_policy_grad: NULL argument (features, actions, weight and target are required)");
+  const wab_policy_weights& go = *grads_out;
+  if (!go.w1 || !go.b1 || !go.w2 || !go.b2 || !go.w3 || !go.b3 || !go.wa || !go.ba || !go.wv || !go.bv)
+    return fail(WAB_E_INVALID, "wab_policy_grad: every gradient pointer must be set");
+  if (loss->value_loss != WAB_VALUE_LOSS_SMOOTH_L1 && loss->value_loss != WAB_VALUE_LOSS_MSE)
+    return fail(WAB_E_INVALID, "wab_policy_grad: value_loss must be WAB_VALUE_LOSS_SMOOTH_L1 or WAB_VALUE_LOSS_MSE");
+  const int64_t cr = grad_chunk_rows(loss->chunk_rows);
+  if (cr < 0) return fail(WAB_E_INVALID, "wab_policy_grad: chunk_rows must be 0 or a positive multiple of 128");
+  if (!p->loaded) return fail(WAB_E_STATE, "wab_policy_grad: call wab_policy_load first");
+  const wab::GradPlan g = wab::grad_plan(p->dims);
+  const wab::GradWorkspace lay = wab::grad_workspace(g, cr);
+  if (workspace_bytes < lay.total)
+    return fail(WAB_E_INVALID, "wab_policy_grad: the workspace has " + std::to_string(workspace_bytes) +
+                                   " bytes, wab_policy_grad_workspace asks for " + std::to_string(lay.total));
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
+    return fail(WAB_E_INVALID, "wab_policy_grad: the workspace must be 256-byte aligned");
+  const void* f32s[] = {features, weight, target, loss_out, logp, value, entropy, go.w1, go.b1, go.w2, go.b2,
+                        go.w3, go.b3, go.wa, go.ba, go.wv, go.bv};
+  for (const void* q : f32s)
+    if ((reinterpret_cast<uintptr_t>(q) & 3u) != 0)
+      return fail(WAB_E_INVALID, "wab_policy_grad: float arrays must be 4-byte aligned");
+  DeviceGuard guard(p->device);
+  // wab_policy_bwd_kernel's dynamic LDS can exceed the 64 KB default: as wab_policy_create's
+  const void* const bwd = policy_bwd_kernel(p->dims);
+  HIP_TRY(raise_lds(p->device, bwd, p->lds_max));
+  unsigned char* const base = static_cast<unsigned char*>(workspace);
+  uint32_t* const bad = reinterpret_cast<uint32_t*>(base + lay.bad);
+  uint16_t* const wt = reinterpret_cast<uint16_t*>(base + lay.wt);
+  uint16_t* const ws = reinterpret_cast<uint16_t*>(base + lay.ws);
+  float* const slab = reinterpret_cast<float*>(base + lay.slab);
+  double* const part = reinterpret_cast<double*>(base + lay.part);
+  double* const lsum = reinterpret_cast<double*>(base + lay.loss);
+  hipStream_t st = (hipStream_t)stream;
+
+  // the transposed image, from the packed weights as they are at this point of the stream (every
+  // call: a flag on the host would go stale under graph replay)
+  wab::GradPackParams kp;
+  kp.g = g;
+  kp.w = p->w;
+  kp.wt = wt;
+  kp.bad = bad;
+  hipLaunchKernelGGL(wab::wab_policy_grad_pack, dim3(std::min<uint32_t>((g.wt_total + 255u) / 256u, 1024u)), dim3(256),
+                     0, st, kp);
+  HIP_TRY(hipGetLastError());
+
+  wab::GradBwdParams bp;
+  bp.g = g;
+  bp.N = N;
+  bp.chunk_rows = cr;
+  bp.features = features;
+  bp.actions = actions;
+  bp.weight = weight;
+  bp.target = target;
+  bp.w = p->w;
+  bp.b = p->b;
+  bp.wt = wt;
+  bp.value_coef = loss->value_coef;
+  bp.entropy_coef = loss->entropy_coef;
+  bp.mse = loss->value_loss == WAB_VALUE_LOSS_MSE ? 1 : 0;
+  bp.logp = logp;
+  bp.value = value;
+  bp.entropy = entropy;
+  bp.ws = ws;
+  bp.part = part;
+  bp.bad = bad;
+  wab::GradWgradParams wp;
+  wp.g = g;
+  wp.N = N;
+  wp.chunk_rows = cr;
+  wp.features = features;
+  wp.ws = ws;
+  wp.part = part;
+  wp.slab = slab;
+  wp.loss = lsum;
+  for (int64_t row0 = 0; row0 < N; row0 += cr) {
+    const int64_t rows = std::min<int64_t>(cr, N - row0);
+    const unsigned blocks = (unsigned)((rows + wab::kGradRows - 1) / wab::kGradRows);
+    bp.row0 = row0;
+    launch_params(bwd, blocks, g.lds_total, st, bp);
+    HIP_TRY(hipGetLastError());
+    wp.row0 = row0;
+    wp.n_blocks = (int32_t)blocks;
+    wp.first = row0 == 0 ? 1 : 0;
+    hipLaunchKernelGGL(wab::wab_policy_wgrad_kernel, dim3((unsigned)g.n_tasks + 1u, (unsigned)g.slabs), dim3(64), 0,
+                       st, wp);
+    HIP_TRY(hipGetLastError());
+  }
+
+  wab::GradReduceParams rp;
+  rp.g = g;
+  rp.empty = N == 0 ? 1 : 0;
+  rp.accumulate = loss->accumulate ? 1 : 0;
+  rp.scale = loss->scale;
+  rp.value_coef = loss->value_coef;
+  rp.entropy_coef = loss->entropy_coef;
+  rp.slab = slab;
+  rp.loss = lsum;
+  rp.w1 = const_cast<float*>(go.w1); rp.b1 = const_cast<float*>(go.b1);
+  rp.w2 = const_cast<float*>(go.w2); rp.b2 = const_cast<float*>(go.b2);
+  rp.w3 = const_cast<float*>(go.w3); rp.b3 = const_cast<float*>(go.b3);
+  rp.wa = const_cast<float*>(go.wa); rp.ba = const_cast<float*>(go.ba);
+  rp.wv = const_cast<float*>(go.wv); rp.bv = const_cast<float*>(go.bv);
+  rp.loss_out = loss_out;
+  const wab::PolicyDims& d = p->dims;
+  const int64_t elems = (int64_t)d.h1 * (d.F + 1) + (int64_t)d.h2 * (d.h1 + 1) + (int64_t)d.h3 * (d.h2 + 1) +
+                        (int64_t)(d.A + 1) * (d.h3 + 1);
+  hipLaunchKernelGGL(wab::wab_policy_grad_reduce_kernel, dim3((unsigned)std::min<int64_t>((elems + 255) / 256, 4096)),
+                     dim3(256), 0, st, rp);
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+int wab_policy_grad_bad_actions(const wab_policy* p, const void* workspace, void* stream, uint64_t* out) {
+  g_err.clear();
+  if (!p || !workspace || !out) return fail(WAB_E_INVALID, "wab_policy_grad_bad_actions: NULL argument");
+  DeviceGuard guard(p->device);
+  uint32_t v = 0;
+  HIP_TRY(hipMemcpyAsync(&v, workspace, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  *out = v;
+  if (v != 0)
+    return fail(WAB_E_INVALID, "wab_policy_grad: " + std::to_string(v) + " rows had an action outside [0, " +
+                                   std::to_string(p->dims.A) + "); they were left out of the loss and the gradients");
+  return WAB_OK;
+}
+
+int wab_debug_policy_grad_plan(const wab_policy* p, int32_t chunk_rows, int32_t out[5]) {
+  g_err.clear();
+  if (!p || !out) return fail(WAB_E_INVALID, "wab_debug_policy_grad_plan: NULL argument");
+  const int64_t cr = grad_chunk_rows(chunk_rows);
+  if (cr < 0) return fail(WAB_E_INVALID, "wab_debug_policy_grad_plan: chunk_rows must be 0 or a positive multiple of 128");
+  const wab::GradPlan g = wab::grad_plan(p->dims);
+  out[0] = wab::kGradRows;
+  out[1] = g.slabs;
+  out[2] = (int32_t)cr;
+  out[3] = (int32_t)g.lds_total;
+  out[4] = 0;  // wab_policy_wgrad_kernel uses no LDS
+  return WAB_OK;
+}
+
+int wab_rollout_policy_fused(const wab_handle* h, const wab_policy* p) {
+  g_err.clear();
+  if (!h || !p) return fail(WAB_E_INVALID, "wab_rollout_policy_fused: NULL argument");
+  if (int rc = check_pair(h, p, "wab_rollout_policy_fused", 0)) return rc;
+  return roll_policy_plan(h, p, 1, false, nullptr, &g_err) ? 1 : 0;
+}
+
+int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int32_t T, const wab_obs* obs_seq,
+                       int8_t* actions, float* value, float* probs, float* reward, uint8_t* done, float* features,
+                       float* features_last, double gamma, const float* bootstrap, float* returns, void* stream) {
+  g_err.clear();
+  if (!h || !p) return fail(WAB_E_INVALID, "wab_rollout_policy: NULL argument");
+  if (T < 0) return fail(WAB_E_INVALID, "wab_rollout_policy: T must be >= 0");
+  if (!features0 || !actions || !reward || !done || !features_last || !obs_seq || !obs_seq->food_turns ||
+      !obs_seq->role || !obs_seq->status)
+    return fail(WAB_E_INVALID, "wab_rollout_policy: NULL argument (features0, actions, reward, done, features_last "
+                               "and the scalars of obs_seq are required)");
+  if (int rc = check_pair(h, p, "wab_rollout_policy", PAIR_RUNS | PAIR_FEATURES)) return rc;
+  const int F = p->dims.F;
+  const auto misaligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3u) != 0; };
+  if (misaligned4(features0) || (probs && misaligned4(probs)) || (value && misaligned4(value)))
+    return fail(WAB_E_INVALID, "wab_rollout_policy: features0, probs and value must be 4-byte aligned");
+  if (!aligned16(features_last) || (features && !aligned16(features)))
+    return fail(WAB_E_INVALID, "wab_rollout_policy: features and features_last must be 16-byte aligned");
+  if (obs_seq->planes && !aligned16(obs_seq->planes))
+    return fail(WAB_E_INVALID, "wab_rollout_policy: planes must be 16-byte aligned");
+  const int64_t B = h->p.B;
+  const size_t OB = (size_t)h->p.OB, BF = (size_t)B * (size_t)F;
+  if (T == 0 || B == 0) return WAB_OK;
+  const bool fused_returns = returns && T <= wab::kMaxFusedReturnSteps;
+  wab::RollPolicy rp;
+  bool fused = roll_policy_plan(h, p, T, fused_returns, &rp, nullptr);
+  if (obs_seq->planes && ((size_t)B * OB) % 16u != 0) fused = false;  // (the launch's 16-byte obs stores)
+  if (returns && !(fused && fused_returns) && h->rewards.n < 0)  // (checked before anything runs)
+    return fail(WAB_E_INVALID, "wab_rollout_policy: returns of this segment need the exact-reward scan, and two of "
+                               "the options' rewards round to the same float32 (pass returns = NULL)");
+  if (fused) {
+    // one launch: each workgroup runs its 64 envs through the T steps, the policy between them
+    // (wab_step_small<8, 11, FEAT, ROLL, .., POLICY>), the returns of the segment at its end
+    Params q = h->p;
+    bind_obs(q, obs_seq);
+    bind_step(q, actions, reward, done);
+    q.features = features_last;  // (non-null: the featurizer is on; the rows go where q.pol says)
+    q.n_steps = T;
+    if (fused_returns) {
+      q.returns = returns;
+      q.bootstrap = bootstrap;
+      q.gamma = gamma;
+    }
+    rp.features0 = features0;
+    rp.features = features;
+    rp.features_last = features_last;
+    rp.actions = actions;
+    rp.probs = probs;
+    rp.value = value;
+    rp.w = p->w;
+    rp.b = p->b;
+    q.pol = rp;
+    DeviceGuard guard(h->device);
+    ++h->rollout_launches;
+    launch_params(small_kernel(h, true, true, true), (unsigned)h->n_blocks, rp.total, (hipStream_t)stream, q);
+    HIP_TRY(hipGetLastError());
+    if (fused_returns || !returns) return WAB_OK;
+    return wab_discounted_returns_exact(h, reward, done, T, B, gamma, bootstrap, returns, stream);
+  }
+  // the 2 T calls; a step's rows go straight to their slice when there is one and it is aligned,
+  // else through the handle's pair of rows (alternating: step t reads one, writes the other)
+  ++h->rollout_step_calls;
+  const bool direct = features && (BF * 4u) % 16u == 0;
+  float* bounce = nullptr;
+  if (!direct && T > 1) {
+    bounce = bounce_rows(h, BF);
+    if (!bounce) return fail(WAB_E_NOMEM, "wab_rollout_policy: hipMalloc");
+  }
+  const size_t bounce_stride = (BF + 3u) & ~(size_t)3u;
+  if (features && features != features0) {
+    DeviceGuard guard(h->device);
+    HIP_TRY(hipMemcpyAsync(features, features0, BF * 4u, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  }
+  const float* cur = features0;
+  for (int32_t t = 0; t < T; ++t) {
+    const size_t tb = (size_t)t * (size_t)B;
+    int rc = wab_policy_act(h, p, cur, actions + tb, probs ? probs + tb * (size_t)p->dims.A : nullptr,
+                            value ? value + tb : nullptr, stream);
+    if (rc != WAB_OK) return rc;
+    ObsSlice s;
+    if ((rc = obs_slice(h, obs_seq, t, "wab_rollout_policy", &s)) != WAB_OK) return rc;
+    float* slice = features && t + 1 < T ? features + (size_t)(t + 1) * BF : nullptr;
+    float* dst = t + 1 == T ? features_last : direct ? slice : bounce + (size_t)(t & 1) * bounce_stride;
+    rc = wab_step_features(h, actions + tb, &s.o, reward + tb, done + tb, dst, stream);
+    if (rc != WAB_OK) return rc;
+    if ((rc = obs_slice_done(h, s, stream)) != WAB_OK) return rc;
+    if (slice && dst != slice) {
+      DeviceGuard guard(h->device);
+      HIP_TRY(hipMemcpyAsync(slice, dst, BF * 4u, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+    cur = dst;
+  }
+  if (!returns) return WAB_OK;
+  return wab_discounted_returns_exact(h, reward, done, T, B, gamma, bootstrap, returns, stream);
+}
+
+int wab_debug_policy_plan(const wab_policy* p, int32_t out[5]) {
+  g_err.clear();
+  if (!p || !out) return fail(WAB_E_INVALID, "wab_debug_policy_plan: NULL argument");
+  out[0] = p->lds.n_chunks;
+  out[1] = p->lds.KC;
+  out[2] = 16 * p->dims.KS1 - (p->lds.n_chunks - 1) * p->lds.KC;
+  out[3] = (int32_t)p->lds.total;
+  out[4] = policy_two_tiles(p->dims) ? 1 : 0;
+  return WAB_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // wab_episodes.h — parameters of the episode accounting and normalisation kernels
-// (wab_episodes.hip), shared with the host side in wab_capi.hip.
+// (wab_episodes.hip), shared with the host side in wab_capi_segment.hip.
 #pragma once
 
 #include <stdint.h>
@@ -40,5 +40,14 @@ struct EpisodeParams {
   uint32_t* local;       // workspace: [N] exclusive offset of each entry within its tile
   RewardTable tab;       // the inexact rewards, padded to the kernel's NE (wab_returns_kernel)
 };
+
+// the kernels (wab_episodes.hip), launched from wab_capi_segment.hip
+__global__ void wab_episode_count_kernel(EpisodeParams p);
+__global__ void wab_episode_scan_kernel(EpisodeParams p);
+template <int NE>
+__global__ void wab_episode_walk_kernel(EpisodeParams p);
+__global__ void wab_normalize_kernel(const float* x, const uint8_t* done, int32_t T, int64_t B, double eps, float* out);
+__global__ void wab_normalize_lds_kernel(const float* x, const uint8_t* done, int32_t T, int64_t B, double eps,
+                                         float* out);
 
 }  // namespace wab

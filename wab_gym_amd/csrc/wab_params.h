@@ -438,4 +438,25 @@ struct RenderParams {
   uint8_t* rgb;
 };
 
+// The kernels over these blocks, declared where both their definitions and the host code that
+// launches them (wab_capi*.hip) see the same signature.  Their instances are in the defining files.
+template <int MODE, int SLOTS, bool SMALL>
+__global__ void wab_kernel(Params p);  // wab_step.hip
+template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES = false, bool POLICY = false>
+__global__ void wab_step_small(Params p0);  // wab_step_small.hip
+template <int MODE, int SLOTS>
+__global__ void wab_step_wide(Params p0);  // wab_step_wide.hip
+template <int SLOTS, int FIXW>
+__global__ void wab_rollout_wide(Params p0);
+__global__ void wab_featurize_kernel(FeatParams p);  // wab_features.hip
+__global__ void wab_featurize_small_kernel(FeatParams p);
+template <int VEC, int NE>
+__global__ void wab_returns_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done, int32_t T,
+                                   int64_t B, double gamma, const float* __restrict__ bootstrap,
+                                   float* __restrict__ out, RewardTable tab);
+__global__ void wab_render_kernel(RenderParams p);        // wab_render.hip
+__global__ void wab_egocentric_kernel(EgoParams p);       // wab_egocentric.hip
+__global__ void wab_snapshot_pack(SnapParams p);          // wab_snapshot.hip
+__global__ void wab_snapshot_unpack(SnapParams p);
+
 }  // namespace wab

@@ -104,4 +104,9 @@ struct PolicyPackParams {
   float* b;
 };
 
+// the kernels (wab_policy.hip), launched from wab_capi_policy.hip
+__global__ void wab_policy_pack(PolicyPackParams p);
+template <bool TWO>
+__global__ void wab_policy_kernel(PolicyParams p);
+
 }  // namespace wab

@@ -181,4 +181,11 @@ struct GradReduceParams {
   float* loss_out;         // {policy, value, entropy, total}
 };
 
+// the kernels (wab_policy_grad.hip), launched from wab_capi_policy.hip
+__global__ void wab_policy_grad_pack(GradPackParams p);
+template <bool TWO>
+__global__ void wab_policy_bwd_kernel(GradBwdParams p);
+__global__ void wab_policy_wgrad_kernel(GradWgradParams p);
+__global__ void wab_policy_grad_reduce_kernel(GradReduceParams p);
+
 }  // namespace wab

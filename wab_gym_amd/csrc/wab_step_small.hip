@@ -1844,7 +1844,7 @@ __device__ __forceinline__ void roll_apply(Params& p, const RollSlices& r) {
 // POLICY (wab_rollout_policy; with FEAT and ROLL): the device policy chooses each step's actions
 // inside the launch (roll_policy); its fragments and accumulators sit next to the carried state,
 // so these instances take two waves per SIMD's registers
-template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES, bool POLICY = false>
+template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES, bool POLICY>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(POLICY ? 2 : ROLL ? 4 : 1))) void wab_step_small(Params p0) {
   static_assert(!POLICY || (FEAT && ROLL), "the policy build is a build of wab_rollout_features' kernel");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];

@@ -31,13 +31,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/wab_torus.h"
 #include "wab_device.h"
+#include "wab_host.h"
 
 // Diagnostic builds only (tools/ab_torus.sh; results wrong by design): WAB2_ABLATE bit 1 skips
 // the view computation of the records, bit 2 their global stores, bit 4 the bush-food bytes,
@@ -1418,31 +1417,17 @@ struct wab2_handle {
 
 namespace {
 
+using wab_host::DeviceGuard;
+
+// wab2_last_error's string, apart from wab_last_error's: HIP_TRY (wab_host.h) reports through
+// this file's fail
 thread_local std::string g_err2;
 
 int fail(int code, const std::string& msg) {
   g_err2 = msg;
   return code;
 }
-
-#define HIP_TRY2(expr)                                                                \
-  do {                                                                                \
-    hipError_t e_ = (expr);                                                           \
-    if (e_ != hipSuccess)                                                             \
-      return fail(WAB2_E_HIP, std::string(#expr " failed: ") + hipGetErrorString(e_)); \
-  } while (0)
-
-struct DeviceGuard2 {
-  int prev = -1;
-  explicit DeviceGuard2(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard2() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
+static_assert(WAB2_E_HIP == WAB_E_HIP, "HIP_TRY returns WAB_E_HIP");
 
 int record_size(const wab2_config* c) {
   const int N = c->num_ostriches + c->num_wolves + c->num_bushes;
@@ -1509,7 +1494,6 @@ const void* torus_kernel(const TParams& p) {
 uint32_t magic20(int n) { return n > 0 ? (uint32_t)(((1u << 20) + (uint32_t)n - 1u) / (uint32_t)n) : 0u; }
 
 void launch_torus(const wab2_handle* h, const TParams& p0, hipStream_t stream) {
-  const dim3 grid((unsigned)h->n_blocks), block(wab2::kThreads);
   TParams p = p0;
   p.magic_m = magic20(std::min(p.o1, p.NM) - p.o0);
   p.magic_b = magic20(p.o1 - std::max(p.o0, p.NM));
@@ -1518,20 +1502,8 @@ void launch_torus(const wab2_handle* h, const TParams& p0, hipStream_t stream) {
 #if WAB2_STAMPS
   p.stamps = (unsigned long long*)(uintptr_t)strtoull(getenv("WAB2_STAMPS_PTR") ? getenv("WAB2_STAMPS_PTR") : "0", nullptr, 0);
 #endif
-  if (fixed_counts(p)) {
-    hipLaunchKernelGGL((wab2::wab_torus_kernel<7, 1, 8, 16>), grid, block, h->lds, stream, p);
-    return;
-  }
-  switch ((p.N + 3) / 4) {
-    case 1: hipLaunchKernelGGL(wab2::wab_torus_kernel<1>, grid, block, h->lds, stream, p); break;
-    case 2: hipLaunchKernelGGL(wab2::wab_torus_kernel<2>, grid, block, h->lds, stream, p); break;
-    case 3: hipLaunchKernelGGL(wab2::wab_torus_kernel<3>, grid, block, h->lds, stream, p); break;
-    case 4: hipLaunchKernelGGL(wab2::wab_torus_kernel<4>, grid, block, h->lds, stream, p); break;
-    case 5: hipLaunchKernelGGL(wab2::wab_torus_kernel<5>, grid, block, h->lds, stream, p); break;
-    case 6: hipLaunchKernelGGL(wab2::wab_torus_kernel<6>, grid, block, h->lds, stream, p); break;
-    case 7: hipLaunchKernelGGL(wab2::wab_torus_kernel<7>, grid, block, h->lds, stream, p); break;
-    default: hipLaunchKernelGGL(wab2::wab_torus_kernel<8>, grid, block, h->lds, stream, p); break;
-  }
+  static_assert(wab2::kThreads == 256, "launch_params launches workgroups of 256");
+  wab_host::launch_params(torus_kernel(p), (unsigned)h->n_blocks, h->lds, stream, p);
 }
 
 }  // namespace
@@ -1563,7 +1535,7 @@ int wab2_create_at(const wab2_config* cfg, int64_t batch, uint64_t seed, int64_t
   // they are tiles of the world, [0, W) x [0, H)
   const std::string pv = check_positions(positions, batch, N, cfg->width - 1, cfg->height - 1, "wab2_create_at");
   if (!pv.empty()) return fail(WAB2_E_INVALID, pv);
-  DeviceGuard2 dg(device);
+  DeviceGuard dg(device);
   wab2_handle* h = new wab2_handle();
   h->device = device;
   TParams& p = h->p;
@@ -1615,18 +1587,9 @@ int wab2_create_at(const wab2_config* cfg, int64_t batch, uint64_t seed, int64_t
   if (e == hipSuccess) { e = alloc(&q, NBp * 4); p.turn = (int32_t*)q; }
   if (e == hipSuccess) { e = alloc(&q, NBp * 4); p.episode = (uint32_t*)q; }
   if (e == hipSuccess) { e = alloc(&q, 2 * sizeof(unsigned long long)); p.counters = (unsigned long long*)q; }
-  if (e == hipSuccess && h->lds > 64 * 1024) {
-    // the attribute is per kernel instance, which handles of other bush counts share: only ever
-    // raise it (a later, smaller handle must not lower the limit an earlier one launches with)
-    static std::mutex mu;
-    static std::map<const void*, size_t> lds_set;
-    std::lock_guard<std::mutex> lock(mu);
-    size_t& cur = lds_set[torus_kernel(p)];
-    if (h->lds > cur) {
-      e = hipFuncSetAttribute(torus_kernel(p), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds);
-      if (e == hipSuccess) cur = h->lds;
-    }
-  }
+  // (the attribute is per device and kernel instance, which handles of other bush counts share:
+  // raise_lds only ever raises it)
+  if (e == hipSuccess) e = wab_host::raise_lds(h->device, torus_kernel(p), h->lds);
   if (e == hipSuccess && positions) {
     const size_t bytes = (size_t)batch * p.N * 2 * sizeof(int32_t);
     e = alloc(&q, bytes);
@@ -1651,7 +1614,7 @@ int wab2_create_at(const wab2_config* cfg, int64_t batch, uint64_t seed, int64_t
 
 int wab2_destroy(wab2_handle* h) {
   if (!h) return WAB2_OK;
-  DeviceGuard2 dg(h->device);
+  DeviceGuard dg(h->device);
   (void)hipDeviceSynchronize();
   for (void* a : h->allocs) (void)hipFree(a);
   delete h;
@@ -1675,7 +1638,7 @@ int wab2_reset_at(wab2_handle* h, const uint8_t* mask, const int32_t* positions,
   const std::string pv = check_positions(positions, hp.B, hp.N, hp.W, hp.H, "wab2_reset_at");
   if (!pv.empty()) return fail(WAB2_E_INVALID, pv);
   h->next_entity = 0;  // reset_environment: num_entities_acted_this_turn = 0 (WAB_Environment2.py:117)
-  DeviceGuard2 dg(h->device);
+  DeviceGuard dg(h->device);
   TParams p = h->p;
   p.mask = mask;
   if (positions) {
@@ -1683,17 +1646,17 @@ int wab2_reset_at(wab2_handle* h, const uint8_t* mask, const int32_t* positions,
     const size_t bytes = (size_t)p.B * p.N * 2 * sizeof(int32_t);
     if (!h->pos) {
       void* q = nullptr;
-      HIP_TRY2(hipMalloc(&q, bytes));
+      HIP_TRY(hipMalloc(&q, bytes));
       h->allocs.push_back(q);
       h->pos = (int32_t*)q;
     }
-    HIP_TRY2(hipMemcpyAsync(h->pos, positions, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(h->pos, positions, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
     p.pos = h->pos;
   }
   hipLaunchKernelGGL(wab2::wab_torus_reset_kernel, dim3((unsigned)((p.B + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, p);
-  HIP_TRY2(hipGetLastError());
-  if (positions) HIP_TRY2(hipStreamSynchronize((hipStream_t)stream));  // the host array may go now
+  HIP_TRY(hipGetLastError());
+  if (positions) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the host array may go now
   return WAB2_OK;
 }
 
@@ -1706,7 +1669,7 @@ int wab2_rollout(wab2_handle* h, const int8_t* actions, int32_t T, uint8_t* obs,
   if (h->next_entity != 0)
     return fail(WAB2_E_INVALID, "wab2_step/wab2_rollout: a turn is half done (entity " +
                                     std::to_string(h->next_entity) + " acts next: wab2_take_action)");
-  DeviceGuard2 dg(h->device);
+  DeviceGuard dg(h->device);
   TParams p = h->p;
   p.T = T;
   p.actions = actions;
@@ -1716,7 +1679,7 @@ int wab2_rollout(wab2_handle* h, const int8_t* actions, int32_t T, uint8_t* obs,
   p.world_reset = world_reset;
   p.act_scalar = ((reinterpret_cast<uintptr_t>(actions) & 3u) == 0u && (p.B * p.N) % 4 == 0) ? 1 : 0;
   launch_torus(h, p, (hipStream_t)stream);
-  HIP_TRY2(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return WAB2_OK;
 }
 
@@ -1732,7 +1695,7 @@ int wab2_get_obs(wab2_handle* h, int32_t entity, uint8_t* obs, void* stream) {
     return fail(WAB2_E_INVALID, "wab2_get_obs: entity " + std::to_string(entity) +
                                     " has acted this turn or does not exist (World.get_observations asserts "
                                     "the entity has not acted, World.py:362)");
-  DeviceGuard2 dg(h->device);
+  DeviceGuard dg(h->device);
   TParams p = h->p;
   p.T = 1;
   p.a0 = p.a1 = entity;  // nothing acts
@@ -1744,7 +1707,7 @@ int wab2_get_obs(wab2_handle* h, int32_t entity, uint8_t* obs, void* stream) {
   p.done = nullptr;
   p.world_reset = nullptr;
   launch_torus(h, p, (hipStream_t)stream);
-  HIP_TRY2(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return WAB2_OK;
 }
 
@@ -1755,7 +1718,7 @@ int wab2_take_action(wab2_handle* h, int32_t entity, const int8_t* actions, floa
   if (entity != h->next_entity)
     return fail(WAB2_E_INVALID, "wab2_take_action: entity " + std::to_string(h->next_entity) +
                                     " acts next (entities act in id order, once per turn)");
-  DeviceGuard2 dg(h->device);
+  DeviceGuard dg(h->device);
   TParams p = h->p;
   p.T = 1;
   p.a0 = entity;
@@ -1767,7 +1730,7 @@ int wab2_take_action(wab2_handle* h, int32_t entity, const int8_t* actions, floa
   p.done = done;
   p.world_reset = world_reset;
   launch_torus(h, p, (hipStream_t)stream);
-  HIP_TRY2(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   h->next_entity = (entity + 1) % h->p.N;
   return WAB2_OK;
 }
@@ -1775,23 +1738,23 @@ int wab2_take_action(wab2_handle* h, int32_t entity, const int8_t* actions, floa
 int wab2_get_state(wab2_handle* h, int32_t* df_xy, int32_t* obj_xy, double* food, uint8_t* visible, uint8_t* status,
                    int32_t* turn, uint32_t* episode, void* stream) {
   if (!h) return fail(WAB2_E_INVALID, "handle is NULL");
-  DeviceGuard2 dg(h->device);
+  DeviceGuard dg(h->device);
   const TParams& p = h->p;
-  HIP_TRY2(hipStreamSynchronize((hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   const size_t Bp = (size_t)p.Bp, B = (size_t)p.B, N = (size_t)p.N;
   std::vector<int32_t> ox(Bp * N), oy(Bp * N), tn(Bp);
   std::vector<uint16_t> df(Bp * N);
   std::vector<double> fd(Bp * (p.NM ? p.NM : 1));
   std::vector<uint8_t> bf(Bp * (p.NB ? p.NB : 1)), os(Bp * (p.NO ? p.NO : 1));
   std::vector<uint32_t> ep(Bp);
-  HIP_TRY2(hipMemcpy(ox.data(), p.ox, ox.size() * 4, hipMemcpyDeviceToHost));
-  HIP_TRY2(hipMemcpy(oy.data(), p.oy, oy.size() * 4, hipMemcpyDeviceToHost));
-  HIP_TRY2(hipMemcpy(df.data(), p.df, df.size() * 2, hipMemcpyDeviceToHost));
-  HIP_TRY2(hipMemcpy(fd.data(), p.food, fd.size() * 8, hipMemcpyDeviceToHost));
-  HIP_TRY2(hipMemcpy(bf.data(), p.bfood, bf.size(), hipMemcpyDeviceToHost));
-  HIP_TRY2(hipMemcpy(os.data(), p.ost, os.size(), hipMemcpyDeviceToHost));
-  HIP_TRY2(hipMemcpy(tn.data(), p.turn, tn.size() * 4, hipMemcpyDeviceToHost));
-  HIP_TRY2(hipMemcpy(ep.data(), p.episode, ep.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ox.data(), p.ox, ox.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(oy.data(), p.oy, oy.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(df.data(), p.df, df.size() * 2, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(fd.data(), p.food, fd.size() * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(bf.data(), p.bfood, bf.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(os.data(), p.ost, os.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tn.data(), p.turn, tn.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ep.data(), p.episode, ep.size() * 4, hipMemcpyDeviceToHost));
   for (size_t b = 0; b < B; ++b) {
     for (size_t e = 0; e < N; ++e) {
       const size_t a = e * Bp + b, q = b * N + e;
@@ -1815,10 +1778,10 @@ int wab2_get_state(wab2_handle* h, int32_t* df_xy, int32_t* obj_xy, double* food
 
 int wab2_get_counters(wab2_handle* h, wab2_counters* out, void* stream) {
   if (!h || !out) return fail(WAB2_E_INVALID, "handle or out is NULL");
-  DeviceGuard2 dg(h->device);
-  HIP_TRY2(hipStreamSynchronize((hipStream_t)stream));
+  DeviceGuard dg(h->device);
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   unsigned long long c[2];
-  HIP_TRY2(hipMemcpy(c, h->p.counters, sizeof(c), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(c, h->p.counters, sizeof(c), hipMemcpyDeviceToHost));
   out->turns = c[0];
   out->resets = c[1];
   return WAB2_OK;
