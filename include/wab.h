@@ -48,6 +48,8 @@
  *   wab_policy_act        <- Policy.forward + select_action's sample  actor_critic.py:76-125
  *   wab_rollout_policy    <- T steps of actor_critic.main's loop with   actor_critic.py:108-125,
  *                            select_action choosing each action          185-200
+ *   wab_policy_grad       <- finish_episode's loss and loss.backward()  actor_critic.py:148-165
+ *   wab_policy_adam_step  <- optimizer.step() (optim.Adam)              actor_critic.py:104, 165
  */
 #ifndef WAB_H_
 #define WAB_H_
@@ -59,7 +61,7 @@
 extern "C" {
 #endif
 
-#define WAB_ABI_VERSION 12
+#define WAB_ABI_VERSION 13
 #define WAB_MAX_WOLF_SLOTS 32 /* largest per-env live-wolf slot count (wab_config.wolf_slots) */
 #define WAB_MAX_VIEW 63       /* largest odd width/height accepted */
 
@@ -563,6 +565,76 @@ int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions,
 /* The number of rows the latest wab_policy_grad on this workspace left out for their action
  * (synchronises `stream`).  WAB_E_INVALID, with the count in the message, when it is not 0. */
 int wab_policy_grad_bad_actions(const wab_policy* p, const void* workspace, void* stream, uint64_t* out);
+
+/* ---- device policy: the optimizer step (actor_critic.py:104, 165) ----------------------- */
+
+/* torch.optim.Adam's step (AdamW's with `decoupled`) over the ten parameter tensors, with a
+ * global-norm clip (torch's clip_grad_norm_ rule) and no step at all on a non-finite gradient
+ * (the two guards actor_critic.py:112-113 asks for), and the re-pack of the bf16 image
+ * wab_policy_act reads: after the call no wab_policy_load is needed.
+ *
+ * Numeric contract.  Flat order: the ten tensors in wab_policy_weights' order, each row-major; P
+ * elements in all.  No operation is contracted into an fma; every operation named is IEEE
+ * correctly rounded, round to nearest even.
+ *   Norm:   q_i = (double)g_i * (double)g_i (exact);  S = the adjacent-pair tree sum of q,
+ *           zero-padded to the next power of two >= P (x'[i] = x[2i] + x[2i+1] until one value is
+ *           left);  norm = sqrt(S) in double;  grad_norm = (float)norm.
+ *   Skip:   S not finite (some g_i is NaN or +-Inf): params, moments, the image, step and the
+ *           beta powers keep their bits; skipped += 1; grad_norm and clip_scale are still written.
+ *   Clip:   c = 1.0f if max_grad_norm <= 0, else with r = max_grad_norm / (norm + 1e-6) in
+ *           double, c = (float)(r < 1.0 ? r : 1.0) (a NaN norm gives 1).  clip_scale = c.
+ *   Scalars (double unless cast):
+ *           b1p = (step == 0 ? 1.0 : beta1_pow) * beta1;  b2p likewise;
+ *           a = (float)(lr / (1.0 - b1p));  r2 = sqrtf((float)(1.0 - b2p));
+ *           b1f = (float)beta1, omb1 = (float)(1.0 - beta1), b2f, omb2 likewise, epsf = (float)eps,
+ *           wdf = (float)weight_decay, decayf = (float)(1.0 - lr * weight_decay);
+ *           then step += 1 and beta1_pow = b1p, beta2_pow = b2p are stored.  The beta powers are
+ *           running products, so that they are the same bits everywhere (pow() is not).
+ *   Per element, float32, in this order:
+ *           g = g_i * c
+ *           weight_decay != 0, not decoupled:  g = g + wdf * p
+ *           weight_decay != 0, decoupled:      p = p * decayf
+ *           m = b1f * m + omb1 * g
+ *           v = b2f * v + (omb2 * g) * g
+ *           den = sqrtf(v) / r2 + epsf
+ *           p = p - a * (m / den)
+ *           the image's element of p = bf16(p), nearest even, as wab_policy_load rounds it.
+ * Results are bitwise reproducible: no atomics, every sum has one order, a function of the shape.
+ * This is Adam as torch computes it up to the order of float32 roundings (torch: step_size / bias
+ * corrections folded differently); DESIGN.md has both measured against float64. */
+typedef struct wab_adam_config {   /* host, by pointer */
+  double lr, beta1, beta2, eps, weight_decay;
+  double max_grad_norm;            /* <= 0: no clip */
+  int32_t decoupled;               /* nonzero: AdamW's decay */
+} wab_adam_config;
+
+typedef struct wab_adam_state {    /* DEVICE memory, caller-owned, 8-byte aligned; all-zero bytes = a fresh optimizer */
+  uint64_t step, skipped;          /* steps taken; calls skipped for a non-finite gradient */
+  double beta1_pow, beta2_pow;     /* beta^step as running products (read only when step > 0) */
+  float grad_norm, clip_scale;     /* of the latest call */
+  uint64_t reserved;
+} wab_adam_state;
+
+/* Bytes of workspace wab_policy_adam_step needs (it depends on the policy's shape alone); 0 with
+ * wab_last_error set for NULL. */
+size_t wab_policy_adam_workspace(const wab_policy* p);
+
+/* params, exp_avg, exp_avg_sq: ten device arrays each in wab_policy_weights' layout, read and
+ * written through (the const of the struct's fields notwithstanding, as wab_policy_grad's
+ * grads_out); grads: read.  No array may overlap another.  state: device.  workspace: device
+ * memory, 8-byte aligned, contents meaningless before and after.
+ * Three stream-ordered launches (four where the network has more than 2^20 parameters): no
+ * allocation, no synchronisation, safe to capture in a hipGraph; cfg is read on the host at the
+ * call (a captured graph keeps its values).
+ * The image's padding must already be zero, as wab_policy_load leaves it: WAB_E_STATE before the
+ * first wab_policy_load.  WAB_E_INVALID, before anything is launched, for a NULL argument or
+ * array pointer, lr < 0, a beta outside [0, 1), eps <= 0, weight_decay < 0, a NaN among them, a
+ * workspace smaller than wab_policy_adam_workspace's answer, or a misaligned array, state or
+ * workspace. */
+int wab_policy_adam_step(wab_policy* p, const wab_policy_weights* params, const wab_policy_weights* grads,
+                         const wab_policy_weights* exp_avg, const wab_policy_weights* exp_avg_sq,
+                         const wab_adam_config* cfg, wab_adam_state* state, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ---- closed-loop rollout: policy and env step, T steps (actor_critic.py:108-125, 185-200) -- */
 

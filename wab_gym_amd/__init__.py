@@ -26,10 +26,10 @@ def __getattr__(name):
         from .snapshot import EnvSnapshot
 
         return EnvSnapshot
-    if name == "DevicePolicy":
-        from .policy import DevicePolicy
+    if name in ("DevicePolicy", "DeviceAdam"):
+        from . import policy
 
-        return DevicePolicy
+        return getattr(policy, name)
     if name == "EpisodeMonitor":
         from .monitor import EpisodeMonitor
 
@@ -41,5 +41,5 @@ def __getattr__(name):
     raise AttributeError(name)
 
 
-__all__ = ["BatchedWolvesAndBushesEnv", "DevicePolicy", "EnvSnapshot", "default_game_options",
+__all__ = ["BatchedWolvesAndBushesEnv", "DevicePolicy", "DeviceAdam", "EnvSnapshot", "default_game_options",
            "make_config", "bush_thresholds"]

@@ -25,6 +25,7 @@ EXPORTED = [
     "wab_episode_stats_workspace", "wab_episode_stats_update", "wab_normalize_episode_returns",
     "wab_gae", "wab_whiten_workspace", "wab_whiten", "wab_debug_gae_plan",
     "wab_policy_grad_workspace", "wab_policy_grad", "wab_policy_grad_bad_actions", "wab_debug_policy_grad_plan",
+    "wab_policy_adam_workspace", "wab_policy_adam_step",
     # include/wab_torus.h: the Environment 2.0 torus world
     "wab2_abi_version", "wab2_last_error", "wab2_record_size", "wab2_create", "wab2_destroy",
     "wab2_batch", "wab2_reset", "wab2_step", "wab2_rollout", "wab2_get_state", "wab2_get_counters",
@@ -34,7 +35,7 @@ EXPORTED = [
 ABI2_VERSION = 1
 OBS_SAME_BUFFER, OBS_FRESH_BUFFER = 0, 1  # wab_set_obs_placement
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 SNAPSHOT_MAGIC, SNAPSHOT_VERSION = 0x53424157, 1  # 'WABS' (wab_snapshot_info)
 
 
@@ -72,6 +73,17 @@ VALUE_LOSS = {"smooth_l1": 0, "mse": 1}  # WAB_VALUE_LOSS_*
 class WabPolicyLoss(ctypes.Structure):
     _fields_ = [("value_coef", ctypes.c_float), ("entropy_coef", ctypes.c_float), ("value_loss", ctypes.c_int32),
                 ("scale", ctypes.c_float), ("accumulate", ctypes.c_int32), ("chunk_rows", ctypes.c_int32)]
+
+
+class WabAdamConfig(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_grad_norm")] \
+        + [("decoupled", ctypes.c_int32)]
+
+
+class WabAdamState(ctypes.Structure):  # device memory; this mirror reads a copy of it
+    _fields_ = [("step", ctypes.c_uint64), ("skipped", ctypes.c_uint64), ("beta1_pow", ctypes.c_double),
+                ("beta2_pow", ctypes.c_double), ("grad_norm", ctypes.c_float), ("clip_scale", ctypes.c_float),
+                ("reserved", ctypes.c_uint64)]
 
 
 class WabError(RuntimeError):
@@ -154,6 +166,9 @@ def load():
     L.wab_policy_grad.argtypes = [P, P, P, P, P, I64, P, P, P, P, P, P, P, ctypes.c_size_t, P]
     L.wab_policy_grad_bad_actions.argtypes = [P, P, P, P]
     L.wab_debug_policy_grad_plan.argtypes = [P, I32, P]
+    L.wab_policy_adam_workspace.argtypes = [P]
+    L.wab_policy_adam_workspace.restype = ctypes.c_size_t
+    L.wab_policy_adam_step.argtypes = [P, P, P, P, P, P, P, P, ctypes.c_size_t, P]
     L.wab2_abi_version.restype = ctypes.c_int
     L.wab2_last_error.restype = ctypes.c_char_p
     L.wab2_record_size.argtypes = [P]
@@ -172,7 +187,7 @@ def load():
     L.wab2_take_action.argtypes = [P, I32, P, P, P, P, P]
     for name in EXPORTED:
         if name not in ("wab_abi_version", "wab_last_error", "wab_batch", "wab_step_kernel", "wab_snapshot_hash",
-                        "wab_episode_stats_workspace", "wab_whiten_workspace", "wab_policy_grad_workspace", "wab2_abi_version", "wab2_last_error", "wab2_batch"):
+                        "wab_episode_stats_workspace", "wab_whiten_workspace", "wab_policy_grad_workspace", "wab_policy_adam_workspace", "wab2_abi_version", "wab2_last_error", "wab2_batch"):
             getattr(L, name).restype = ctypes.c_int
     if L.wab_abi_version() != ABI_VERSION:
         raise WabError("libwab_hip.so ABI %d != %d" % (L.wab_abi_version(), ABI_VERSION))

@@ -1,6 +1,7 @@
 // wab_capi_policy.hip — the C-ABI's device policy: create, load, act (wab_policy.hip), loss and
-// parameter gradients (wab_policy_grad.hip) and the closed-loop rollout wab_rollout_policy (the
-// POLICY instances of wab_step_small.hip, or act and step in turns).
+// parameter gradients (wab_policy_grad.hip), the optimizer step (wab_policy_opt.hip) and the
+// closed-loop rollout wab_rollout_policy (the POLICY instances of wab_step_small.hip, or act and
+// step in turns).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +10,7 @@
 
 #include "wab_host.h"
 #include "wab_policy_grad.h"
+#include "wab_policy_opt.h"
 
 using namespace wab_host;
 
@@ -377,6 +379,125 @@ int wab_debug_policy_grad_plan(const wab_policy* p, int32_t chunk_rows, int32_t 
   out[2] = (int32_t)cr;
   out[3] = (int32_t)g.lds_total;
   out[4] = 0;  // wab_policy_wgrad_kernel uses no LDS
+  return WAB_OK;
+}
+
+// ---- device policy: the optimizer step (wab_policy_opt.hip) --------------------------------
+
+size_t wab_policy_adam_workspace(const wab_policy* p) {
+  g_err.clear();
+  if (!p) {
+    g_err = "wab_policy_adam_workspace: NULL policy";
+    return 0;
+  }
+  return (size_t)wab::adam_levels(wab::adam_flat(p->dims).off[wab::kAdamTensors]).total * sizeof(double);
+}
+
+int wab_policy_adam_step(wab_policy* p, const wab_policy_weights* params, const wab_policy_weights* grads,
+                         const wab_policy_weights* exp_avg, const wab_policy_weights* exp_avg_sq,
+                         const wab_adam_config* cfg, wab_adam_state* state, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+  g_err.clear();
+  if (!p || !params || !grads || !exp_avg || !exp_avg_sq || !cfg || !state || !workspace)
+    return fail(WAB_E_INVALID, "wab_policy_adam_step: NULL argument");
+  const wab_policy_weights* const sets[4] = {params, grads, exp_avg, exp_avg_sq};
+  const char* const set_names[4] = {"params", "grads", "exp_avg", "exp_avg_sq"};
+  for (int s = 0; s < 4; ++s) {
+    const wab_policy_weights& w = *sets[s];
+    const float* const q[wab::kAdamTensors] = {w.w1, w.b1, w.w2, w.b2, w.w3, w.b3, w.wa, w.ba, w.wv, w.bv};
+    for (const float* x : q) {
+      if (!x) return fail(WAB_E_INVALID, std::string("wab_policy_adam_step: every pointer of ") + set_names[s] + " must be set");
+      if ((reinterpret_cast<uintptr_t>(x) & 3u) != 0)
+        return fail(WAB_E_INVALID, "wab_policy_adam_step: float arrays must be 4-byte aligned");
+    }
+  }
+  // (written so that a NaN is refused too)
+  if (!(cfg->lr >= 0.0)) return fail(WAB_E_INVALID, "wab_policy_adam_step: lr must be >= 0");
+  if (!(cfg->beta1 >= 0.0 && cfg->beta1 < 1.0) || !(cfg->beta2 >= 0.0 && cfg->beta2 < 1.0))
+    return fail(WAB_E_INVALID, "wab_policy_adam_step: beta1 and beta2 must be in [0, 1)");
+  if (!(cfg->eps > 0.0)) return fail(WAB_E_INVALID, "wab_policy_adam_step: eps must be > 0");
+  if (!(cfg->weight_decay >= 0.0)) return fail(WAB_E_INVALID, "wab_policy_adam_step: weight_decay must be >= 0");
+  if (cfg->max_grad_norm != cfg->max_grad_norm)
+    return fail(WAB_E_INVALID, "wab_policy_adam_step: max_grad_norm is NaN");
+  wab::AdamFlat flat = wab::adam_flat(p->dims);
+  const wab::AdamLevels lv = wab::adam_levels(flat.off[wab::kAdamTensors]);
+  if (workspace_bytes < (size_t)lv.total * sizeof(double))
+    return fail(WAB_E_INVALID, "wab_policy_adam_step: the workspace has " + std::to_string(workspace_bytes) +
+                                   " bytes, wab_policy_adam_workspace asks for " +
+                                   std::to_string((size_t)lv.total * sizeof(double)));
+  if ((reinterpret_cast<uintptr_t>(workspace) & 7u) != 0 || (reinterpret_cast<uintptr_t>(state) & 7u) != 0)
+    return fail(WAB_E_INVALID, "wab_policy_adam_step: the workspace and the state must be 8-byte aligned");
+  if (!p->loaded) return fail(WAB_E_STATE, "wab_policy_adam_step: call wab_policy_load first");
+
+  static_assert(sizeof(wab_adam_state) == 48 && sizeof(wab::AdamState) == sizeof(wab_adam_state),
+                "wab_adam_state's layout is part of the ABI");
+  wab::AdamConsts c;
+  c.lr = cfg->lr;
+  c.beta1 = cfg->beta1;
+  c.beta2 = cfg->beta2;
+  c.max_grad_norm = cfg->max_grad_norm;
+  c.b1f = (float)cfg->beta1;
+  c.omb1 = (float)(1.0 - cfg->beta1);
+  c.b2f = (float)cfg->beta2;
+  c.omb2 = (float)(1.0 - cfg->beta2);
+  c.epsf = (float)cfg->eps;
+  c.wdf = (float)cfg->weight_decay;
+  c.decayf = (float)(1.0 - cfg->lr * cfg->weight_decay);
+  c.decay = cfg->weight_decay != 0.0 ? (cfg->decoupled ? 2 : 1) : 0;
+
+  DeviceGuard guard(p->device);
+  hipStream_t st = (hipStream_t)stream;
+  double* const part = static_cast<double*>(workspace);
+  wab::AdamNormParams np;
+  np.flat = flat;
+  const float* const gs[wab::kAdamTensors] = {grads->w1, grads->b1, grads->w2, grads->b2, grads->w3,
+                                              grads->b3, grads->wa, grads->ba, grads->wv, grads->bv};
+  for (int t = 0; t < wab::kAdamTensors; ++t) np.flat.g[t] = gs[t];
+  np.part = part + lv.offset[0];
+  hipLaunchKernelGGL(wab::wab_adam_norm_kernel, dim3(lv.count[0]), dim3(256), 0, st, np);
+  HIP_TRY(hipGetLastError());
+  for (int l = 1; l < lv.n_levels; ++l) {
+    wab::AdamMidParams mp;
+    mp.in = part + lv.offset[l - 1];
+    mp.n_in = lv.count[l - 1];
+    mp.out = part + lv.offset[l];
+    hipLaunchKernelGGL(wab::wab_adam_mid_kernel, dim3(lv.count[l]), dim3(256), 0, st, mp);
+    HIP_TRY(hipGetLastError());
+  }
+  const int last = lv.n_levels - 1;
+
+  wab::AdamUpdateParams up;
+  up.d = p->dims;
+  up.c = c;
+  up.part = part + lv.offset[last];
+  up.n_part = lv.count[last];
+  up.state = reinterpret_cast<const wab::AdamState*>(state);
+  up.gw1 = grads->w1; up.gb1 = grads->b1; up.gw2 = grads->w2; up.gb2 = grads->b2; up.gw3 = grads->w3;
+  up.gb3 = grads->b3; up.gwa = grads->wa; up.gba = grads->ba; up.gwv = grads->wv; up.gbv = grads->bv;
+  const auto rw = [](const float* x) { return const_cast<float*>(x); };
+  up.w1 = rw(params->w1); up.b1 = rw(params->b1); up.w2 = rw(params->w2); up.b2 = rw(params->b2);
+  up.w3 = rw(params->w3); up.b3 = rw(params->b3); up.wa = rw(params->wa); up.ba = rw(params->ba);
+  up.wv = rw(params->wv); up.bv = rw(params->bv);
+  up.m1 = rw(exp_avg->w1); up.mb1 = rw(exp_avg->b1); up.m2 = rw(exp_avg->w2); up.mb2 = rw(exp_avg->b2);
+  up.m3 = rw(exp_avg->w3); up.mb3 = rw(exp_avg->b3); up.ma = rw(exp_avg->wa); up.mba = rw(exp_avg->ba);
+  up.mv = rw(exp_avg->wv); up.mbv = rw(exp_avg->bv);
+  up.v1 = rw(exp_avg_sq->w1); up.vb1 = rw(exp_avg_sq->b1); up.v2 = rw(exp_avg_sq->w2); up.vb2 = rw(exp_avg_sq->b2);
+  up.v3 = rw(exp_avg_sq->w3); up.vb3 = rw(exp_avg_sq->b3); up.va = rw(exp_avg_sq->wa); up.vba = rw(exp_avg_sq->ba);
+  up.vv = rw(exp_avg_sq->wv); up.vbv = rw(exp_avg_sq->bv);
+  up.w = p->w;
+  up.b = p->b;
+  // one thread per image element up to 2^16 workgroups (16 M elements), a grid-stride loop beyond
+  const unsigned blocks = (unsigned)std::min<uint32_t>((p->dims.w_total + 255u) / 256u, 65536u);
+  hipLaunchKernelGGL(wab::wab_adam_update_kernel, dim3(blocks), dim3(256), 0, st, up);
+  HIP_TRY(hipGetLastError());
+
+  wab::AdamFinishParams fp;
+  fp.c = c;
+  fp.part = up.part;
+  fp.n_part = up.n_part;
+  fp.state = reinterpret_cast<wab::AdamState*>(state);
+  hipLaunchKernelGGL(wab::wab_adam_finish_kernel, dim3(1), dim3(256), 0, st, fp);
+  HIP_TRY(hipGetLastError());
   return WAB_OK;
 }
 

@@ -7,12 +7,15 @@ action sampled in the same launch (wab_policy_act, wab_gym_amd/csrc/wab_policy.h
     policy.loss_and_grad(features, actions, weight, target, into=model)   # finish_episode's loss
                                                  # and loss.backward() (wab_policy_grad)
 
-The optimizer stays in torch: loss_and_grad fills each parameter's .grad, the caller steps and
-reloads.
+    opt = DeviceAdam(policy, model, lr=3e-4)     # optimizer.step() and the re-pack in HIP
+    opt.step()                                   # (wab_policy_adam_step): no policy.load after it
 
-What the kernels compute is `reference_forward` and `reference_loss_and_grad` below (the numeric
-contracts, in torch on the CPU) and `sample_reference` (the sampling rule, in numpy); the tests
-check the kernels against them.
+loss_and_grad fills each parameter's .grad; the caller steps with DeviceAdam, or with a torch
+optimizer and reloads.
+
+What the kernels compute is `reference_forward`, `reference_loss_and_grad` (the numeric
+contracts, in torch on the CPU), `reference_adam_step` (in numpy) and `sample_reference` (the
+sampling rule, in numpy) below; the tests check the kernels against them.
 The reference's `+ U(0, 1) / 100` input noise (actor_critic.py:189) is not reproduced.
 """
 from __future__ import annotations
@@ -193,6 +196,176 @@ def check_loss_args(shape, features, actions, weight, target, value_loss="smooth
     if n >= 1 << 31:
         raise ValueError("loss_and_grad takes fewer than 2^31 rows")
     return n
+
+
+ADAM_TENSORS = tuple("%s.%s" % (n, part) for n in LAYERS for part in ("weight", "bias"))  # the flat order
+
+
+def pair_tree_sum(q):
+    """The adjacent-pair tree sum of a 1-D float64 array, zero-padded to the next power of two:
+    x = x[0::2] + x[1::2] until one value is left (the order wab_policy_adam_step's norm is
+    summed in)."""
+    q = np.asarray(q, np.float64).ravel()
+    n = 1
+    while n < q.size:
+        n *= 2
+    x = np.zeros(n, np.float64)
+    x[:q.size] = q
+    with np.errstate(all="ignore"):
+        while x.size > 1:
+            x = x[0::2] + x[1::2]
+    return x[0]
+
+
+def check_adam_args(lr, betas, eps, weight_decay, max_grad_norm):
+    """The argument checks of wab_policy_adam_step, on the host (ValueError)."""
+    if not float(lr) >= 0.0:
+        raise ValueError("lr must be >= 0, not %r" % (lr,))
+    if len(betas) != 2 or not all(0.0 <= float(b) < 1.0 for b in betas):
+        raise ValueError("betas must be two numbers in [0, 1), not %r" % (betas,))
+    if not float(eps) > 0.0:
+        raise ValueError("eps must be > 0, not %r" % (eps,))
+    if not float(weight_decay) >= 0.0:
+        raise ValueError("weight_decay must be >= 0, not %r" % (weight_decay,))
+    if float(max_grad_norm) != float(max_grad_norm):
+        raise ValueError("max_grad_norm is NaN")
+
+
+def adam_beta_powers(step, betas):
+    """beta1^step and beta2^step as the optimizer state keeps them: `step` sequential double
+    multiplications each (0.0 for step 0, where they are not read)."""
+    out = []
+    for b in betas:
+        p = 0.0
+        for i in range(int(step)):
+            p = (1.0 if i == 0 else p) * float(b)
+        out.append(p)
+    return tuple(out)
+
+
+def adam_fresh_state():
+    """wab_adam_state of a fresh optimizer (all-zero bytes), as a dict."""
+    return {"step": 0, "skipped": 0, "beta1_pow": 0.0, "beta2_pow": 0.0, "grad_norm": np.float32(0.0),
+            "clip_scale": np.float32(0.0)}
+
+
+def reference_adam_step(params, grads, exp_avg, exp_avg_sq, state, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                        weight_decay=0.0, decoupled=False, max_grad_norm=0.0):
+    """wab_policy_adam_step's numeric contract (include/wab.h) in numpy: float32 arrays and
+    scalars, float64 where the contract says so, the norm's sum by pair_tree_sum.  params, grads,
+    exp_avg, exp_avg_sq: the ten arrays each in ADAM_TENSORS order; state: a dict as
+    adam_fresh_state().  Nothing is modified; returns (params, exp_avg, exp_avg_sq, state), new."""
+    check_adam_args(lr, betas, eps, weight_decay, max_grad_norm)
+    f32 = np.float32
+
+    def arrays(xs, what):
+        xs = [np.array(x.detach().cpu().numpy() if hasattr(x, "detach") else x, copy=True) for x in xs]
+        if len(xs) != len(ADAM_TENSORS) or any(x.dtype != np.float32 for x in xs):
+            raise ValueError("%s must be ten float32 arrays" % what)
+        return xs
+
+    p, g, m, v = (arrays(x, n) for x, n in ((params, "params"), (grads, "grads"), (exp_avg, "exp_avg"),
+                                            (exp_avg_sq, "exp_avg_sq")))
+    st = dict(state)
+    with np.errstate(all="ignore"):
+        flat = np.concatenate([x.ravel() for x in g]).astype(np.float64)
+        S = pair_tree_sum(flat * flat)
+        norm = np.sqrt(np.float64(S))
+        st["grad_norm"] = f32(norm)
+        c = f32(1.0)
+        if max_grad_norm > 0:
+            r = np.float64(max_grad_norm) / (norm + np.float64(1e-6))
+            c = f32(r if r < 1.0 else 1.0)
+        st["clip_scale"] = c
+        if not np.isfinite(S):
+            st["skipped"] = int(st["skipped"]) + 1
+            return p, m, v, st
+        beta1, beta2 = float(betas[0]), float(betas[1])
+        b1p = (1.0 if st["step"] == 0 else float(st["beta1_pow"])) * beta1
+        b2p = (1.0 if st["step"] == 0 else float(st["beta2_pow"])) * beta2
+        a = f32(float(lr) / (1.0 - b1p))
+        r2 = np.sqrt(f32(1.0 - b2p))
+        b1f, omb1, b2f, omb2 = f32(beta1), f32(1.0 - beta1), f32(beta2), f32(1.0 - beta2)
+        epsf, wdf, decayf = f32(eps), f32(weight_decay), f32(1.0 - float(lr) * float(weight_decay))
+        st["step"] = int(st["step"]) + 1
+        st["beta1_pow"], st["beta2_pow"] = b1p, b2p
+        for i in range(len(p)):
+            gi = g[i] * c
+            if weight_decay != 0 and not decoupled:
+                gi = gi + wdf * p[i]
+            if weight_decay != 0 and decoupled:
+                p[i] = p[i] * decayf
+            m[i] = b1f * m[i] + omb1 * gi
+            v[i] = b2f * v[i] + (omb2 * gi) * gi
+            den = np.sqrt(v[i]) / r2 + epsf
+            p[i] = p[i] - a * (m[i] / den)
+            assert p[i].dtype == np.float32 and m[i].dtype == np.float32 and v[i].dtype == np.float32
+    return p, m, v, st
+
+
+def adam_state_dict(step, exp_avg, exp_avg_sq, order, lr, betas, eps, weight_decay, decoupled, max_grad_norm):
+    """An optimizer state in torch.optim.Adam's state_dict() layout: state[order[k]] = {"step",
+    "exp_avg", "exp_avg_sq"} for tensor k of ADAM_TENSORS (order[k]: its index in
+    model.parameters()), one param group with Adam's keys (AdamW's with `decoupled`) plus
+    "max_grad_norm".  A fresh optimizer (step 0) has an empty state, as torch's."""
+    import torch
+
+    kind = torch.optim.AdamW if decoupled else torch.optim.Adam
+    group = dict(kind([torch.zeros(1)]).defaults)  # every key this torch's step() reads
+    group.update(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
+                 weight_decay=float(weight_decay), max_grad_norm=float(max_grad_norm),
+                 params=list(range(len(order))))
+    state = {}
+    if int(step) > 0:
+        for k, i in enumerate(order):
+            state[int(i)] = {"step": torch.tensor(float(step), dtype=torch.float32),
+                             "exp_avg": exp_avg[k].detach().clone(), "exp_avg_sq": exp_avg_sq[k].detach().clone()}
+    return {"state": state, "param_groups": [group]}
+
+
+def parse_adam_state_dict(sd, order, shapes):
+    """What DeviceAdam.load_state_dict takes from a state_dict() of torch.optim.Adam / AdamW or of
+    DeviceAdam over the same model: (step, exp_avg, exp_avg_sq, hyper), the moments in
+    ADAM_TENSORS order (None for an empty state), hyper a dict of lr, betas, eps, weight_decay,
+    decoupled and, where the dict has it, max_grad_norm.  ValueError for another layout: more than
+    one param group, amsgrad or maximize, a state that covers some tensors only, steps that differ
+    between tensors, or moments of another shape."""
+    if not isinstance(sd, dict) or "state" not in sd or "param_groups" not in sd:
+        raise ValueError("not an optimizer state_dict (state, param_groups)")
+    if len(sd["param_groups"]) != 1:
+        raise ValueError("DeviceAdam takes one param group, the state_dict has %d" % len(sd["param_groups"]))
+    group = sd["param_groups"][0]
+    if sorted(group["params"]) != sorted(int(i) for i in order):
+        raise ValueError("the state_dict's param group does not hold the model's ten parameters")
+    if group.get("amsgrad") or group.get("maximize"):
+        raise ValueError("amsgrad and maximize are not supported")
+    hyper = {"lr": float(group["lr"]), "betas": (float(group["betas"][0]), float(group["betas"][1])),
+             "eps": float(group["eps"]), "weight_decay": float(group["weight_decay"]),
+             "decoupled": bool(group.get("decoupled_weight_decay", False))}
+    if "max_grad_norm" in group:
+        hyper["max_grad_norm"] = float(group["max_grad_norm"])
+    check_adam_args(hyper["lr"], hyper["betas"], hyper["eps"], hyper["weight_decay"], hyper.get("max_grad_norm", 0.0))
+    state = sd["state"]
+    if len(state) == 0:
+        return 0, None, None, hyper
+    if sorted(state.keys()) != sorted(int(i) for i in order):
+        raise ValueError("the state_dict's state covers parameters %s, the model's are %s"
+                         % (sorted(state.keys()), sorted(order)))
+    steps = {float(state[int(i)]["step"]) for i in order}
+    if len(steps) != 1:
+        raise ValueError("the parameters' step counts differ: %s" % sorted(steps))
+    step = steps.pop()
+    if step != int(step) or step < 0:
+        raise ValueError("step must be a non-negative integer, not %r" % step)
+    m, v = [], []
+    for k, i in enumerate(order):
+        for key, dst in (("exp_avg", m), ("exp_avg_sq", v)):
+            x = state[int(i)][key]
+            if tuple(x.shape) != tuple(shapes[k]):
+                raise ValueError("%s of %s has shape %s, expected %s" % (key, ADAM_TENSORS[k], tuple(x.shape),
+                                                                        tuple(shapes[k])))
+            dst.append(x)
+    return int(step), m, v, hyper
 
 
 def keyed_u(seed, env_ids, episode, turn):
@@ -402,3 +575,134 @@ class DevicePolicy:
             self.close()
         except Exception:
             pass
+
+
+class DeviceAdam:
+    """torch.optim.Adam (AdamW with decoupled=True) for the ten parameters of a DevicePolicy's
+    model, stepped on the device by wab_policy_adam_step: the global-norm clip (max_grad_norm > 0,
+    torch's clip_grad_norm_ rule), no step at all on a non-finite gradient, the Adam update of the
+    float32 parameters in place (model.state_dict() stays the truth) and the policy's bf16 image
+    in the same launch, so no policy.load(model) follows a step().  What it computes is
+    reference_adam_step.  Three launches on the env's stream, no host synchronisation: step() can
+    be captured in a graph (which then keeps the lr of the capture).
+
+        opt = DeviceAdam(policy, model, lr=3e-4, max_grad_norm=0.5)
+        policy.loss_and_grad(..., into=model);  opt.step()
+
+    The policy must hold the model's current weights (policy.load(model), as DevicePolicy(model,
+    env) leaves it); parameters changed by other hands need a policy.load(model) again."""
+
+    def __init__(self, policy, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False,
+                 max_grad_norm=0.0):
+        import torch
+
+        self._torch = torch
+        check_adam_args(lr, betas, eps, weight_decay, max_grad_norm)
+        self.policy = policy
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.weight_decay, self.decoupled = float(weight_decay), bool(decoupled)
+        self.max_grad_norm = float(max_grad_norm)
+        dev = policy.env.device
+        if shape_of(model) != policy.shape:
+            raise ValueError("the model's layers differ from the policy's %s" % (policy.shape,))
+        self.params = []
+        for name in ADAM_TENSORS:
+            layer, part = name.split(".")
+            prm = getattr(getattr(model, layer), part)
+            if prm.dtype != torch.float32 or prm.device != dev or not prm.is_contiguous():
+                raise ValueError("%s must be a contiguous float32 tensor on %s (it is updated in place)" % (name, dev))
+            self.params.append(prm)
+        all_params = list(model.parameters())
+        self._order = []
+        for name, prm in zip(ADAM_TENSORS, self.params):
+            idx = [i for i, q in enumerate(all_params) if q is prm]
+            if len(idx) != 1:
+                raise ValueError("%s is not one of model.parameters()" % name)
+            self._order.append(idx[0])
+        if len(all_params) != len(self.params):
+            raise ValueError("the model has %d parameters; DeviceAdam steps the ten of the policy's five Linears "
+                             "and would leave the others untrained" % len(all_params))
+        self.exp_avg = [torch.zeros_like(p) for p in self.params]
+        self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
+        L = _lib.load()
+        need = int(L.wab_policy_adam_workspace(policy._p))
+        if need == 0:
+            _lib.check(-1, "wab_policy_adam_workspace")
+        self._ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        self._state = torch.zeros(ctypes.sizeof(_lib.WabAdamState) // 8, dtype=torch.int64, device=dev)
+        self._w = [_lib.WabPolicyWeights(*[x.data_ptr() for x in xs])
+                   for xs in (self.params, self.exp_avg, self.exp_avg_sq)]
+
+    def _config(self):
+        check_adam_args(self.lr, self.betas, self.eps, self.weight_decay, self.max_grad_norm)
+        return _lib.WabAdamConfig(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                                  self.max_grad_norm, 1 if self.decoupled else 0)
+
+    def step(self):
+        """One optimizer step from each parameter's .grad (RuntimeError if one is missing)."""
+        t = self._torch
+        ptrs = []
+        for name, prm in zip(ADAM_TENSORS, self.params):
+            g = prm.grad
+            if g is None:
+                raise RuntimeError("%s has no .grad: run loss_and_grad(..., into=model) (or backward()) before "
+                                   "step()" % name)
+            if g.dtype != t.float32 or g.device != prm.device or not g.is_contiguous() or g.shape != prm.shape:
+                raise ValueError("%s.grad must be a contiguous float32 tensor of the parameter's shape and device"
+                                 % name)
+            ptrs.append(g.data_ptr())
+        gw = _lib.WabPolicyWeights(*ptrs)
+        cfg = self._config()
+        pol = self.policy
+        _lib.check(_lib.load().wab_policy_adam_step(pol._p, ctypes.addressof(self._w[0]), ctypes.addressof(gw),
+                                                    ctypes.addressof(self._w[1]), ctypes.addressof(self._w[2]),
+                                                    ctypes.addressof(cfg), self._state.data_ptr(), self._ws.data_ptr(),
+                                                    self._ws.numel() * 8, pol.env._stream()), "wab_policy_adam_step")
+
+    def zero_grad(self, set_to_none=False):
+        """As torch's, with set_to_none False by default: loss_and_grad(into=model) overwrites the
+        gradients, and a captured graph needs them to stay where they are."""
+        for prm in self.params:
+            if prm.grad is not None:
+                if set_to_none:
+                    prm.grad = None
+                else:
+                    prm.grad.zero_()
+
+    def _read_state(self):
+        raw = self._state.cpu().numpy().tobytes()  # (synchronises)
+        return _lib.WabAdamState.from_buffer_copy(raw)
+
+    def stats(self):
+        """{"step", "skipped", "grad_norm", "clip_scale"}: steps taken, calls skipped for a
+        non-finite gradient, and the latest call's gradient norm and clip factor.  Synchronises."""
+        s = self._read_state()
+        return {"step": int(s.step), "skipped": int(s.skipped), "grad_norm": float(s.grad_norm),
+                "clip_scale": float(s.clip_scale)}
+
+    def state_dict(self):
+        """torch.optim.Adam's state_dict() layout (adam_state_dict), so that a checkpoint moves
+        between the two optimizers.  Synchronises."""
+        s = self._read_state()
+        return adam_state_dict(int(s.step), self.exp_avg, self.exp_avg_sq, self._order, self.lr, self.betas, self.eps,
+                               self.weight_decay, self.decoupled, self.max_grad_norm)
+
+    def load_state_dict(self, sd):
+        """Take the step count, moments and hyperparameters of a state_dict() of DeviceAdam or of
+        torch.optim.Adam / AdamW over the same model; the beta powers are rebuilt by `step`
+        sequential double multiplications.  The skipped count starts again at 0."""
+        t = self._torch
+        step, m, v, hyper = parse_adam_state_dict(sd, self._order, [tuple(p.shape) for p in self.params])
+        self.lr, self.betas, self.eps = hyper["lr"], hyper["betas"], hyper["eps"]
+        self.weight_decay, self.decoupled = hyper["weight_decay"], hyper["decoupled"]
+        self.max_grad_norm = hyper.get("max_grad_norm", self.max_grad_norm)
+        for k in range(len(self.params)):
+            if m is None:
+                self.exp_avg[k].zero_()
+                self.exp_avg_sq[k].zero_()
+            else:
+                self.exp_avg[k].copy_(m[k].to(t.float32))
+                self.exp_avg_sq[k].copy_(v[k].to(t.float32))
+        b1p, b2p = adam_beta_powers(step, self.betas)
+        host = _lib.WabAdamState(step, 0, b1p, b2p, 0.0, 0.0, 0)
+        self._state.copy_(t.from_numpy(np.frombuffer(bytes(host), dtype=np.int64).copy()))
