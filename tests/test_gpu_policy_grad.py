@@ -2,7 +2,9 @@
 (wab_gym_amd.policy.reference_loss_and_grad):
 
 1. every term in its place, bit for bit: one live row, dW_l the outer product of db_l and x_{l-1};
-2. sums across tiles, slabs and chunks, bit for bit: two live rows, fl32(term_1 + term_2);
+2. sums across tiles, slabs and chunks, bit for bit: two live rows, fl32(term_1 + term_2).  The
+   two rows lie in row blocks 0 and 1, two slabs, so this is the reducer's add; sums inside a
+   slab (a slab's second block, N > 128 slabs) are tests/test_gpu_policy_grad_slabs.py's;
 3. chunk_rows changes no bit, and neither does a second run;
 4. every tensor, loss and row output within half of E (what the bf16 contract itself costs
    against stock fp32 autograd on the same inputs, tests/policy_grad_cases.py);

@@ -115,6 +115,57 @@ def test_what_the_contract_costs_against_fp32_autograd():
             assert 0 < E[k] < float("inf"), (n, k, E[k])
 
 
+def test_slab_table_is_the_plans_formula():
+    """tests/test_gpu_policy_grad_slabs.py builds every N from S: the table, the formula's mirror
+    and the header's constants agree, and each N puts the blocks where its test says."""
+    tasks = {(1, 1, 1, 1, 5): 4, (17, 33, 33, 33, 5): 7, "odd": 6, "ref": 35, (449, 129, 150, 128, 6): 50, "wide": 41}
+    for net, S in pgc.SLABS.items():
+        assert pgc.plan_tasks(net) == tasks[net] and pgc.plan_slabs(net) == S, net
+        n = pgc.fold_rows_n(S)
+        live = pgc.fold_live_rows(S)
+        assert [b for b, _ in live] == [0, S, 2 * S, 1, S + 1, 5, (n - 1) // 128] and live[-1][1] == n - 1
+        assert all(i // 128 == b for b, i in live) and {i % 128 for _, i in live} >= {0, 31, 32, 127}
+        blocks = (pgc.two_per_slab_n(S) + 127) // 128
+        assert min(len(range(s, blocks, S)) for s in range(S)) == 2
+    src = open(os.path.join(os.path.dirname(HEADER), "..", "wab_gym_amd", "csrc", "wab_policy_grad.h")).read()
+    assert re.search(r"kGradMaxSlabs = 64;", src) and re.search(r"int s = \(2048 \+ t - 1\) / t;", src)
+    assert re.search(r"kGradDefaultChunk = 32768;", src)
+
+
+def test_fold_orders_of_the_slab_cases():
+    """pgc.fold on terms whose three orders give three different fp32 results."""
+    S, e = 3, np.float32(2.0 ** -24)
+    one = np.float32(1.0)
+    # slab 0 holds blocks 0, 3, 6; slab 1 block 1
+    terms = {0: np.array([one, one]), 3: np.array([e, e]), 6: np.array([e, -one]), 1: np.array([0, e])}
+    terms = {b: v.astype(np.float32) for b, v in terms.items()}
+    up = np.float32(1.0 + 2.0 ** -23)
+    # column 0: (1 + e) + e = 1, but (e + e) + 1 = 1 + 2^-23.  Column 1: slab 0 is ((1 + e) - 1) = 0 or
+    # ((-1 + e) + 1) = e, then slab 1's e; in one accumulator 1 + e + e - 1 = 0
+    assert np.array_equal(pgc.fold(terms, S, "slabs"), np.array([one, e], np.float32))
+    assert np.array_equal(pgc.fold(terms, S, "descending"), np.array([up, 2 * e], np.float32))
+    assert np.array_equal(pgc.fold(terms, S, "flat"), np.array([one, 0], np.float32))
+    assert np.array_equal(pgc.fold(terms, S, "slabs", 0.25), np.array([0.25, e / 4], np.float32))
+    assert pgc.fold_f64({0: 1.0, 3: 2.0 ** -53, 6: 2.0 ** -53, 1: 2.0 ** -52}, S) == 1.0 + 2.0 ** -52
+
+
+def test_mfma_accumulate_model_gives_the_recorded_results():
+    """pgc.mfma_accumulate against what the instruction returned on an MI355X
+    (tests/golden/make_golden_mfma.py): every record, among them those where fl32(C + a b) is
+    another float32, with C under the product and above it."""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mfma_accumulate.npz"))
+    c, a, b, d = z["c"], z["a"], z["b"], z["d"]
+    assert len(c) >= 16384 and bool((c == 0).any())
+    assert np.array_equal(pgc.mfma_accumulate(c, a, b), d)
+    rne = (c.astype(np.float64) + a.astype(np.float64) * b.astype(np.float64)).astype(np.float32)
+    ec, ep = np.frexp(c)[1], np.frexp(a)[1] + np.frexp(b)[1] - 1
+    other = rne != d
+    assert int((other & (ec < ep)).sum()) > 100 and int((other & (ec > ep + 8)).sum()) > 0
+    # a product alone, or an accumulator alone, comes back as it is
+    assert np.array_equal(pgc.mfma_accumulate(np.zeros_like(a), a, b), a * b)
+    assert np.array_equal(pgc.mfma_accumulate(c, a, np.zeros_like(b)), c)
+
+
 def test_header_and_mirror_carry_the_gradient_abi():
     src = open(HEADER).read()
     version = int(re.search(r"#define\s+WAB_ABI_VERSION\s+(\d+)", src).group(1))
