@@ -84,7 +84,8 @@ bool roll_policy_plan(const wab_handle* h, const wab_policy* p, int32_t T, bool 
   q.features = reinterpret_cast<float*>(16);  // (layout only)
   q.returns = reinterpret_cast<float*>(16);
   q.n_steps = wab::kMaxFusedReturnSteps;
-  if (wab::roll_policy_lds(p->dims, wab::small_layout(q).total * 4u).total > h->lds_max)
+  const wab::RollPolicy rp = wab::roll_policy_lds(p->dims, wab::small_layout(q).total * 4u);
+  if (rp.reg_a + rp.lds.total > h->lds_max)
     return no("the kernel's LDS exceeds the device's limit per workgroup");
   if (out) {
     q.n_steps = T;
@@ -118,7 +119,7 @@ int wab_policy_create(const wab_policy_shape* shape, int device, wab_policy** ou
   if (!p) return fail(WAB_E_NOMEM, "wab_policy_create: out of host memory");
   p->device = device;
   p->dims = wab::policy_dims(shape->in_features, shape->h1, shape->h2, shape->h3, shape->n_actions);
-  p->lds = wab::policy_lds(p->dims);
+  p->lds = wab::policy_lds(p->dims, wab::kPolicyEnvs, wab::kPolicyLdsBudget);
   DeviceGuard guard(device);
   // the kernel's dynamic LDS can exceed the 64 KB default (the attribute is a maximum per device
   // and kernel, so it is set to the device's limit, whatever other policies on the device need)
@@ -320,7 +321,7 @@ int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions,
     const int64_t rows = std::min<int64_t>(cr, N - row0);
     const unsigned blocks = (unsigned)((rows + wab::kGradRows - 1) / wab::kGradRows);
     bp.row0 = row0;
-    launch_params(bwd, blocks, g.lds_total, st, bp);
+    launch_params(bwd, blocks, g.lds.total, st, bp);
     HIP_TRY(hipGetLastError());
     wp.row0 = row0;
     wp.n_blocks = (int32_t)blocks;
@@ -377,7 +378,7 @@ int wab_debug_policy_grad_plan(const wab_policy* p, int32_t chunk_rows, int32_t 
   out[0] = wab::kGradRows;
   out[1] = g.slabs;
   out[2] = (int32_t)cr;
-  out[3] = (int32_t)g.lds_total;
+  out[3] = (int32_t)g.lds.total;
   out[4] = 0;  // wab_policy_wgrad_kernel uses no LDS
   return WAB_OK;
 }
@@ -561,7 +562,7 @@ int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int
     q.pol = rp;
     DeviceGuard guard(h->device);
     ++h->rollout_launches;
-    launch_params(small_kernel(h, true, true, true), (unsigned)h->n_blocks, rp.total, (hipStream_t)stream, q);
+    launch_params(small_kernel(h, true, true, true), (unsigned)h->n_blocks, rp.reg_a + rp.lds.total, (hipStream_t)stream, q);
     HIP_TRY(hipGetLastError());
     if (fused_returns || !returns) return WAB_OK;
     return wab_discounted_returns_exact(h, reward, done, T, B, gamma, bootstrap, returns, stream);

@@ -58,9 +58,8 @@ constexpr int kStampStride = 48;
 // input image [64][KC + 8], then X2; region B holds X1, then X3 (as PolicyLds, for 64 envs).
 struct RollPolicy {
   PolicyDims d;
-  int32_t KC, n_chunks;                      // input columns per chunk (a multiple of 16), chunks
-  int32_t pitch_in, pitch1, pitch2, pitch3;  // elements
-  uint32_t reg_a, reg_b, total;              // byte offsets of the regions in the workgroup's LDS, its bytes
+  PolicyLds lds;            // for 64 envs, chunks of kPolicyMaxChunk columns; offsets from reg_a
+  uint32_t reg_a;           // byte offset of region A in the workgroup's LDS
   const float* features0;   // [B][F]: what actions[0] is chosen from
   float* features;          // [T][B][F] or null: slice t is what actions[t] was chosen from
   float* features_last;     // [B][F]: the features after the last step
@@ -75,18 +74,8 @@ struct RollPolicy {
 __host__ __device__ inline RollPolicy roll_policy_lds(const PolicyDims& d, uint32_t base) {
   RollPolicy r = {};
   r.d = d;
-  r.pitch1 = 32 * d.NT1 + 8;
-  r.pitch2 = 32 * d.NT2 + 8;
-  r.pitch3 = 32 * d.NT3 + 8;
-  const int kpad = 16 * d.KS1;
-  r.n_chunks = (kpad + kPolicyMaxChunk - 1) / kPolicyMaxChunk;
-  r.KC = ((kpad + r.n_chunks - 1) / r.n_chunks + 15) / 16 * 16;
-  r.pitch_in = r.KC + 8;
-  const uint32_t rows = 64u * 2u;  // bytes per element column of 64 envs
-  const uint32_t chunk = rows * (uint32_t)r.pitch_in, x2 = rows * (uint32_t)r.pitch2;
+  r.lds = policy_lds(d, 64, kPolicyLdsNoBudget);
   r.reg_a = (base + 15u) & ~15u;
-  r.reg_b = r.reg_a + (chunk > x2 ? chunk : x2);
-  r.total = r.reg_b + rows * (uint32_t)(r.pitch1 > r.pitch3 ? r.pitch1 : r.pitch3);
   return r;
 }
 

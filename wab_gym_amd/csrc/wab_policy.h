@@ -48,9 +48,11 @@ __host__ __device__ inline PolicyDims policy_dims(int F, int h1, int h2, int h3,
   return d;
 }
 
-// LDS of wab_policy_kernel: region A holds the input chunk [128][KC + 8] bf16 during layer 1,
-// then X2 [128][32 NT2 + 8]; region B holds X1, then X3.  Row pitches are an odd number of
-// 16-byte units, so the 16-byte fragment reads of 8 consecutive rows hit 8 different bank groups.
+// LDS of the forward pass for a workgroup of `envs` envs: region A holds the input chunk
+// [envs][KC + 8] bf16 during layer 1, then X2 [envs][32 NT2 + 8]; region B holds X1, then X3.  Row
+// pitches are an odd number of 16-byte units, so the 16-byte fragment reads of 8 consecutive rows
+// hit 8 different bank groups.  The one derivation for wab_policy_kernel, wab_policy_bwd_kernel
+// (GradPlan) and the rollout's policy phase (RollPolicy, behind the step's own LDS).
 struct PolicyLds {
   int32_t KC, n_chunks;               // columns per chunk (a multiple of 16), chunks
   int32_t pitch_in, pitch1, pitch2, pitch3;  // elements
@@ -58,17 +60,20 @@ struct PolicyLds {
   uint32_t total;                     // bytes
 };
 
-__host__ __device__ inline PolicyLds policy_lds(const PolicyDims& d) {
+constexpr uint32_t kPolicyLdsBudget = 80u * 1024u;  // act, grad: two workgroups per CU
+constexpr uint32_t kPolicyLdsNoBudget = 0xFFFFFFFFu;  // rollout: chunks of kPolicyMaxChunk, whatever their bytes
+
+// `budget`: the bytes the chunk is sized to together with region B (at least X2's bytes, which
+// region A holds anyway, at least one k-step, at most kPolicyMaxChunk columns)
+__host__ __device__ inline PolicyLds policy_lds(const PolicyDims& d, int envs, uint32_t budget) {
   PolicyLds L;
   L.pitch1 = 32 * d.NT1 + 8;
   L.pitch2 = 32 * d.NT2 + 8;
   L.pitch3 = 32 * d.NT3 + 8;
-  const uint32_t rows = (uint32_t)kPolicyEnvs * 2u;
+  const uint32_t rows = (uint32_t)envs * 2u;  // bytes per element column
   const uint32_t region_b = rows * (uint32_t)(L.pitch1 > L.pitch3 ? L.pitch1 : L.pitch3);
   const uint32_t x2 = rows * (uint32_t)L.pitch2;
-  // the chunk as wide as two workgroups per CU allow (80 KB each), at least X2's bytes (region A
-  // holds X2 anyway) and at least one k-step
-  uint32_t budget = region_b < 80u * 1024u ? 80u * 1024u - region_b : 0u;
+  budget = region_b < budget ? budget - region_b : 0u;
   if (budget < x2) budget = x2;
   int kc_max = ((int)(budget / rows) - 8) / 16 * 16;
   if (kc_max < 16) kc_max = 16;

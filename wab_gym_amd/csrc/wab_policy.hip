@@ -100,61 +100,29 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_kernel(PolicyPara
   uint4 hdr = make_uint4(0u, 0u, 0u, 0u);
   if (sampler) hdr = p.hdr[env0 + my_env];
 
-  // ---- layer 1: chunks of KC input columns through LDS; wave w holds tiles w and w + 4
-  pol_f32x16 acc0[4], acc1[4];
-  pol_zero(acc0);
-  if (TWO) pol_zero(acc1);
-  const int KC = p.lds.KC, pitch_in = p.lds.pitch_in;
-  const int kpad = 16 * d.KS1;
+  // ---- layer 1: chunks of KC input columns through region A -> X1 (region B)
+  pol_layer1<4, TWO>(
+      d, p.lds, wimg, regA, wave, lane,
+      [&](int k0, int kn) {
+        pol_stage_rows<kPolicyEnvs>(p.features + (size_t)env0 * (size_t)d.F, d.F, n_env, k0, kn, regA, p.lds.pitch_in,
+                                    wave, lane, [](int, int, float, bool) {});
+      },
+      [] { __syncthreads(); },
+      [&](const pol_f32x16(&acc)[4], int t, int) { pol_store<false>(acc, p.b + d.b1, t, regB, p.lds.pitch1, lane); });
   uint4 wf[kPolicyMaxKs];
-  const uint4* const w1t = wimg + (d.w1 >> 3) + (size_t)wave * (size_t)d.KS1 * 64u + (size_t)lane;
-  for (int c = 0; c < p.lds.n_chunks; ++c) {
-    const int k0 = c * KC;
-    const int kn = kpad - k0 < KC ? kpad - k0 : KC;  // columns of this chunk (a multiple of 16)
-    const int ks0 = k0 >> 4, nks = kn >> 4;
-    if (wave < d.NT1) pol_load_frags(wf, w1t + (size_t)ks0 * 64u, nks);
-    if (c > 0) __syncthreads();  // the last chunk's fragments have been read
-    // wave w loads rows w, w + 4, ...: a lane takes one column of 16 rows at a time, the 16 loads
-    // issued together (addresses clamped into the batch, so none is conditional; rows past the
-    // batch and the pad columns are stored as zeros)
-    for (int kl = lane; kl < kn; kl += 64) {
-      const int k = k0 + kl;
-      const bool kin = k < d.F;
-      const float* col = p.features + (size_t)env0 * (size_t)d.F + (size_t)(kin ? k : d.F - 1);
-      constexpr int kRows = 16;  // (32 in flight measured the same: 55.9-56.2 against 55.8-56.0 us)
-      for (int eb = 0; eb < kPolicyEnvs / 4; eb += kRows) {
-        float v[kRows];
-#pragma unroll
-        for (int i = 0; i < kRows; ++i) {
-          const int e = wave + 4 * (eb + i);
-          v[i] = col[(size_t)(e < n_env ? e : n_env - 1) * (size_t)d.F];
-        }
-#pragma unroll
-        for (int i = 0; i < kRows; ++i) {
-          const int e = wave + 4 * (eb + i);
-          regA[(size_t)e * (size_t)pitch_in + (size_t)kl] = (uint16_t)((kin && e < n_env) ? pol_bf16(v[i]) : 0u);
-        }
-      }
-    }
-    __syncthreads();
-    const uint16_t* x = regA + (size_t)r * (size_t)pitch_in + 8 * h;
-    if (wave < d.NT1) pol_mma(acc0, wf, nks, x, pitch_in);
-    if (TWO && wave + 4 < d.NT1) {
-      pol_load_frags(wf, w1t + ((size_t)4 * (size_t)d.KS1 + (size_t)ks0) * 64u, nks);
-      pol_mma(acc1, wf, nks, x, pitch_in);
-    }
-  }
-  if (wave < d.NT1) pol_store<false>(acc0, p.b + d.b1, wave, regB, p.lds.pitch1, lane);
-  if (TWO && wave + 4 < d.NT1) pol_store<false>(acc1, p.b + d.b1, wave + 4, regB, p.lds.pitch1, lane);
   const uint4* const w2 = wimg + (d.w2 >> 3), * const w3 = wimg + (d.w3 >> 3);
   if (wave < d.NT2) pol_load_frags(wf, w2 + (size_t)wave * (size_t)d.KS2 * 64u + (size_t)lane, d.KS2);
   __syncthreads();  // X1 complete; region A free
 
   // ---- layer 2: X1 (region B) -> X2 (region A); layer 3: X2 -> X3 (region B), clamped
-  pol_layer<false, 4>(wf, w2, p.b + d.b2, d.NT2, d.KS2, regB, p.lds.pitch1, regA, p.lds.pitch2, wave, lane);
+  pol_layer<4, true>(wf, w2, d.NT2, d.KS2, regB, p.lds.pitch1, wave, lane, [&](const pol_f32x16(&acc)[4], int t, int) {
+    pol_store<false>(acc, p.b + d.b2, t, regA, p.lds.pitch2, lane);
+  });
   if (wave < d.NT3) pol_load_frags(wf, w3 + (size_t)wave * (size_t)d.KS3 * 64u + (size_t)lane, d.KS3);
   __syncthreads();
-  pol_layer<true, 4>(wf, w3, p.b + d.b3, d.NT3, d.KS3, regA, p.lds.pitch2, regB, p.lds.pitch3, wave, lane);
+  pol_layer<4, true>(wf, w3, d.NT3, d.KS3, regA, p.lds.pitch2, wave, lane, [&](const pol_f32x16(&acc)[4], int t, int) {
+    pol_store<true>(acc, p.b + d.b3, t, regB, p.lds.pitch3, lane);
+  });
   pol_load_frags(wf, wimg + (d.wh >> 3) + (size_t)lane, d.KS4);
   __syncthreads();
 

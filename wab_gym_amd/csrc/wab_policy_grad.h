@@ -30,9 +30,9 @@ constexpr int kGradDefaultChunk = 32768;  // rows per chunk: the bf16 workspace 
 struct GradPlan {
   PolicyDims d;
   // wab_policy_bwd_kernel's LDS, wab_policy_kernel's two regions: region A holds the input chunk,
-  // then X_2, then D_4 [128][24], then D_2; region B X_1, X_3, then D_3
-  int32_t KC, n_chunks, pitch_in, pitch1, pitch2, pitch3, pitch4;
-  uint32_t off_b, lds_total;
+  // then X_2, then D_4 [128][pitch4], then D_2; region B X_1, X_3, then D_3
+  PolicyLds lds;
+  int32_t pitch4;
   // transposed image (uint16 units) and its k-steps
   uint32_t wt1, wt2, wt3, wt_total;
   int32_t KT1, KT2, KT3;  // ceil(h2 / 16), ceil(h3 / 16), 1
@@ -49,26 +49,8 @@ struct GradPlan {
 __host__ __device__ inline GradPlan grad_plan(const PolicyDims& d) {
   GradPlan g;
   g.d = d;
-  g.pitch1 = 32 * d.NT1 + 8;
-  g.pitch2 = 32 * d.NT2 + 8;
-  g.pitch3 = 32 * d.NT3 + 8;
-  g.pitch4 = kGradHeadUnits + 8;
-  const uint32_t rows = (uint32_t)kGradRows * 2u;
-  const uint32_t region_b = rows * (uint32_t)(g.pitch1 > g.pitch3 ? g.pitch1 : g.pitch3);
-  const uint32_t a_min = rows * (uint32_t)g.pitch2;  // (>= D_4's 6 KB: pitch2 >= 40)
-  // the input chunk as wide as two workgroups per CU allow, as policy_lds chooses it
-  uint32_t budget = region_b < 80u * 1024u ? 80u * 1024u - region_b : 0u;
-  if (budget < a_min) budget = a_min;
-  int kc_max = ((int)(budget / rows) - 8) / 16 * 16;
-  if (kc_max < 16) kc_max = 16;
-  if (kc_max > kPolicyMaxChunk) kc_max = kPolicyMaxChunk;
-  const int kpad = 16 * d.KS1;
-  g.n_chunks = (kpad + kc_max - 1) / kc_max;
-  g.KC = ((kpad + g.n_chunks - 1) / g.n_chunks + 15) / 16 * 16;
-  g.pitch_in = g.KC + 8;
-  const uint32_t chunk = rows * (uint32_t)g.pitch_in;
-  g.off_b = chunk > a_min ? chunk : a_min;
-  g.lds_total = g.off_b + region_b;
+  g.lds = policy_lds(d, kGradRows, kPolicyLdsBudget);
+  g.pitch4 = kGradHeadUnits + 8;  // (D_4's 6 KB fit region A: X_2's pitch is >= 40)
 
   g.KT1 = (d.h2 + 15) / 16;
   g.KT2 = (d.h3 + 15) / 16;

@@ -3,9 +3,9 @@
 // stored rows (features, action, weight, value target).  gfx950.
 //
 // Numeric contract (wab_gym_amd/policy.py reference_loss_and_grad states the same in torch):
-//   * forward: wab_policy_act's, through the same pol_* functions (wab_policy_dev.h); the hidden
-//     epilogue below repeats pol_store's operations in its order, so x_l and the value have
-//     wab_policy_act's bits;
+//   * forward: wab_policy_act's, through the same pol_* functions (wab_policy_dev.h): the layer-1
+//     chunk loop, the tile passes, pol_store (the epilogue below is a hook on it) and pol_softmax,
+//     so x_l, the value and the probabilities have wab_policy_act's bits;
 //   * head, fp32, per row: p = the forward's probabilities, log p_k = (logit_k - max) - logf(sum),
 //     H = -sum_k p_k log p_k, g_logit_k = weight (p_k - [k = a]) + entropy_coef p_k (log p_k + H),
 //     g_v = value_coef l'(v - target), l smooth_l1 (beta 1) or 0.5 d^2;
@@ -62,44 +62,22 @@ __global__ __launch_bounds__(256) void wab_policy_grad_pack(GradPackParams p) {
 }
 
 // ------------------------------------------------------------------------ epilogues
-// pol_store's value (the same operations in the same order) into the next layer's LDS image and
-// the workspace, and the masks: bit (g & 1) * 16 + 4 mt + i of sb[g >> 1] is z >= 0, of cb the
-// same for -4 <= leaky_relu(z) <= 4.  Rows past n_env go to the workspace as zeros.
+// pol_store with the workspace column and the masks as its hook: bit (g & 1) * 16 + 4 mt + i of
+// sb[g >> 1] is z >= 0, of cb the same for -4 <= leaky_relu(z) <= 4.  Rows past n_env go to the
+// workspace as zeros.
 template <bool CLAMP>
 __device__ __forceinline__ void grad_fwd_store(const pol_f32x16 (&acc)[4], const float* __restrict__ bias, int tile,
                                                uint16_t* xn, int pitch, int lane, int n_env, uint16_t* wsx,
                                                int64_t cr, uint32_t (&sb)[2], uint32_t (&cb)[2]) {
-  const int r = lane & 31, h = lane >> 5;
   sb[0] = sb[1] = 0u;
   cb[0] = cb[1] = 0u;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const int n = 32 * tile + 8 * g + 4 * h;
-    const float4 bv = *reinterpret_cast<const float4*>(bias + n);
-    const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      uint32_t o[4];
-      const bool row_in = mt * 32 + r < n_env;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float v = acc[mt][4 * g + i] + bb[i];
-        const uint32_t bit = 1u << ((g & 1) * 16 + 4 * mt + i);
-        if (v >= 0.0f) sb[g >> 1] |= bit;
-        v = v >= 0.0f ? v : 0.01f * v;
-        if (CLAMP) {
-          if (v >= -4.0f && v <= 4.0f) cb[g >> 1] |= bit;
-          v = fminf(fmaxf(v, -4.0f), 4.0f);
-        }
-        o[i] = pol_bf16(v);
-        wsx[(size_t)(n + i) * (size_t)cr + (size_t)(mt * 32 + r)] = (uint16_t)(row_in ? o[i] : 0u);
-      }
-      uint2 w;
-      w.x = o[0] | (o[1] << 16);
-      w.y = o[2] | (o[3] << 16);
-      *reinterpret_cast<uint2*>(xn + (size_t)(mt * 32 + r) * (size_t)pitch + (size_t)n) = w;
-    }
-  }
+  pol_store<CLAMP>(acc, bias, tile, xn, pitch, lane,
+                   [&](int g, int mt, int i, int unit, int row, bool pos, bool inside, uint32_t bits) {
+                     const uint32_t bit = 1u << ((g & 1) * 16 + 4 * mt + i);
+                     if (pos) sb[g >> 1] |= bit;
+                     if (CLAMP && inside) cb[g >> 1] |= bit;
+                     wsx[(size_t)unit * (size_t)cr + (size_t)row] = (uint16_t)(row < n_env ? bits : 0u);
+                   });
 }
 
 // D = bf16(dx * slope * clamp mask) of the tile's units into the LDS image the next backward
@@ -145,10 +123,11 @@ template <bool TWO>
 __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char grad_smem[];
   uint16_t* const regA = reinterpret_cast<uint16_t*>(grad_smem);
-  uint16_t* const regB = reinterpret_cast<uint16_t*>(grad_smem + p.g.off_b);
+  uint16_t* const regB = reinterpret_cast<uint16_t*>(grad_smem + p.g.lds.off_b);
   uint16_t* const regC = regA;  // D_4, once X_2 has been read
   const GradPlan& g = p.g;
   const PolicyDims& d = g.d;
+  const PolicyLds& L = g.lds;
   const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
   const int r = lane & 31, h = lane >> 5;
   const int64_t env0 = p.row0 + (int64_t)blockIdx.x * kGradRows;  // (global row; < N by the grid)
@@ -160,124 +139,54 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBw
 
   uint32_t s1[2][2] = {}, s2[2][2] = {}, s3[2][2] = {}, c3[2][2] = {}, cx[2] = {};
 
-  // ---- layer 1: as wab_policy_kernel
-  pol_f32x16 acc0[4], acc1[4];
-  pol_zero(acc0);
-  if (TWO) pol_zero(acc1);
-  const int KC = g.KC, pitch_in = g.pitch_in;
-  const int kpad = 16 * d.KS1;
-  uint4 wf[kPolicyMaxKs];
-  const uint4* const w1t = wimg + (d.w1 >> 3) + (size_t)wave * (size_t)d.KS1 * 64u + (size_t)lane;
-  for (int c = 0; c < g.n_chunks; ++c) {
-    const int k0 = c * KC;
-    const int kn = kpad - k0 < KC ? kpad - k0 : KC;
-    const int ks0 = k0 >> 4, nks = kn >> 4;
-    if (wave < d.NT1) pol_load_frags(wf, w1t + (size_t)ks0 * 64u, nks);
-    if (c > 0) __syncthreads();
-    for (int kl = lane; kl < kn; kl += 64) {
-      const int k = k0 + kl;
-      const bool kin = k < d.F;
-      const float* col = p.features + (size_t)env0 * (size_t)d.F + (size_t)(kin ? k : d.F - 1);
-      constexpr int kRows = 16;
-      for (int eb = 0; eb < kGradRows / 4; eb += kRows) {
-        float v[kRows];
-#pragma unroll
-        for (int i = 0; i < kRows; ++i) {
-          const int e = wave + 4 * (eb + i);
-          v[i] = col[(size_t)(e < n_env ? e : n_env - 1) * (size_t)d.F];
-        }
-#pragma unroll
-        for (int i = 0; i < kRows; ++i) {
-          const int e = wave + 4 * (eb + i);
-          regA[(size_t)e * (size_t)pitch_in + (size_t)kl] = (uint16_t)((kin && e < n_env) ? pol_bf16(v[i]) : 0u);
-        }
-      }
-    }
-    __syncthreads();
-    const uint16_t* x = regA + (size_t)r * (size_t)pitch_in + 8 * h;
-    if (wave < d.NT1) pol_mma(acc0, wf, nks, x, pitch_in);
-    if (TWO && wave + 4 < d.NT1) {
-      pol_load_frags(wf, w1t + ((size_t)4 * (size_t)d.KS1 + (size_t)ks0) * 64u, nks);
-      pol_mma(acc1, wf, nks, x, pitch_in);
-    }
-  }
-  uint16_t* const wsx1 = ws + (size_t)g.u_x[1] * (size_t)cr;
-  if (wave < d.NT1) grad_fwd_store<false>(acc0, p.b + d.b1, wave, regB, g.pitch1, lane, n_env, wsx1, cr, s1[0], cx);
-  if (TWO && wave + 4 < d.NT1)
-    grad_fwd_store<false>(acc1, p.b + d.b1, wave + 4, regB, g.pitch1, lane, n_env, wsx1, cr, s1[1], cx);
+  // ---- layer 1: chunks of KC input columns through region A -> X1 (region B)
+  pol_layer1<4, TWO>(
+      d, L, wimg, regA, wave, lane,
+      [&](int k0, int kn) {
+        pol_stage_rows<kGradRows>(p.features + (size_t)env0 * (size_t)d.F, d.F, n_env, k0, kn, regA, L.pitch_in, wave,
+                                  lane, [](int, int, float, bool) {});
+      },
+      [] { __syncthreads(); },
+      [&](const pol_f32x16(&acc)[4], int t, int j) {
+        grad_fwd_store<false>(acc, p.b + d.b1, t, regB, L.pitch1, lane, n_env, ws + (size_t)g.u_x[1] * (size_t)cr, cr,
+                              s1[j], cx);
+      });
   __syncthreads();  // X1 complete; region A free
 
   // ---- layer 2: X1 (region B) -> X2 (region A); layer 3: X2 -> X3 (region B), clamped
-  {
-    const uint4* const w2 = wimg + (d.w2 >> 3);
-    uint16_t* const wsx = ws + (size_t)g.u_x[2] * (size_t)cr;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int t = wave + 4 * j;
-      if (t < d.NT2) {
-        pol_load_frags(wf, w2 + (size_t)t * (size_t)d.KS2 * 64u + (size_t)lane, d.KS2);
-        pol_zero(acc0);
-        pol_mma(acc0, wf, d.KS2, regB + (size_t)r * (size_t)g.pitch1 + 8 * h, g.pitch1);
-        grad_fwd_store<false>(acc0, p.b + d.b2, t, regA, g.pitch2, lane, n_env, wsx, cr, s2[j], cx);
-      }
-    }
-  }
+  uint4 wf[kPolicyMaxKs];
+  pol_layer<4, false>(wf, wimg + (d.w2 >> 3), d.NT2, d.KS2, regB, L.pitch1, wave, lane,
+                      [&](const pol_f32x16(&acc)[4], int t, int j) {
+                        grad_fwd_store<false>(acc, p.b + d.b2, t, regA, L.pitch2, lane, n_env,
+                                              ws + (size_t)g.u_x[2] * (size_t)cr, cr, s2[j], cx);
+                      });
   __syncthreads();
-  {
-    const uint4* const w3 = wimg + (d.w3 >> 3);
-    uint16_t* const wsx = ws + (size_t)g.u_x[3] * (size_t)cr;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int t = wave + 4 * j;
-      if (t < d.NT3) {
-        pol_load_frags(wf, w3 + (size_t)t * (size_t)d.KS3 * 64u + (size_t)lane, d.KS3);
-        pol_zero(acc0);
-        pol_mma(acc0, wf, d.KS3, regA + (size_t)r * (size_t)g.pitch2 + 8 * h, g.pitch2);
-        grad_fwd_store<true>(acc0, p.b + d.b3, t, regB, g.pitch3, lane, n_env, wsx, cr, s3[j], c3[j]);
-      }
-    }
-  }
+  pol_layer<4, false>(wf, wimg + (d.w3 >> 3), d.NT3, d.KS3, regA, L.pitch2, wave, lane,
+                      [&](const pol_f32x16(&acc)[4], int t, int j) {
+                        grad_fwd_store<true>(acc, p.b + d.b3, t, regB, L.pitch3, lane, n_env,
+                                             ws + (size_t)g.u_x[3] * (size_t)cr, cr, s3[j], c3[j]);
+                      });
   pol_load_frags(wf, wimg + (d.wh >> 3) + (size_t)lane, d.KS4);
   __syncthreads();
 
-  // ---- heads: wave w on rows 32 w .., lanes 0..31 finish (pol_sample's softmax, in its order)
+  // ---- heads: wave w on rows 32 w .., lanes 0..31 finish
   {
-    const pol_f32x16 acc = pol_head_mma(wf, d.KS4, regB + (size_t)(32 * wave + r) * (size_t)g.pitch3 + 8 * h);
-    float lg[kPolicyMaxActions];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      lg[i] = acc[i];
-      lg[4 + i] = __shfl(acc[i], (lane + 32) & 63, 64);
-    }
+    const pol_f32x16 acc = pol_head_mma(wf, d.KS4, regB + (size_t)(32 * wave + r) * (size_t)L.pitch3 + 8 * h);
+    const int A = d.A;
+    const PolSoftmax q = pol_softmax(acc, lane, p.b + d.bh, A);
     const int my = 32 * wave + r;
     const int64_t row = env0 + my;
     const bool live = h == 0 && my < n_env;
     double part[3] = {0.0, 0.0, 0.0};
     if (h == 0) {
-      const float* bh = p.b + d.bh;
-      const int A = d.A;
-      const float val = acc[4] + bh[kPolicyMaxActions];
+      const float val = q.val;
       float z[kPolicyMaxActions], pk[kPolicyMaxActions], gk[kPolicyMaxActions];
-      float m = -INFINITY;
-#pragma unroll
-      for (int k = 0; k < kPolicyMaxActions; ++k) {
-        lg[k] = lg[k] + bh[k];
-        if (k < A) m = fmaxf(m, lg[k]);
-      }
-      float s = 0.0f;
-#pragma unroll
-      for (int k = 0; k < kPolicyMaxActions; ++k) {
-        z[k] = lg[k] - m;
-        lg[k] = k < A ? expf(z[k]) : 0.0f;
-        if (k < A) s = s + lg[k];
-      }
-      const float inv = 1.0f / s;
-      const float ls = logf(s);
+      const float ls = logf(q.s);
       float H = 0.0f;
 #pragma unroll
       for (int k = 0; k < kPolicyMaxActions; ++k) {
-        pk[k] = lg[k] * inv;
-        z[k] = z[k] - ls;  // log p_k
+        pk[k] = q.e[k] * q.inv;
+        z[k] = q.z[k] - ls;  // log p_k
         if (k < A) H = H - pk[k] * z[k];
       }
       int a = 0;
@@ -338,38 +247,23 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBw
   __syncthreads();  // D_4 complete
 
   // ---- dx_3 = D_4 . [Wa; Wv] -> D_3 (region B); dx_2 = D_3 . W_3 -> D_2 (region A); dx_1 -> D_1
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int t = wave + 4 * j;
-    if (t < d.NT3) {
-      pol_load_frags(wf, wtimg + (g.wt3 >> 3) + (size_t)t * (size_t)g.KT3 * 64u + (size_t)lane, g.KT3);
-      pol_zero(acc0);
-      pol_mma(acc0, wf, g.KT3, regC + (size_t)r * (size_t)g.pitch4 + 8 * h, g.pitch4);
-      grad_bwd_store<true, true>(acc0, t, regB, g.pitch3, lane, ws + (size_t)g.u_d[3] * (size_t)cr, cr, s3[j], c3[j]);
-    }
-  }
+  pol_layer<4, false>(wf, wtimg + (g.wt3 >> 3), d.NT3, g.KT3, regC, g.pitch4, wave, lane,
+                      [&](const pol_f32x16(&acc)[4], int t, int j) {
+                        grad_bwd_store<true, true>(acc, t, regB, L.pitch3, lane, ws + (size_t)g.u_d[3] * (size_t)cr, cr,
+                                                   s3[j], c3[j]);
+                      });
   __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int t = wave + 4 * j;
-    if (t < d.NT2) {
-      pol_load_frags(wf, wtimg + (g.wt2 >> 3) + (size_t)t * (size_t)g.KT2 * 64u + (size_t)lane, g.KT2);
-      pol_zero(acc0);
-      pol_mma(acc0, wf, g.KT2, regB + (size_t)r * (size_t)g.pitch3 + 8 * h, g.pitch3);
-      grad_bwd_store<false, true>(acc0, t, regA, g.pitch2, lane, ws + (size_t)g.u_d[2] * (size_t)cr, cr, s2[j], cx);
-    }
-  }
+  pol_layer<4, false>(wf, wtimg + (g.wt2 >> 3), d.NT2, g.KT2, regB, L.pitch3, wave, lane,
+                      [&](const pol_f32x16(&acc)[4], int t, int j) {
+                        grad_bwd_store<false, true>(acc, t, regA, L.pitch2, lane, ws + (size_t)g.u_d[2] * (size_t)cr, cr,
+                                                    s2[j], cx);
+                      });
   __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int t = wave + 4 * j;
-    if (t < d.NT1) {
-      pol_load_frags(wf, wtimg + (g.wt1 >> 3) + (size_t)t * (size_t)g.KT1 * 64u + (size_t)lane, g.KT1);
-      pol_zero(acc0);
-      pol_mma(acc0, wf, g.KT1, regA + (size_t)r * (size_t)g.pitch2 + 8 * h, g.pitch2);
-      grad_bwd_store<false, false>(acc0, t, nullptr, 0, lane, ws + (size_t)g.u_d[1] * (size_t)cr, cr, s1[j], cx);
-    }
-  }
+  pol_layer<4, false>(wf, wtimg + (g.wt1 >> 3), d.NT1, g.KT1, regA, L.pitch2, wave, lane,
+                      [&](const pol_f32x16(&acc)[4], int t, int j) {
+                        grad_bwd_store<false, false>(acc, t, nullptr, 0, lane, ws + (size_t)g.u_d[1] * (size_t)cr, cr,
+                                                     s1[j], cx);
+                      });
 }
 
 template __global__ void wab_policy_bwd_kernel<false>(GradBwdParams p);

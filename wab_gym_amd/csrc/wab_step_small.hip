@@ -1654,93 +1654,65 @@ __device__ __forceinline__ void roll_policy(const Params& p, const SmallLayout& 
   const PolicyDims& d = q.d;
   unsigned char* const smem = reinterpret_cast<unsigned char*>(lds);
   uint16_t* const regA = reinterpret_cast<uint16_t*>(smem + q.reg_a);
-  uint16_t* const regB = reinterpret_cast<uint16_t*>(smem + q.reg_b);
+  uint16_t* const regB = reinterpret_cast<uint16_t*>(smem + q.reg_a + q.lds.off_b);
   const int r = lane & 31, h = lane >> 5;
   const int64_t g0 = (int64_t)blockIdx.x * 64;
   const int n_env = (int)min((int64_t)64, p.B - g0);
   const uint32_t F = (uint32_t)d.F;
   const uint4* const wimg = reinterpret_cast<const uint4*>(q.w);
+  const int pitch_in = q.lds.pitch_in;
 
-  // ---- layer 1: chunks of KC input columns through region A; wave w holds tiles w and w + 4
-  pol_f32x16 acc0[2], acc1[2];
-  pol_zero(acc0);
-  pol_zero(acc1);
-  const int KC = q.KC, pitch_in = q.pitch_in;
-  const int kpad = 16 * d.KS1;
+  // ---- layer 1: chunks of KC input columns through region A -> X1 (region B)
+  pol_layer1<2, true>(
+      d, q.lds, wimg, regA, wave, lane,
+      [&](int k0, int kn) {
+        if constexpr (FIRST) {
+          // as wab_policy_kernel stages them, each element copied to slice 0 of the features
+          float* const copy = q.features && q.features != q.features0 ? q.features + (size_t)g0 * F : nullptr;
+          pol_stage_rows<64>(q.features0 + (size_t)g0 * F, d.F, n_env, k0, kn, regA, pitch_in, wave, lane,
+                             [&](int e, int k, float v, bool inside) {
+                               if (copy && inside) copy[(size_t)e * F + (uint32_t)k] = v;
+                             });
+        } else {
+          // eight columns of one env per thread and pass: bits e F + k .. + 7 of the feature bits, as
+          // 16 bytes of its row (an inactive env's bits are zero: step_features emits nothing for it)
+          const uint32_t* const ob = lds + L.fbits;
+          const uint32_t nj = (uint32_t)kn >> 3;
+          for (uint32_t i = threadIdx.x; i < 64u * nj; i += 256u) {
+            const uint32_t e = i / nj, j = i - e * nj;
+            const uint32_t k = (uint32_t)k0 + 8u * j;
+            uint32_t bits = 0u;
+            if (k < F) {
+              const uint32_t at = e * F + k;  // (the word after the env's last is the bits' slack)
+              const uint64_t ww = (uint64_t)ob[at >> 5] | ((uint64_t)ob[(at >> 5) + 1u] << 32);
+              bits = (uint32_t)(ww >> (at & 31u));
+              bits &= F - k >= 8u ? 0xFFu : (1u << (F - k)) - 1u;
+            }
+            uint4 v;  // bf16 1.0 = 0x3F80
+            v.x = ((bits & 1u) ? 0x3F80u : 0u) | ((bits & 2u) ? 0x3F800000u : 0u);
+            v.y = ((bits & 4u) ? 0x3F80u : 0u) | ((bits & 8u) ? 0x3F800000u : 0u);
+            v.z = ((bits & 16u) ? 0x3F80u : 0u) | ((bits & 32u) ? 0x3F800000u : 0u);
+            v.w = ((bits & 64u) ? 0x3F80u : 0u) | ((bits & 128u) ? 0x3F800000u : 0u);
+            *reinterpret_cast<uint4*>(regA + (size_t)e * (size_t)pitch_in + (size_t)(8u * j)) = v;
+          }
+        }
+      },
+      [] { lds_barrier(); },
+      [&](const pol_f32x16(&acc)[2], int t, int) { pol_store<false>(acc, q.b + d.b1, t, regB, q.lds.pitch1, lane); });
   uint4 wf[kPolicyMaxKs];
-  const uint4* const w1t = wimg + (d.w1 >> 3) + (size_t)wave * (size_t)d.KS1 * 64u + (size_t)lane;
-  for (int c = 0; c < q.n_chunks; ++c) {
-    const int k0 = c * KC;
-    const int kn = kpad - k0 < KC ? kpad - k0 : KC;  // columns of this chunk (a multiple of 16)
-    const int ks0 = k0 >> 4, nks = kn >> 4;
-    if (wave < d.NT1) pol_load_frags(wf, w1t + (size_t)ks0 * 64u, nks);
-    if (c > 0) lds_barrier();  // the last chunk's rows have been read
-    if constexpr (FIRST) {
-      // as wab_policy_kernel loads them: wave w takes rows w, w + 4, ..., a lane one column of the
-      // 16 rows, the loads issued together (addresses clamped into the batch; rows past it and the
-      // pad columns are stored as zeros)
-      const float* const f0 = q.features0 + (size_t)g0 * F;
-      float* const copy = q.features && q.features != q.features0 ? q.features + (size_t)g0 * F : nullptr;
-      for (int kl = lane; kl < kn; kl += 64) {
-        const int k = k0 + kl;
-        const bool kin = (uint32_t)k < F;
-        const float* col = f0 + (size_t)(kin ? (uint32_t)k : F - 1u);
-        float v[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int e = wave + 4 * i;
-          v[i] = col[(size_t)(e < n_env ? e : n_env - 1) * F];
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int e = wave + 4 * i;
-          const bool in = kin && e < n_env;
-          regA[(size_t)e * (size_t)pitch_in + (size_t)kl] = (uint16_t)(in ? pol_bf16(v[i]) : 0u);
-          if (copy && in) copy[(size_t)e * F + (uint32_t)k] = v[i];
-        }
-      }
-    } else {
-      // eight columns of one env per thread and pass: bits e F + k .. + 7 of the feature bits, as
-      // 16 bytes of its row (an inactive env's bits are zero: step_features emits nothing for it)
-      const uint32_t* const ob = lds + L.fbits;
-      const uint32_t nj = (uint32_t)kn >> 3;
-      for (uint32_t i = threadIdx.x; i < 64u * nj; i += 256u) {
-        const uint32_t e = i / nj, j = i - e * nj;
-        const uint32_t k = (uint32_t)k0 + 8u * j;
-        uint32_t bits = 0u;
-        if (k < F) {
-          const uint32_t at = e * F + k;  // (the word after the env's last is the bits' slack)
-          const uint64_t ww = (uint64_t)ob[at >> 5] | ((uint64_t)ob[(at >> 5) + 1u] << 32);
-          bits = (uint32_t)(ww >> (at & 31u));
-          bits &= F - k >= 8u ? 0xFFu : (1u << (F - k)) - 1u;
-        }
-        uint4 v;  // bf16 1.0 = 0x3F80
-        v.x = ((bits & 1u) ? 0x3F80u : 0u) | ((bits & 2u) ? 0x3F800000u : 0u);
-        v.y = ((bits & 4u) ? 0x3F80u : 0u) | ((bits & 8u) ? 0x3F800000u : 0u);
-        v.z = ((bits & 16u) ? 0x3F80u : 0u) | ((bits & 32u) ? 0x3F800000u : 0u);
-        v.w = ((bits & 64u) ? 0x3F80u : 0u) | ((bits & 128u) ? 0x3F800000u : 0u);
-        *reinterpret_cast<uint4*>(regA + (size_t)e * (size_t)pitch_in + (size_t)(8u * j)) = v;
-      }
-    }
-    lds_barrier();
-    const uint16_t* x = regA + (size_t)r * (size_t)pitch_in + 8 * h;
-    if (wave < d.NT1) pol_mma(acc0, wf, nks, x, pitch_in);
-    if (wave + 4 < d.NT1) {
-      pol_load_frags(wf, w1t + ((size_t)4 * (size_t)d.KS1 + (size_t)ks0) * 64u, nks);
-      pol_mma(acc1, wf, nks, x, pitch_in);
-    }
-  }
-  if (wave < d.NT1) pol_store<false>(acc0, q.b + d.b1, wave, regB, q.pitch1, lane);
-  if (wave + 4 < d.NT1) pol_store<false>(acc1, q.b + d.b1, wave + 4, regB, q.pitch1, lane);
   const uint4* const w2 = wimg + (d.w2 >> 3), * const w3 = wimg + (d.w3 >> 3);
   if (wave < d.NT2) pol_load_frags(wf, w2 + (size_t)wave * (size_t)d.KS2 * 64u + (size_t)lane, d.KS2);
   lds_barrier();  // X1 complete; region A free
 
   // ---- layer 2: X1 (region B) -> X2 (region A); layer 3: X2 -> X3 (region B), clamped
-  pol_layer<false, 2>(wf, w2, q.b + d.b2, d.NT2, d.KS2, regB, q.pitch1, regA, q.pitch2, wave, lane);
+  pol_layer<2, true>(wf, w2, d.NT2, d.KS2, regB, q.lds.pitch1, wave, lane, [&](const pol_f32x16(&acc)[2], int t, int) {
+    pol_store<false>(acc, q.b + d.b2, t, regA, q.lds.pitch2, lane);
+  });
   if (wave < d.NT3) pol_load_frags(wf, w3 + (size_t)wave * (size_t)d.KS3 * 64u + (size_t)lane, d.KS3);
   lds_barrier();
-  pol_layer<true, 2>(wf, w3, q.b + d.b3, d.NT3, d.KS3, regA, q.pitch2, regB, q.pitch3, wave, lane);
+  pol_layer<2, true>(wf, w3, d.NT3, d.KS3, regA, q.lds.pitch2, wave, lane, [&](const pol_f32x16(&acc)[2], int t, int) {
+    pol_store<true>(acc, q.b + d.b3, t, regB, q.lds.pitch3, lane);
+  });
   if (wave < 2) pol_load_frags(wf, wimg + (d.wh >> 3) + (size_t)lane, d.KS4);
   lds_barrier();
 
@@ -1749,7 +1721,7 @@ __device__ __forceinline__ void roll_policy(const Params& p, const SmallLayout& 
     const int my_env = 32 * wave + r;
     const bool sampler = h == 0 && my_env < n_env;
     const uint32_t ep = (uint32_t)__shfl((int)episode, my_env, 64), tu = (uint32_t)__shfl((int)turn, my_env, 64);
-    const pol_f32x16 acc = pol_head_mma(wf, d.KS4, regB + (size_t)my_env * (size_t)q.pitch3 + 8 * h);
+    const pol_f32x16 acc = pol_head_mma(wf, d.KS4, regB + (size_t)my_env * (size_t)q.lds.pitch3 + 8 * h);
     const int64_t o = (int64_t)t_out * p.B;
     const int a = pol_sample(acc, lane, sampler, q.b + d.bh, d.A, p.seed, p.env_base, g0 + my_env, ep, tu, q.actions + o,
                              q.probs ? q.probs + o * d.A : nullptr, q.value ? q.value + o : nullptr);
