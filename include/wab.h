@@ -49,6 +49,7 @@
  *   wab_rollout_policy    <- T steps of actor_critic.main's loop with   actor_critic.py:108-125,
  *                            select_action choosing each action          185-200
  *   wab_policy_grad       <- finish_episode's loss and loss.backward()  actor_critic.py:148-165
+ *   wab_policy_grad_ppo   <- the same with PPO's clipped surrogate; wab_policy_evaluate its old_logp
  *   wab_policy_adam_step  <- optimizer.step() (optim.Adam)              actor_critic.py:104, 165
  */
 #ifndef WAB_H_
@@ -61,7 +62,7 @@
 extern "C" {
 #endif
 
-#define WAB_ABI_VERSION 13
+#define WAB_ABI_VERSION 14
 #define WAB_MAX_WOLF_SLOTS 32 /* largest per-env live-wolf slot count (wab_config.wolf_slots) */
 #define WAB_MAX_VIEW 63       /* largest odd width/height accepted */
 
@@ -565,6 +566,54 @@ int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions,
 /* The number of rows the latest wab_policy_grad on this workspace left out for their action
  * (synchronises `stream`).  WAB_E_INVALID, with the count in the message, when it is not 0. */
 int wab_policy_grad_bad_actions(const wab_policy* p, const void* workspace, void* stream, uint64_t* out);
+
+/* ---- device policy: PPO's clipped loss and the evaluate pass ---------------------------- */
+
+/* wab_policy_grad with the clipped surrogate in the place of -weight logp, and optionally the
+ * clipped value loss.  Per row i, everything not named here is wab_policy_grad's contract (forward,
+ * p, log p_k, H, the entropy term, the straight-through backward, slabs, sum orders, scale once,
+ * bad-action rows left out and counted).  A = advantage[i], fp32:
+ *   d = logp_a - old_logp[i];  d = d < -30 ? -30 : (d > 30 ? 30 : d)   (a NaN stays a NaN)
+ *   r = expf(d);  lo = 1.0f - clip, hi = 1.0f + clip, both formed in fp32
+ *   clipped = (A > 0 && r > hi) || (A < 0 && r < lo)
+ *   loss_policy_i = clipped ? -(A (A > 0 ? hi : lo)) : -(r A)
+ *   w_eff = clipped ? 0 : r A   (one fp32 multiply)
+ *   g_logit_k = w_eff (p_k - [k = a]) + entropy_coef p_k (log p_k + H)
+ * which is -min(r A, clamp(r, lo, hi) A) and its gradient except on the ties.  Value term, l the
+ * configured value loss, t the target, c = value_clip (c <= 0: off, old_value may be NULL):
+ *   u = v - old_value[i];  |u| <= c: loss_value_i = l(v - t), g_v = value_coef l'(v - t)
+ *   otherwise vc = old_value[i] + (u > 0 ? c : -c), l1 = l(v - t), l2 = l(vc - t),
+ *   loss_value_i = max(l1, l2), value_clipped = l2 > l1, g_v = value_clipped ? 0 : value_coef l'(v - t)
+ * ppo_out[4] = {clipped rows, sum of k3, value-clipped rows, sum of r} over the rows that took
+ * part, k3 = expm1((double)d) - (double)d per row; summed in double in the loss parts' order, never
+ * scaled.  With unchanged weights and old_logp from wab_policy_evaluate r is exactly 1.0f, and
+ * the gradients are wab_policy_grad's of weight = advantage, bit for bit. */
+typedef struct wab_ppo_config {
+  float clip;         /* in (0, 1) */
+  float value_clip;   /* <= 0: off */
+} wab_ppo_config;
+
+/* wab_policy_grad's arguments, guarantees and workspace, and: advantage [N], old_logp [N],
+ * old_value [N] (NULL iff value_clip <= 0) float32; ppo_out: device float[4] or NULL, added to
+ * with loss->accumulate as loss_out is; ratio [N] float32 or NULL (0 for a bad action).
+ * WAB_E_INVALID also for a clip outside (0, 1) or NaN, a NULL old_logp with N > 0, or a NULL
+ * old_value with value_clip > 0. */
+int wab_policy_grad_ppo(wab_policy* p, const float* features, const int8_t* actions, const float* advantage,
+                        const float* target, const float* old_logp, const float* old_value, int64_t N,
+                        const wab_policy_loss* loss, const wab_ppo_config* ppo,
+                        const wab_policy_weights* grads_out, float loss_out[4], float ppo_out[4],
+                        float* logp, float* value, float* entropy, float* ratio,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* Forward and head alone: logp [N] (log p_i[a_i]; 0 for a bad action, counted as in
+ * wab_policy_grad), value [N] and entropy [N] float32 with the bits wab_policy_grad writes to its
+ * row outputs (value: wab_policy_act's).  Each may be NULL; actions may be NULL when logp is.
+ * workspace: wab_policy_grad's, or any 256-byte-aligned device memory of at least 256 bytes;
+ * wab_policy_grad_bad_actions works on it after the call.  One memset node and one launch,
+ * stream-ordered: no allocation, no synchronisation, safe to capture in a hipGraph. */
+int wab_policy_evaluate(wab_policy* p, const float* features, const int8_t* actions, int64_t N,
+                        float* logp, float* value, float* entropy,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- device policy: the optimizer step (actor_critic.py:104, 165) ----------------------- */
 

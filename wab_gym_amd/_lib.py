@@ -25,6 +25,7 @@ EXPORTED = [
     "wab_episode_stats_workspace", "wab_episode_stats_update", "wab_normalize_episode_returns",
     "wab_gae", "wab_whiten_workspace", "wab_whiten", "wab_debug_gae_plan",
     "wab_policy_grad_workspace", "wab_policy_grad", "wab_policy_grad_bad_actions", "wab_debug_policy_grad_plan",
+    "wab_policy_grad_ppo", "wab_policy_evaluate",
     "wab_policy_adam_workspace", "wab_policy_adam_step",
     # include/wab_torus.h: the Environment 2.0 torus world
     "wab2_abi_version", "wab2_last_error", "wab2_record_size", "wab2_create", "wab2_destroy",
@@ -35,7 +36,7 @@ EXPORTED = [
 ABI2_VERSION = 1
 OBS_SAME_BUFFER, OBS_FRESH_BUFFER = 0, 1  # wab_set_obs_placement
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 SNAPSHOT_MAGIC, SNAPSHOT_VERSION = 0x53424157, 1  # 'WABS' (wab_snapshot_info)
 
 
@@ -68,6 +69,10 @@ class WabPolicyWeights(ctypes.Structure):
 
 
 VALUE_LOSS = {"smooth_l1": 0, "mse": 1}  # WAB_VALUE_LOSS_*
+
+
+class WabPpoConfig(ctypes.Structure):
+    _fields_ = [("clip", ctypes.c_float), ("value_clip", ctypes.c_float)]
 
 
 class WabPolicyLoss(ctypes.Structure):
@@ -165,6 +170,8 @@ def load():
     L.wab_policy_grad_workspace.restype = ctypes.c_size_t
     L.wab_policy_grad.argtypes = [P, P, P, P, P, I64, P, P, P, P, P, P, P, ctypes.c_size_t, P]
     L.wab_policy_grad_bad_actions.argtypes = [P, P, P, P]
+    L.wab_policy_grad_ppo.argtypes = [P, P, P, P, P, P, P, I64, P, P, P, P, P, P, P, P, P, P, ctypes.c_size_t, P]
+    L.wab_policy_evaluate.argtypes = [P, P, P, I64, P, P, P, P, ctypes.c_size_t, P]
     L.wab_debug_policy_grad_plan.argtypes = [P, I32, P]
     L.wab_policy_adam_workspace.argtypes = [P]
     L.wab_policy_adam_workspace.restype = ctypes.c_size_t

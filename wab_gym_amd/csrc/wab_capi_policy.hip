@@ -35,9 +35,16 @@ const void* policy_kernel(const wab::PolicyDims& d) {
   return policy_two_tiles(d) ? reinterpret_cast<const void*>(&wab::wab_policy_kernel<true>)
                              : reinterpret_cast<const void*>(&wab::wab_policy_kernel<false>);
 }
-const void* policy_bwd_kernel(const wab::PolicyDims& d) {
-  return policy_two_tiles(d) ? reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<true>)
-                             : reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<false>);
+template <int MODE>
+const void* policy_bwd_instance(bool two) {
+  return two ? reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<true, MODE>)
+             : reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<false, MODE>);
+}
+const void* policy_bwd_kernel(const wab::PolicyDims& d, int mode) {
+  const bool two = policy_two_tiles(d);
+  return mode == wab::kGradModePpo    ? policy_bwd_instance<wab::kGradModePpo>(two)
+         : mode == wab::kGradModeEval ? policy_bwd_instance<wab::kGradModeEval>(two)
+                                      : policy_bwd_instance<wab::kGradModeGrad>(two);
 }
 
 // What a call on a handle and a policy together needs of the pair: always the same device; with
@@ -235,84 +242,136 @@ size_t wab_policy_grad_workspace(const wab_policy* p, int64_t N, int32_t chunk_r
   return wab::grad_workspace(wab::grad_plan(p->dims), cr).total;
 }
 
-int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions, const float* weight,
-                    const float* target, int64_t N, const wab_policy_loss* loss, const wab_policy_weights* grads_out,
-                    float loss_out[4], float* logp, float* value, float* entropy, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-  g_err.clear();
-  if (!p || !loss || !grads_out || !workspace) return fail(WAB_E_INVALID, "wab_policy_grad: NULL argument");
-  if (N < 0 || N > INT32_MAX) return fail(WAB_E_INVALID, "wab_policy_grad: N outside [0, 2^31)");
-  if (N > 0 && (!features || !actions || !weight || !target))
-    return fail(WAB_E_INVALID, "wab_policy_grad: NULL argument (features, actions, weight and target are required)");
-  const wab_policy_weights& go = *grads_out;
-  if (!go.w1 || !go.b1 || !go.w2 || !go.b2 || !go.w3 || !go.b3 || !go.wa || !go.ba || !go.wv || !go.bv)
-    return fail(WAB_E_INVALID, "wab_policy_grad: every gradient pointer must be set");
-  if (loss->value_loss != WAB_VALUE_LOSS_SMOOTH_L1 && loss->value_loss != WAB_VALUE_LOSS_MSE)
-    return fail(WAB_E_INVALID, "wab_policy_grad: value_loss must be WAB_VALUE_LOSS_SMOOTH_L1 or WAB_VALUE_LOSS_MSE");
-  const int64_t cr = grad_chunk_rows(loss->chunk_rows);
-  if (cr < 0) return fail(WAB_E_INVALID, "wab_policy_grad: chunk_rows must be 0 or a positive multiple of 128");
-  if (!p->loaded) return fail(WAB_E_STATE, "wab_policy_grad: call wab_policy_load first");
+namespace {
+
+// What the three calls on wab_policy_bwd_kernel differ in: wab_policy_grad leaves the ppo fields
+// NULL, wab_policy_evaluate loss and grads_out as well.
+struct GradCall {
+  const char* name;
+  int mode;  // wab::GradMode
+  const float *features, *weight, *target, *old_logp, *old_value;
+  const int8_t* actions;
+  int64_t N;
+  const wab_policy_loss* loss;
+  const wab_ppo_config* ppo;
+  const wab_policy_weights* grads_out;
+  float *loss_out, *ppo_out, *logp, *value, *entropy, *ratio;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+};
+
+// The checks, the parameter blocks and the chunk loop of wab_policy_grad, wab_policy_grad_ppo and
+// wab_policy_evaluate.
+int policy_grad_run(wab_policy* p, const GradCall& c) {
+  const std::string w = std::string(c.name) + ": ";
+  const bool eval = c.mode == wab::kGradModeEval, ppo = c.mode == wab::kGradModePpo;
+  if (!p || !c.workspace || (!eval && (!c.loss || !c.grads_out)) || (ppo && !c.ppo))
+    return fail(WAB_E_INVALID, w + "NULL argument");
+  const int64_t N = c.N;
+  if (N < 0 || N > INT32_MAX) return fail(WAB_E_INVALID, w + "N outside [0, 2^31)");
+  if (eval) {
+    if (N > 0 && (!c.features || (c.logp && !c.actions)))
+      return fail(WAB_E_INVALID, w + "NULL argument (features are required, and actions with logp)");
+  } else if (N > 0 && (!c.features || !c.actions || !c.weight || !c.target)) {
+    return fail(WAB_E_INVALID, w + "NULL argument (features, actions, " + (ppo ? "advantage" : "weight") +
+                                   " and target are required)");
+  }
+  int64_t cr = wab::kGradRows;
+  if (!eval) {
+    const wab_policy_weights& go = *c.grads_out;
+    if (!go.w1 || !go.b1 || !go.w2 || !go.b2 || !go.w3 || !go.b3 || !go.wa || !go.ba || !go.wv || !go.bv)
+      return fail(WAB_E_INVALID, w + "every gradient pointer must be set");
+    if (c.loss->value_loss != WAB_VALUE_LOSS_SMOOTH_L1 && c.loss->value_loss != WAB_VALUE_LOSS_MSE)
+      return fail(WAB_E_INVALID, w + "value_loss must be WAB_VALUE_LOSS_SMOOTH_L1 or WAB_VALUE_LOSS_MSE");
+    cr = grad_chunk_rows(c.loss->chunk_rows);
+    if (cr < 0) return fail(WAB_E_INVALID, w + "chunk_rows must be 0 or a positive multiple of 128");
+  }
+  if (ppo) {
+    if (!(c.ppo->clip > 0.0f && c.ppo->clip < 1.0f)) return fail(WAB_E_INVALID, w + "clip must be inside (0, 1)");
+    if (c.ppo->value_clip != c.ppo->value_clip) return fail(WAB_E_INVALID, w + "value_clip is NaN");
+    if (N > 0 && !c.old_logp) return fail(WAB_E_INVALID, w + "NULL argument (old_logp is required)");
+    if (c.ppo->value_clip > 0.0f && !c.old_value)
+      return fail(WAB_E_INVALID, w + "value_clip > 0 needs old_value");
+  }
+  if (!p->loaded) return fail(WAB_E_STATE, w + "call wab_policy_load first");
   const wab::GradPlan g = wab::grad_plan(p->dims);
   const wab::GradWorkspace lay = wab::grad_workspace(g, cr);
-  if (workspace_bytes < lay.total)
-    return fail(WAB_E_INVALID, "wab_policy_grad: the workspace has " + std::to_string(workspace_bytes) +
-                                   " bytes, wab_policy_grad_workspace asks for " + std::to_string(lay.total));
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255u) != 0)
-    return fail(WAB_E_INVALID, "wab_policy_grad: the workspace must be 256-byte aligned");
-  const void* f32s[] = {features, weight, target, loss_out, logp, value, entropy, go.w1, go.b1, go.w2, go.b2,
-                        go.w3, go.b3, go.wa, go.ba, go.wv, go.bv};
+  // (evaluate keeps nothing in the workspace but the bad-action count, its first word)
+  const size_t need = eval ? (size_t)256 : lay.total;
+  if (c.workspace_bytes < need)
+    return fail(WAB_E_INVALID, w + "the workspace has " + std::to_string(c.workspace_bytes) + " bytes, " +
+                                   (eval ? std::string("256 are needed")
+                                         : "wab_policy_grad_workspace asks for " + std::to_string(need)));
+  if ((reinterpret_cast<uintptr_t>(c.workspace) & 255u) != 0)
+    return fail(WAB_E_INVALID, w + "the workspace must be 256-byte aligned");
+  const wab_policy_weights none = {};
+  const wab_policy_weights& go = eval ? none : *c.grads_out;
+  const void* f32s[] = {c.features, c.weight, c.target, c.old_logp, c.old_value, c.loss_out, c.ppo_out, c.logp,
+                        c.value, c.entropy, c.ratio, go.w1, go.b1, go.w2, go.b2, go.w3, go.b3, go.wa, go.ba,
+                        go.wv, go.bv};
   for (const void* q : f32s)
-    if ((reinterpret_cast<uintptr_t>(q) & 3u) != 0)
-      return fail(WAB_E_INVALID, "wab_policy_grad: float arrays must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(q) & 3u) != 0) return fail(WAB_E_INVALID, w + "float arrays must be 4-byte aligned");
   DeviceGuard guard(p->device);
   // wab_policy_bwd_kernel's dynamic LDS can exceed the 64 KB default: as wab_policy_create's
-  const void* const bwd = policy_bwd_kernel(p->dims);
+  const void* const bwd = policy_bwd_kernel(p->dims, c.mode);
   HIP_TRY(raise_lds(p->device, bwd, p->lds_max));
-  unsigned char* const base = static_cast<unsigned char*>(workspace);
+  unsigned char* const base = static_cast<unsigned char*>(c.workspace);
   uint32_t* const bad = reinterpret_cast<uint32_t*>(base + lay.bad);
   uint16_t* const wt = reinterpret_cast<uint16_t*>(base + lay.wt);
   uint16_t* const ws = reinterpret_cast<uint16_t*>(base + lay.ws);
   float* const slab = reinterpret_cast<float*>(base + lay.slab);
   double* const part = reinterpret_cast<double*>(base + lay.part);
   double* const lsum = reinterpret_cast<double*>(base + lay.loss);
-  hipStream_t st = (hipStream_t)stream;
+  hipStream_t st = (hipStream_t)c.stream;
 
-  // the transposed image, from the packed weights as they are at this point of the stream (every
-  // call: a flag on the host would go stale under graph replay)
-  wab::GradPackParams kp;
-  kp.g = g;
-  kp.w = p->w;
-  kp.wt = wt;
-  kp.bad = bad;
-  hipLaunchKernelGGL(wab::wab_policy_grad_pack, dim3(std::min<uint32_t>((g.wt_total + 255u) / 256u, 1024u)), dim3(256),
-                     0, st, kp);
-  HIP_TRY(hipGetLastError());
+  if (eval) {
+    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
+    cr = ((std::max<int64_t>(N, 1) + wab::kGradRows - 1) / wab::kGradRows) * wab::kGradRows;  // one pass
+  } else {
+    // the transposed image, from the packed weights as they are at this point of the stream (every
+    // call: a flag on the host would go stale under graph replay)
+    wab::GradPackParams kp;
+    kp.g = g;
+    kp.w = p->w;
+    kp.wt = wt;
+    kp.bad = bad;
+    hipLaunchKernelGGL(wab::wab_policy_grad_pack, dim3(std::min<uint32_t>((g.wt_total + 255u) / 256u, 1024u)),
+                       dim3(256), 0, st, kp);
+    HIP_TRY(hipGetLastError());
+  }
 
   wab::GradBwdParams bp;
   bp.g = g;
   bp.N = N;
   bp.chunk_rows = cr;
-  bp.features = features;
-  bp.actions = actions;
-  bp.weight = weight;
-  bp.target = target;
+  bp.features = c.features;
+  bp.actions = c.actions;
+  bp.weight = c.weight;
+  bp.target = c.target;
+  bp.old_logp = c.old_logp;
+  bp.old_value = ppo && c.ppo->value_clip > 0.0f ? c.old_value : nullptr;
+  bp.clip = ppo ? c.ppo->clip : 0.0f;
+  bp.value_clip = ppo ? c.ppo->value_clip : 0.0f;
   bp.w = p->w;
   bp.b = p->b;
-  bp.wt = wt;
-  bp.value_coef = loss->value_coef;
-  bp.entropy_coef = loss->entropy_coef;
-  bp.mse = loss->value_loss == WAB_VALUE_LOSS_MSE ? 1 : 0;
-  bp.logp = logp;
-  bp.value = value;
-  bp.entropy = entropy;
-  bp.ws = ws;
-  bp.part = part;
+  bp.wt = eval ? nullptr : wt;
+  bp.value_coef = eval ? 0.0f : c.loss->value_coef;
+  bp.entropy_coef = eval ? 0.0f : c.loss->entropy_coef;
+  bp.mse = !eval && c.loss->value_loss == WAB_VALUE_LOSS_MSE ? 1 : 0;
+  bp.logp = c.logp;
+  bp.value = c.value;
+  bp.entropy = c.entropy;
+  bp.ratio = c.ratio;
+  bp.ws = eval ? nullptr : ws;
+  bp.part = eval ? nullptr : part;
   bp.bad = bad;
   wab::GradWgradParams wp;
   wp.g = g;
   wp.N = N;
   wp.chunk_rows = cr;
-  wp.features = features;
+  wp.n_terms = ppo ? wab::kGradPpoTerms : wab::kGradLossTerms;
+  wp.features = c.features;
   wp.ws = ws;
   wp.part = part;
   wp.slab = slab;
@@ -323,6 +382,7 @@ int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions,
     bp.row0 = row0;
     launch_params(bwd, blocks, g.lds.total, st, bp);
     HIP_TRY(hipGetLastError());
+    if (eval) continue;
     wp.row0 = row0;
     wp.n_blocks = (int32_t)blocks;
     wp.first = row0 == 0 ? 1 : 0;
@@ -330,14 +390,15 @@ int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions,
                        st, wp);
     HIP_TRY(hipGetLastError());
   }
+  if (eval) return WAB_OK;
 
   wab::GradReduceParams rp;
   rp.g = g;
   rp.empty = N == 0 ? 1 : 0;
-  rp.accumulate = loss->accumulate ? 1 : 0;
-  rp.scale = loss->scale;
-  rp.value_coef = loss->value_coef;
-  rp.entropy_coef = loss->entropy_coef;
+  rp.accumulate = c.loss->accumulate ? 1 : 0;
+  rp.scale = c.loss->scale;
+  rp.value_coef = c.loss->value_coef;
+  rp.entropy_coef = c.loss->entropy_coef;
   rp.slab = slab;
   rp.loss = lsum;
   rp.w1 = const_cast<float*>(go.w1); rp.b1 = const_cast<float*>(go.b1);
@@ -345,7 +406,8 @@ int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions,
   rp.w3 = const_cast<float*>(go.w3); rp.b3 = const_cast<float*>(go.b3);
   rp.wa = const_cast<float*>(go.wa); rp.ba = const_cast<float*>(go.ba);
   rp.wv = const_cast<float*>(go.wv); rp.bv = const_cast<float*>(go.bv);
-  rp.loss_out = loss_out;
+  rp.loss_out = c.loss_out;
+  rp.ppo_out = ppo ? c.ppo_out : nullptr;
   const wab::PolicyDims& d = p->dims;
   const int64_t elems = (int64_t)d.h1 * (d.F + 1) + (int64_t)d.h2 * (d.h1 + 1) + (int64_t)d.h3 * (d.h2 + 1) +
                         (int64_t)(d.A + 1) * (d.h3 + 1);
@@ -353,6 +415,52 @@ int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions,
                      dim3(256), 0, st, rp);
   HIP_TRY(hipGetLastError());
   return WAB_OK;
+}
+
+}  // namespace
+
+int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions, const float* weight,
+                    const float* target, int64_t N, const wab_policy_loss* loss, const wab_policy_weights* grads_out,
+                    float loss_out[4], float* logp, float* value, float* entropy, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  g_err.clear();
+  GradCall c = {};
+  c.name = "wab_policy_grad";
+  c.mode = wab::kGradModeGrad;
+  c.features = features; c.actions = actions; c.weight = weight; c.target = target;
+  c.N = N; c.loss = loss; c.grads_out = grads_out; c.loss_out = loss_out;
+  c.logp = logp; c.value = value; c.entropy = entropy;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  return policy_grad_run(p, c);
+}
+
+int wab_policy_grad_ppo(wab_policy* p, const float* features, const int8_t* actions, const float* advantage,
+                        const float* target, const float* old_logp, const float* old_value, int64_t N,
+                        const wab_policy_loss* loss, const wab_ppo_config* ppo, const wab_policy_weights* grads_out,
+                        float loss_out[4], float ppo_out[4], float* logp, float* value, float* entropy, float* ratio,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  g_err.clear();
+  GradCall c = {};
+  c.name = "wab_policy_grad_ppo";
+  c.mode = wab::kGradModePpo;
+  c.features = features; c.actions = actions; c.weight = advantage; c.target = target;
+  c.old_logp = old_logp; c.old_value = old_value;
+  c.N = N; c.loss = loss; c.ppo = ppo; c.grads_out = grads_out; c.loss_out = loss_out; c.ppo_out = ppo_out;
+  c.logp = logp; c.value = value; c.entropy = entropy; c.ratio = ratio;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  return policy_grad_run(p, c);
+}
+
+int wab_policy_evaluate(wab_policy* p, const float* features, const int8_t* actions, int64_t N, float* logp,
+                        float* value, float* entropy, void* workspace, size_t workspace_bytes, void* stream) {
+  g_err.clear();
+  GradCall c = {};
+  c.name = "wab_policy_evaluate";
+  c.mode = wab::kGradModeEval;
+  c.features = features; c.actions = actions; c.N = N;
+  c.logp = logp; c.value = value; c.entropy = entropy;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  return policy_grad_run(p, c);
 }
 
 int wab_policy_grad_bad_actions(const wab_policy* p, const void* workspace, void* stream, uint64_t* out) {

@@ -13,6 +13,15 @@ constexpr int kGradHeadUnits = 16;      // G_4's columns: [0, 8) the action logi
 constexpr int kGradMaxSlabs = 64;
 constexpr int kGradDefaultChunk = 32768;  // rows per chunk: the bf16 workspace of the reference net is 54 MiB
 
+// wab_policy_bwd_kernel's modes: the loss and gradients of wab_policy_grad, those of the clipped
+// surrogate (wab_policy_grad_ppo), or forward and head alone (wab_policy_evaluate)
+enum GradMode : int { kGradModeGrad = 0, kGradModePpo = 1, kGradModeEval = 2 };
+// The rows' sums a wave hands on, as doubles: {loss_policy, loss_value, entropy} in every gradient
+// mode, then the clipped surrogate's {clipped rows, sum of k3, value-clipped rows, sum of r}.
+constexpr int kGradLossTerms = 3;  // terms of wab_policy_grad
+constexpr int kGradPpoTerms = 7;   // terms of wab_policy_grad_ppo
+constexpr int kGradTermPitch = 8;  // doubles per wave and per slab
+
 // The transposed packed weights the backward chain reads (the A operands of dx_l = D_{l+1} . W_{l+1}):
 // image l is pack_layer's layout of W_{l+1}^T, NT_l tiles of 32 units of layer l by KS k-steps of
 // 16 units of layer l + 1.  The head's image has one k-step: columns 0..7 the action head's rows,
@@ -105,8 +114,8 @@ inline GradWorkspace grad_workspace(const GradPlan& g, int64_t chunk_rows) {
   w.wt = o; o = up(o + (size_t)g.wt_total * 2u);
   w.ws = o; o = up(o + (size_t)g.u_total * (size_t)chunk_rows * 2u);
   w.slab = o; o = up(o + (size_t)g.slabs * (size_t)g.n_tasks * (size_t)(kGradTiles * 1024) * 4u);
-  w.part = o; o = up(o + (size_t)(chunk_rows / kGradRows) * 4u * 3u * 8u);  // [block][wave][3] doubles
-  w.loss = o; o = up(o + (size_t)g.slabs * 3u * 8u);                         // [slab][3] doubles
+  w.part = o; o = up(o + (size_t)(chunk_rows / kGradRows) * 4u * (size_t)kGradTermPitch * 8u);  // [block][wave][8] doubles
+  w.loss = o; o = up(o + (size_t)g.slabs * (size_t)kGradTermPitch * 8u);                         // [slab][8] doubles
   w.total = o;
   return w;
 }
@@ -124,8 +133,11 @@ struct GradBwdParams {
   int64_t chunk_rows;      // the workspace's row pitch
   const float* features;   // [N][F]
   const int8_t* actions;   // [N]
-  const float* weight;     // [N]
+  const float* weight;     // [N]: the weight, or the advantage of the clipped surrogate
   const float* target;     // [N]
+  const float* old_logp;   // [N] (clipped surrogate)
+  const float* old_value;  // [N] or null (clipped surrogate with value_clip > 0)
+  float clip, value_clip;  // (clipped surrogate) value_clip <= 0: off
   const uint16_t* w;       // forward image
   const float* b;          // padded biases
   const uint16_t* wt;      // transposed image
@@ -134,8 +146,9 @@ struct GradBwdParams {
   float* logp;             // [N] or null
   float* value;            // [N] or null
   float* entropy;          // [N] or null
-  uint16_t* ws;            // bf16 workspace of the chunk
-  double* part;            // [chunk block][wave][3]: the waves' sums of the rows' loss terms
+  float* ratio;            // [N] or null (clipped surrogate)
+  uint16_t* ws;            // bf16 workspace of the chunk (null: evaluate)
+  double* part;            // [chunk block][wave][8]: the waves' sums of the rows' loss terms
   uint32_t* bad;           // count of rows whose action is outside [0, A)
 };
 
@@ -145,6 +158,7 @@ struct GradWgradParams {
   int64_t chunk_rows;
   int32_t n_blocks;        // row blocks of this chunk
   int32_t first;           // 1: the slabs start from zero (the call's first chunk)
+  int32_t n_terms;         // loss terms the call sums: kGradLossTerms or kGradPpoTerms
   const float* features;
   const uint16_t* ws;
   const double* part;
@@ -161,11 +175,12 @@ struct GradReduceParams {
   const double* loss;
   float *w1, *b1, *w2, *b2, *w3, *b3, *wa, *ba, *wv, *bv;  // torch Linear layout, device
   float* loss_out;         // {policy, value, entropy, total}
+  float* ppo_out;          // {clipped rows, sum of k3, value-clipped rows, sum of r} or null
 };
 
 // the kernels (wab_policy_grad.hip), launched from wab_capi_policy.hip
 __global__ void wab_policy_grad_pack(GradPackParams p);
-template <bool TWO>
+template <bool TWO, int MODE = kGradModeGrad>
 __global__ void wab_policy_bwd_kernel(GradBwdParams p);
 __global__ void wab_policy_wgrad_kernel(GradWgradParams p);
 __global__ void wab_policy_grad_reduce_kernel(GradReduceParams p);

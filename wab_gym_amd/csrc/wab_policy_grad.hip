@@ -18,6 +18,10 @@
 //     adds the slabs in ascending order in fp32 and multiplies by `scale` once.  The loss terms
 //     are summed in double (lanes by a fixed shuffle tree, waves, blocks and slabs in order).
 // No float atomics; every sum has one order, so results are bitwise reproducible.
+// wab_policy_grad_ppo (reference_ppo_loss_and_grad; include/wab.h) is the same with the head's
+// weight replaced by the clipped surrogate's r A or 0, g_v by 0 where the value loss is clipped,
+// and four more sums; wab_policy_evaluate is the forward and the head's row outputs alone.  Both
+// are instances of wab_policy_bwd_kernel (MODE), so logp, value and entropy have the same bits.
 //
 // wab_policy_bwd_kernel: one workgroup per 128 rows, wab_policy_kernel's plan (the rows' features
 // staged as bf16 chunks, the waves splitting the 32-unit tiles).  A lane keeps the leaky_relu and
@@ -118,9 +122,21 @@ __device__ __forceinline__ double grad_wave_sum(double v) {
   return v;
 }
 
+// the configured value loss of one difference and its derivative
+__device__ __forceinline__ float grad_value_loss(float dl, bool mse, float& dv) {
+  const float ad = fabsf(dl);
+  const bool quad = mse || ad < 1.0f;
+  dv = quad ? dl : (dl > 0.0f ? 1.0f : -1.0f);
+  return quad ? 0.5f * dl * dl : ad - 0.5f;
+}
+
 // ------------------------------------------------------------------------ forward, head, backward chain
-template <bool TWO>
+// MODE (wab_policy_grad.h): kGradModePpo changes the head's weight, value gradient and sums alone;
+// kGradModeEval ends after the head's row outputs and touches no workspace but the bad count.
+template <bool TWO, int MODE>
 __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBwdParams p) {
+  constexpr bool PPO = MODE == kGradModePpo, EVAL = MODE == kGradModeEval;
+  constexpr int TERMS = PPO ? kGradPpoTerms : kGradLossTerms;
   extern __shared__ __attribute__((aligned(16))) unsigned char grad_smem[];
   uint16_t* const regA = reinterpret_cast<uint16_t*>(grad_smem);
   uint16_t* const regB = reinterpret_cast<uint16_t*>(grad_smem + p.g.lds.off_b);
@@ -148,8 +164,11 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBw
       },
       [] { __syncthreads(); },
       [&](const pol_f32x16(&acc)[4], int t, int j) {
-        grad_fwd_store<false>(acc, p.b + d.b1, t, regB, L.pitch1, lane, n_env, ws + (size_t)g.u_x[1] * (size_t)cr, cr,
-                              s1[j], cx);
+        if constexpr (EVAL)
+          pol_store<false>(acc, p.b + d.b1, t, regB, L.pitch1, lane);
+        else
+          grad_fwd_store<false>(acc, p.b + d.b1, t, regB, L.pitch1, lane, n_env, ws + (size_t)g.u_x[1] * (size_t)cr, cr,
+                                s1[j], cx);
       });
   __syncthreads();  // X1 complete; region A free
 
@@ -157,14 +176,20 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBw
   uint4 wf[kPolicyMaxKs];
   pol_layer<4, false>(wf, wimg + (d.w2 >> 3), d.NT2, d.KS2, regB, L.pitch1, wave, lane,
                       [&](const pol_f32x16(&acc)[4], int t, int j) {
-                        grad_fwd_store<false>(acc, p.b + d.b2, t, regA, L.pitch2, lane, n_env,
-                                              ws + (size_t)g.u_x[2] * (size_t)cr, cr, s2[j], cx);
+                        if constexpr (EVAL)
+                          pol_store<false>(acc, p.b + d.b2, t, regA, L.pitch2, lane);
+                        else
+                          grad_fwd_store<false>(acc, p.b + d.b2, t, regA, L.pitch2, lane, n_env,
+                                                ws + (size_t)g.u_x[2] * (size_t)cr, cr, s2[j], cx);
                       });
   __syncthreads();
   pol_layer<4, false>(wf, wimg + (d.w3 >> 3), d.NT3, d.KS3, regA, L.pitch2, wave, lane,
                       [&](const pol_f32x16(&acc)[4], int t, int j) {
-                        grad_fwd_store<true>(acc, p.b + d.b3, t, regB, L.pitch3, lane, n_env,
-                                             ws + (size_t)g.u_x[3] * (size_t)cr, cr, s3[j], c3[j]);
+                        if constexpr (EVAL)
+                          pol_store<true>(acc, p.b + d.b3, t, regB, L.pitch3, lane);
+                        else
+                          grad_fwd_store<true>(acc, p.b + d.b3, t, regB, L.pitch3, lane, n_env,
+                                               ws + (size_t)g.u_x[3] * (size_t)cr, cr, s3[j], c3[j]);
                       });
   pol_load_frags(wf, wimg + (d.wh >> 3) + (size_t)lane, d.KS4);
   __syncthreads();
@@ -177,7 +202,7 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBw
     const int my = 32 * wave + r;
     const int64_t row = env0 + my;
     const bool live = h == 0 && my < n_env;
-    double part[3] = {0.0, 0.0, 0.0};
+    double part[TERMS] = {};
     if (h == 0) {
       const float val = q.val;
       float z[kPolicyMaxActions], pk[kPolicyMaxActions], gk[kPolicyMaxActions];
@@ -190,60 +215,114 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBw
         if (k < A) H = H - pk[k] * z[k];
       }
       int a = 0;
-      float wgt = 0.0f, tgt = 0.0f;
+      float wgt = 0.0f, tgt = 0.0f, olp = 0.0f, ov = 0.0f;
       if (live) {
-        a = (int)p.actions[row];
-        wgt = p.weight[row];
-        tgt = p.target[row];
+        if (!EVAL || p.actions) a = (int)p.actions[row];
+        if (!EVAL) {
+          wgt = p.weight[row];
+          tgt = p.target[row];
+        }
+        if (PPO) {
+          olp = p.old_logp[row];
+          if (p.value_clip > 0.0f) ov = p.old_value[row];
+        }
       }
       const bool bad = a < 0 || a >= A;
       const bool use = live && !bad;
       if (live && bad) atomicAdd(p.bad, 1u);
       float la = 0.0f;
+      if constexpr (EVAL) {
+        // (a chain of selects on `a` alone is turned into an indexed load from a scratch copy of z)
+        uint32_t za = 0u;
 #pragma unroll
-      for (int k = 0; k < kPolicyMaxActions; ++k) {
-        if (k == a) la = z[k];
-        const float g1 = wgt * (pk[k] - (k == a ? 1.0f : 0.0f));
-        const float g2 = p.entropy_coef * (pk[k] * (z[k] + H));
-        gk[k] = (use && k < A) ? g1 + g2 : 0.0f;
-      }
-      const float dl = val - tgt, ad = fabsf(dl);
-      const bool quad = p.mse || ad < 1.0f;
-      const float lv = quad ? 0.5f * dl * dl : ad - 0.5f;
-      const float dv = quad ? dl : (dl > 0.0f ? 1.0f : -1.0f);
-      const float gv = use ? p.value_coef * dv : 0.0f;
-      if (use) {
-        part[0] = (double)(-(wgt * la));
-        part[1] = (double)lv;
-        part[2] = (double)H;
-      }
-      if (live) {
-        if (p.logp) p.logp[row] = bad ? 0.0f : la;
-        if (p.value) p.value[row] = val;
-        if (p.entropy) p.entropy[row] = H;
-      }
-      // D_4's row: [g_logit (8) | g_v | 0 x 7] as bf16, to region C and the workspace
-      uint32_t o[kGradHeadUnits];
+        for (int k = 0; k < kPolicyMaxActions; ++k) za |= k == a ? __builtin_bit_cast(uint32_t, z[k]) : 0u;
+        la = __builtin_bit_cast(float, za);
+        if (live) {
+          if (p.logp) p.logp[row] = bad ? 0.0f : la;
+          if (p.value) p.value[row] = val;
+          if (p.entropy) p.entropy[row] = H;
+        }
+      } else {
+        // the clipped surrogate (include/wab.h): r = exp(clamp(logp - old_logp)), the weight r A or,
+        // where the clip holds the row, 0
+        float weff = wgt, lpol = 0.0f, rr = 0.0f, dlt = 0.0f;
+        bool clipped = false;
+        if constexpr (PPO) {
 #pragma unroll
-      for (int k = 0; k < kGradHeadUnits; ++k)
-        o[k] = k < kPolicyMaxActions ? pol_bf16(gk[k < kPolicyMaxActions ? k : 0])
-                                     : (k == kPolicyMaxActions ? pol_bf16(gv) : 0u);
-      uint4 q0, q1;
-      q0.x = o[0] | (o[1] << 16); q0.y = o[2] | (o[3] << 16); q0.z = o[4] | (o[5] << 16); q0.w = o[6] | (o[7] << 16);
-      q1.x = o[8] | (o[9] << 16); q1.y = o[10] | (o[11] << 16); q1.z = o[12] | (o[13] << 16); q1.w = o[14] | (o[15] << 16);
-      uint4* const drow = reinterpret_cast<uint4*>(regC + (size_t)my * (size_t)g.pitch4);
-      drow[0] = q0;
-      drow[1] = q1;
-      uint16_t* const wsd = ws + (size_t)g.u_d[4] * (size_t)cr + (size_t)my;
+          for (int k = 0; k < kPolicyMaxActions; ++k)
+            if (k == a) la = z[k];
+          dlt = la - olp;
+          dlt = dlt < -30.0f ? -30.0f : (dlt > 30.0f ? 30.0f : dlt);
+          rr = expf(dlt);
+          const float lo = 1.0f - p.clip, hi = 1.0f + p.clip;
+          clipped = (wgt > 0.0f && rr > hi) || (wgt < 0.0f && rr < lo);
+          const float ra = rr * wgt;
+          weff = clipped ? 0.0f : ra;
+          lpol = clipped ? -(wgt * (wgt > 0.0f ? hi : lo)) : -ra;
+        }
 #pragma unroll
-      for (int k = 0; k < kGradHeadUnits; ++k) wsd[(size_t)k * (size_t)cr] = (uint16_t)o[k];
+        for (int k = 0; k < kPolicyMaxActions; ++k) {
+          if (k == a) la = z[k];
+          const float g1 = weff * (pk[k] - (k == a ? 1.0f : 0.0f));
+          const float g2 = p.entropy_coef * (pk[k] * (z[k] + H));
+          gk[k] = (use && k < A) ? g1 + g2 : 0.0f;
+        }
+        float dv;
+        float lv = grad_value_loss(val - tgt, p.mse != 0, dv);
+        bool vclipped = false;
+        if constexpr (PPO) {
+          const float u = val - ov, c = p.value_clip;
+          if (c > 0.0f && !(fabsf(u) <= c)) {
+            float dv2;
+            const float l2 = grad_value_loss((ov + (u > 0.0f ? c : -c)) - tgt, p.mse != 0, dv2);
+            vclipped = l2 > lv;
+            lv = vclipped ? l2 : lv;
+          }
+        }
+        const float gv = (use && !vclipped) ? p.value_coef * dv : 0.0f;
+        if (use) {
+          part[0] = PPO ? (double)lpol : (double)(-(wgt * la));
+          part[1] = (double)lv;
+          part[2] = (double)H;
+          if constexpr (PPO) {
+            part[3] = clipped ? 1.0 : 0.0;
+            part[4] = expm1((double)dlt) - (double)dlt;  // Schulman's k3, from the fp32 d
+            part[5] = vclipped ? 1.0 : 0.0;
+            part[6] = (double)rr;
+          }
+        }
+        if (live) {
+          if (p.logp) p.logp[row] = bad ? 0.0f : la;
+          if (p.value) p.value[row] = val;
+          if (p.entropy) p.entropy[row] = H;
+          if (PPO && p.ratio) p.ratio[row] = bad ? 0.0f : rr;
+        }
+        // D_4's row: [g_logit (8) | g_v | 0 x 7] as bf16, to region C and the workspace
+        uint32_t o[kGradHeadUnits];
+#pragma unroll
+        for (int k = 0; k < kGradHeadUnits; ++k)
+          o[k] = k < kPolicyMaxActions ? pol_bf16(gk[k < kPolicyMaxActions ? k : 0])
+                                       : (k == kPolicyMaxActions ? pol_bf16(gv) : 0u);
+        uint4 q0, q1;
+        q0.x = o[0] | (o[1] << 16); q0.y = o[2] | (o[3] << 16); q0.z = o[4] | (o[5] << 16); q0.w = o[6] | (o[7] << 16);
+        q1.x = o[8] | (o[9] << 16); q1.y = o[10] | (o[11] << 16); q1.z = o[12] | (o[13] << 16); q1.w = o[14] | (o[15] << 16);
+        uint4* const drow = reinterpret_cast<uint4*>(regC + (size_t)my * (size_t)g.pitch4);
+        drow[0] = q0;
+        drow[1] = q1;
+        uint16_t* const wsd = ws + (size_t)g.u_d[4] * (size_t)cr + (size_t)my;
+#pragma unroll
+        for (int k = 0; k < kGradHeadUnits; ++k) wsd[(size_t)k * (size_t)cr] = (uint16_t)o[k];
+      }
     }
+    if constexpr (!EVAL) {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const double v = grad_wave_sum(part[j]);
-      if (lane == 0) p.part[((size_t)blockIdx.x * 4u + (size_t)wave) * 3u + (size_t)j] = v;
+      for (int j = 0; j < TERMS; ++j) {
+        const double v = grad_wave_sum(part[j]);
+        if (lane == 0) p.part[((size_t)blockIdx.x * 4u + (size_t)wave) * (size_t)kGradTermPitch + (size_t)j] = v;
+      }
     }
   }
+  if constexpr (EVAL) return;  // forward and head alone
   __syncthreads();  // D_4 complete
 
   // ---- dx_3 = D_4 . [Wa; Wv] -> D_3 (region B); dx_2 = D_3 . W_3 -> D_2 (region A); dx_1 -> D_1
@@ -266,8 +345,12 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBw
                       });
 }
 
-template __global__ void wab_policy_bwd_kernel<false>(GradBwdParams p);
-template __global__ void wab_policy_bwd_kernel<true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModeGrad>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModeGrad>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModePpo>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModePpo>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModeEval>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModeEval>(GradBwdParams p);
 
 // ------------------------------------------------------------------------ dW, db
 // the slab's row blocks of this chunk, ascending: acc[i] += D_l[rows, tile i]^T . [X_{l-1} | 1][rows, tile kt]
@@ -340,11 +423,11 @@ __global__ __launch_bounds__(64) void wab_policy_wgrad_kernel(GradWgradParams p)
   const int64_t B0 = p.row0 / kGradRows;
   if (task == g.n_tasks) {
     // the loss terms of the slab's row blocks, ascending, waves in order
-    if (lane < 3) {
-      double* const dst = p.loss + (size_t)slab * 3u + (size_t)lane;
+    if (lane < p.n_terms) {
+      double* const dst = p.loss + (size_t)slab * (size_t)kGradTermPitch + (size_t)lane;
       double v = p.first ? 0.0 : *dst;
       for (int64_t b = B0 + ((int64_t)slab - B0 % S + S) % S; b < B0 + p.n_blocks; b += S)
-        for (int w = 0; w < 4; ++w) v = v + p.part[((size_t)(b - B0) * 4u + (size_t)w) * 3u + (size_t)lane];
+        for (int w = 0; w < 4; ++w) v = v + p.part[((size_t)(b - B0) * 4u + (size_t)w) * (size_t)kGradTermPitch + (size_t)lane];
       *dst = v;
     }
     return;
@@ -418,10 +501,19 @@ __global__ __launch_bounds__(256) void wab_policy_grad_reduce_kernel(GradReduceP
     double l[3] = {0.0, 0.0, 0.0};
     if (!p.empty)
       for (int s = 0; s < g.slabs; ++s)
-        for (int j = 0; j < 3; ++j) l[j] = l[j] + p.loss[(size_t)s * 3u + (size_t)j];
+        for (int j = 0; j < 3; ++j) l[j] = l[j] + p.loss[(size_t)s * (size_t)kGradTermPitch + (size_t)j];
     const double tot = (double)p.scale * (l[0] + (double)p.value_coef * l[1] - (double)p.entropy_coef * l[2]);
     const float out[4] = {(float)l[0], (float)l[1], (float)l[2], (float)tot};
     for (int j = 0; j < 4; ++j) p.loss_out[j] = p.accumulate ? p.loss_out[j] + out[j] : out[j];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && p.ppo_out) {
+    // the clipped surrogate's diagnostics, never scaled
+    for (int j = 0; j < kGradPpoTerms - kGradLossTerms; ++j) {
+      double v = 0.0;
+      if (!p.empty)
+        for (int s = 0; s < g.slabs; ++s) v = v + p.loss[(size_t)s * (size_t)kGradTermPitch + (size_t)(kGradLossTerms + j)];
+      p.ppo_out[j] = p.accumulate ? p.ppo_out[j] + (float)v : (float)v;
+    }
   }
 }
 

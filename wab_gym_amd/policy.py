@@ -6,6 +6,9 @@ action sampled in the same launch (wab_policy_act, wab_gym_amd/csrc/wab_policy.h
     ...optimizer.step()...; policy.load(model)   # stream-ordered re-pack, no host sync
     policy.loss_and_grad(features, actions, weight, target, into=model)   # finish_episode's loss
                                                  # and loss.backward() (wab_policy_grad)
+    old = policy.evaluate(features, actions)["logp"]                      # (wab_policy_evaluate)
+    policy.ppo_loss_and_grad(features, actions, advantage, target, old, clip=0.2, into=model)
+                                                 # PPO's clipped loss (wab_policy_grad_ppo)
 
     opt = DeviceAdam(policy, model, lr=3e-4)     # optimizer.step() and the re-pack in HIP
     opt.step()                                   # (wab_policy_adam_step): no policy.load after it
@@ -93,6 +96,66 @@ def reference_forward(state_dict, features, hidden=None):
     return e / e.sum(dim=-1, keepdim=True), linear(x, "value_head")[:, 0]
 
 
+def _value_loss(d, value_loss):
+    """(l(d), l'(d)) of the configured value loss, float64 tensors."""
+    import torch
+
+    if value_loss == "mse":
+        return 0.5 * d * d, d
+    return (torch.where(d.abs() < 1.0, 0.5 * d * d, d.abs() - 0.5), torch.where(d.abs() < 1.0, d, torch.sign(d)))
+
+
+def _reference_head_and_backward(state_dict, features, actions, head, entropy_coef, scale, round_grads):
+    """What reference_loss_and_grad and reference_ppo_loss_and_grad share: the forward, p, log p,
+    H, then head(logp, v) -> (w rows, g_v rows, loss_policy, loss_value, extras), then G_4 and the
+    straight-through backward.  Returns (loss parts, logp, v, H, grads, extras)."""
+    import torch
+
+    sd = {k: v.detach().to("cpu", torch.float32) for k, v in _state_dict(state_dict).items()}
+
+    def bf(x):
+        return x.to(torch.float32).to(torch.bfloat16).to(torch.float64)
+
+    def rd(g):
+        return bf(g) if round_grads else g
+
+    x0 = bf(torch.as_tensor(features).detach().to("cpu", torch.float32))
+    a = torch.as_tensor(actions).detach().to("cpu", torch.int64)
+    hidden = []
+    _, v = reference_forward(sd, features, hidden=hidden)
+    xs = [x0] + [h[1] for h in hidden]
+    wq = {n: bf(sd[n + ".weight"]) for n in LAYERS}
+    logits = xs[3] @ wq["action_head"].T + sd["action_head.bias"].to(torch.float64)
+    zc = logits - logits.max(dim=-1, keepdim=True).values
+    logp_all = zc - torch.log(torch.exp(zc).sum(dim=-1, keepdim=True))
+    p = torch.exp(logp_all)
+    H = -(p * logp_all).sum(dim=-1)
+    onehot = torch.zeros_like(p)
+    onehot[torch.arange(len(a)), a] = 1.0
+    logp = (logp_all * onehot).sum(dim=-1)
+    w, gv, loss_policy, loss_value, extras = head(logp, v)
+    loss_entropy = H.sum()
+
+    Da = rd(w[:, None] * (p - onehot) + entropy_coef * p * (logp_all + H[:, None]))
+    Dv = rd(gv)[:, None]
+    grads = {"action_head.weight": Da.T @ xs[3], "action_head.bias": Da.sum(dim=0),
+             "value_head.weight": Dv.T @ xs[3], "value_head.bias": Dv.sum(dim=0)}
+    dx = Da @ wq["action_head"] + Dv @ wq["value_head"]
+    slope = float(np.float32(0.01))
+    for i in (2, 1, 0):
+        z = hidden[i][0]
+        G = dx * torch.where(z >= 0, 1.0, slope)
+        if i == 2:
+            y = torch.where(z >= 0, z, z * slope)
+            G = G * ((y >= -4.0) & (y <= 4.0)).to(torch.float64)
+        D = rd(G)
+        grads[LAYERS[i] + ".weight"] = D.T @ xs[i]
+        grads[LAYERS[i] + ".bias"] = D.sum(dim=0)
+        dx = D @ wq[LAYERS[i]]
+    grads = {k: g * scale for k, g in grads.items()}
+    return (loss_policy, loss_value, loss_entropy), logp, v, H, grads, extras
+
+
 def reference_loss_and_grad(state_dict, features, actions, weight, target, value_coef=1.0, entropy_coef=0.0,
                             value_loss="smooth_l1", scale=1.0, round_grads=True):
     """wab_policy_grad's numeric contract in torch on the CPU, float64, written out by hand (no
@@ -112,65 +175,83 @@ def reference_loss_and_grad(state_dict, features, actions, weight, target, value
 
     if value_loss not in ("smooth_l1", "mse"):
         raise ValueError("value_loss must be 'smooth_l1' or 'mse'")
-    sd = {k: v.detach().to("cpu", torch.float32) for k, v in _state_dict(state_dict).items()}
-
-    def bf(x):
-        return x.to(torch.float32).to(torch.bfloat16).to(torch.float64)
-
-    def rd(g):
-        return bf(g) if round_grads else g
-
-    x0 = bf(torch.as_tensor(features).detach().to("cpu", torch.float32))
-    a = torch.as_tensor(actions).detach().to("cpu", torch.int64)
     w = torch.as_tensor(weight).detach().to("cpu", torch.float64)
     tg = torch.as_tensor(target).detach().to("cpu", torch.float64)
-    hidden = []
-    _, v = reference_forward(sd, features, hidden=hidden)
-    xs = [x0] + [h[1] for h in hidden]
-    wq = {n: bf(sd[n + ".weight"]) for n in LAYERS}
-    logits = xs[3] @ wq["action_head"].T + sd["action_head.bias"].to(torch.float64)
-    zc = logits - logits.max(dim=-1, keepdim=True).values
-    logp_all = zc - torch.log(torch.exp(zc).sum(dim=-1, keepdim=True))
-    p = torch.exp(logp_all)
-    H = -(p * logp_all).sum(dim=-1)
-    onehot = torch.zeros_like(p)
-    onehot[torch.arange(len(a)), a] = 1.0
-    logp = (logp_all * onehot).sum(dim=-1)
-    d = v - tg
-    if value_loss == "mse":
-        lv, dv = 0.5 * d * d, d
-    else:
-        lv = torch.where(d.abs() < 1.0, 0.5 * d * d, d.abs() - 0.5)
-        dv = torch.where(d.abs() < 1.0, d, torch.sign(d))
-    loss_policy, loss_value, loss_entropy = -(w * logp).sum(), lv.sum(), H.sum()
-    total = scale * (loss_policy + value_coef * loss_value - entropy_coef * loss_entropy)
 
-    Da = rd(w[:, None] * (p - onehot) + entropy_coef * p * (logp_all + H[:, None]))
-    Dv = rd(value_coef * dv)[:, None]
-    grads = {"action_head.weight": Da.T @ xs[3], "action_head.bias": Da.sum(dim=0),
-             "value_head.weight": Dv.T @ xs[3], "value_head.bias": Dv.sum(dim=0)}
-    dx = Da @ wq["action_head"] + Dv @ wq["value_head"]
-    slope = float(np.float32(0.01))
-    for i in (2, 1, 0):
-        z = hidden[i][0]
-        G = dx * torch.where(z >= 0, 1.0, slope)
-        if i == 2:
-            y = torch.where(z >= 0, z, z * slope)
-            G = G * ((y >= -4.0) & (y <= 4.0)).to(torch.float64)
-        D = rd(G)
-        grads[LAYERS[i] + ".weight"] = D.T @ xs[i]
-        grads[LAYERS[i] + ".bias"] = D.sum(dim=0)
-        dx = D @ wq[LAYERS[i]]
-    grads = {k: g * scale for k, g in grads.items()}
-    return {"loss": (loss_policy, loss_value, loss_entropy, total), "logp": logp, "value": v, "entropy": H,
-            "grads": grads}
+    def head(logp, v):
+        lv, dv = _value_loss(v - tg, value_loss)
+        return w, value_coef * dv, -(w * logp).sum(), lv.sum(), None
+
+    (lp, lvs, le), logp, v, H, grads, _ = _reference_head_and_backward(state_dict, features, actions, head,
+                                                                       entropy_coef, scale, round_grads)
+    total = scale * (lp + value_coef * lvs - entropy_coef * le)
+    return {"loss": (lp, lvs, le, total), "logp": logp, "value": v, "entropy": H, "grads": grads}
 
 
-def check_loss_args(shape, features, actions, weight, target, value_loss="smooth_l1", reduction="sum", into=None,
-                    accumulate=False):
-    """loss_and_grad's checks that need no device: returns N, the row count.  features [N, F] or
-    [T, B, F] float32, actions int8, weight and target float32 of the leading shape, all
-    contiguous and on one device."""
+def reference_ppo_loss_and_grad(state_dict, features, actions, advantage, target, old_logp, clip=0.2, old_value=None,
+                                value_clip=None, value_coef=1.0, entropy_coef=0.0, value_loss="smooth_l1", scale=1.0,
+                                round_grads=True):
+    """wab_policy_grad_ppo's numeric contract (include/wab.h) in torch on the CPU, float64, by
+    hand: reference_loss_and_grad with the clipped surrogate's effective weight and the clipped
+    value loss.  Per row, A the advantage, lo = float32(1) - float32(clip), hi = float32(1) +
+    float32(clip) (the two float32 values the kernel forms):
+
+        d = clamp(logp - old_logp, -30, 30);  r = exp(d)
+        clipped = (A > 0 and r > hi) or (A < 0 and r < lo)
+        loss_policy_i = -(A (hi if A > 0 else lo)) if clipped else -(r A);  w_eff = 0 if clipped else r A
+        u = v - old_value;  |u| <= value_clip: the plain value loss and gradient;  otherwise
+        vc = old_value + sign(u) value_clip, loss_value_i = max(l(v - t), l(vc - t)), and g_v = 0
+        where l(vc - t) > l(v - t) (value_clipped)
+
+    value_clip None or <= 0: no value clipping.  Returns reference_loss_and_grad's dict plus
+    "ratio", "clipped", "value_clipped" rows and "ppo" = (clipped rows, sum of k3 = expm1(d) - d,
+    value-clipped rows, sum of r)."""
+    import torch
+
+    if value_loss not in ("smooth_l1", "mse"):
+        raise ValueError("value_loss must be 'smooth_l1' or 'mse'")
+    A = torch.as_tensor(advantage).detach().to("cpu", torch.float64)
+    tg = torch.as_tensor(target).detach().to("cpu", torch.float64)
+    olp = torch.as_tensor(old_logp).detach().to("cpu", torch.float64)
+    one, cl = np.float32(1.0), np.float32(clip)
+    lo, hi = float(one - cl), float(one + cl)
+    vclip_on = value_clip is not None and float(value_clip) > 0
+    if vclip_on and old_value is None:
+        raise ValueError("value_clip > 0 needs old_value")
+    c = float(np.float32(value_clip)) if vclip_on else 0.0
+
+    def head(logp, v):
+        d = (logp - olp).clamp(-30.0, 30.0)
+        r = torch.exp(d)
+        clipped = ((A > 0) & (r > hi)) | ((A < 0) & (r < lo))
+        bound = torch.where(A > 0, hi, lo)
+        lpol = torch.where(clipped, -(A * bound), -(r * A))
+        w_eff = torch.where(clipped, torch.zeros_like(A), r * A)
+        l1, dv = _value_loss(v - tg, value_loss)
+        lv, vcl = l1, torch.zeros_like(clipped)
+        if vclip_on:
+            ov = torch.as_tensor(old_value).detach().to("cpu", torch.float64)
+            u = v - ov
+            vc = ov + torch.where(u > 0, c, -c)
+            l2, _ = _value_loss(vc - tg, value_loss)
+            outside = ~(u.abs() <= c)
+            vcl = outside & (l2 > l1)
+            lv = torch.where(vcl, l2, l1)
+        gv = torch.where(vcl, torch.zeros_like(dv), value_coef * dv)
+        ppo = (clipped.to(torch.float64).sum(), (torch.expm1(d) - d).sum(), vcl.to(torch.float64).sum(), r.sum())
+        return w_eff, gv, lpol.sum(), lv.sum(), {"ratio": r, "clipped": clipped, "value_clipped": vcl, "ppo": ppo}
+
+    (lp, lvs, le), logp, v, H, grads, extra = _reference_head_and_backward(state_dict, features, actions, head,
+                                                                           entropy_coef, scale, round_grads)
+    total = scale * (lp + value_coef * lvs - entropy_coef * le)
+    out = {"loss": (lp, lvs, le, total), "logp": logp, "value": v, "entropy": H, "grads": grads}
+    out.update(extra)
+    return out
+
+
+def check_rows(shape, features, **rows):
+    """features [N, F] or [T, B, F] float32 and the named per-row tensors (actions int8, every other
+    float32) of the leading shape, all contiguous and on the features' device: returns N."""
     import torch
 
     F = shape[0]
@@ -178,23 +259,49 @@ def check_loss_args(shape, features, actions, weight, target, value_loss="smooth
             or features.shape[-1] != F or not features.is_contiguous():
         raise ValueError("features must be a contiguous float32 tensor of shape [N, %d] or [T, B, %d]" % (F, F))
     lead = tuple(features.shape[:-1])
-    for name, x, dt in (("actions", actions, torch.int8), ("weight", weight, torch.float32),
-                        ("target", target, torch.float32)):
+    for name, x in rows.items():
+        dt = torch.int8 if name == "actions" else torch.float32
         if not isinstance(x, torch.Tensor) or x.dtype != dt or tuple(x.shape) != lead or not x.is_contiguous() \
                 or x.device != features.device:
             raise ValueError("%s must be a contiguous %s tensor of shape %s on %s"
                              % (name, str(dt).replace("torch.", ""), lead, features.device))
+    n = 1
+    for k in lead:
+        n *= int(k)
+    if n >= 1 << 31:
+        raise ValueError("loss_and_grad takes fewer than 2^31 rows")
+    return n
+
+
+def check_loss_args(shape, features, actions, weight, target, value_loss="smooth_l1", reduction="sum", into=None,
+                    accumulate=False):
+    """loss_and_grad's checks that need no device: returns N, the row count.  features [N, F] or
+    [T, B, F] float32, actions int8, weight and target float32 of the leading shape, all
+    contiguous and on one device."""
+    n = check_rows(shape, features, actions=actions, weight=weight, target=target)
     if value_loss not in _lib.VALUE_LOSS:
         raise ValueError("value_loss must be 'smooth_l1' or 'mse', not %r" % (value_loss,))
     if reduction not in ("sum", "mean"):
         raise ValueError("reduction must be 'sum' or 'mean', not %r" % (reduction,))
     if accumulate and into is None:
         raise ValueError("accumulate=True needs into=: there is no earlier gradient to add to")
-    n = 1
-    for k in lead:
-        n *= int(k)
-    if n >= 1 << 31:
-        raise ValueError("loss_and_grad takes fewer than 2^31 rows")
+    return n
+
+
+def check_ppo_args(shape, features, actions, advantage, target, old_logp, clip=0.2, old_value=None, value_clip=None,
+                   value_loss="smooth_l1", reduction="sum", into=None, accumulate=False):
+    """ppo_loss_and_grad's checks that need no device: check_loss_args', and old_logp (old_value
+    where value_clip > 0) float32 of the leading shape, contiguous, on the features' device; clip
+    inside (0, 1); value_clip None, or a number (<= 0: off).  Returns N."""
+    n = check_loss_args(shape, features, actions, advantage, target, value_loss, reduction, into, accumulate)
+    if not 0.0 < float(clip) < 1.0:
+        raise ValueError("clip must be inside (0, 1), not %r" % (clip,))
+    if value_clip is not None and float(value_clip) != float(value_clip):
+        raise ValueError("value_clip is NaN")
+    on = value_clip is not None and float(value_clip) > 0
+    if on and old_value is None:
+        raise ValueError("value_clip > 0 needs old_value")
+    check_rows(shape, features, old_logp=old_logp, **({"old_value": old_value} if on else {}))
     return n
 
 
@@ -531,11 +638,7 @@ class DevicePolicy:
                                  float(scale) if scale is not None else (1.0 / n if reduction == "mean" and n > 0
                                                                          else 1.0), 1 if accumulate else 0,
                                  int(chunk_rows))
-        need = L.wab_policy_grad_workspace(self._p, n, int(chunk_rows))
-        if need == 0:
-            _lib.check(-1, "wab_policy_grad_workspace")
-        if self._grad_ws is None or self._grad_ws.numel() < need:
-            self._grad_ws = t.empty(need, dtype=t.uint8, device=self.env.device)
+        self._workspace(n, chunk_rows)
         loss = t.zeros(4, dtype=t.float32, device=self.env.device)
         rows = [t.empty(n, dtype=t.float32, device=self.env.device) for _ in range(3)] if return_rows else [None] * 3
         gw = _lib.WabPolicyWeights(*[grads["%s.%s" % (nm, part)].data_ptr() for nm in LAYERS
@@ -551,6 +654,83 @@ class DevicePolicy:
         if return_rows:
             lead = tuple(features.shape[:-1])
             out["logp"], out["value"], out["entropy_rows"] = [r.view(lead) for r in rows]
+        return out
+
+    def _workspace(self, n, chunk_rows):
+        L = _lib.load()
+        need = L.wab_policy_grad_workspace(self._p, n, int(chunk_rows))
+        if need == 0:
+            _lib.check(-1, "wab_policy_grad_workspace")
+        if self._grad_ws is None or self._grad_ws.numel() < need:
+            self._grad_ws = self._torch.empty(need, dtype=self._torch.uint8, device=self.env.device)
+        return self._grad_ws
+
+    def evaluate(self, features, actions=None):
+        """Forward and head alone (wab_policy_evaluate), one launch on the env's stream, no host
+        synchronisation: {"value", "entropy"} float32 of features' leading shape ([N, F] or
+        [T, B, F], viewed), and "logp" with `actions` (int8 of that shape).  The bits are those
+        loss_and_grad(return_rows=True) returns, so under unchanged weights a PPO ratio built from
+        this logp is exactly 1.  A row whose action is out of range has logp 0 and is counted:
+        check() raises for it."""
+        t = self._torch
+        n = check_rows(self.shape, features, **({} if actions is None else {"actions": actions}))
+        if features.device != self.env.device:
+            raise ValueError("features must be on %s" % (self.env.device,))
+        if self._grad_ws is None:
+            self._grad_ws = t.empty(256, dtype=t.uint8, device=self.env.device)
+        names = (("logp",) if actions is not None else ()) + ("value", "entropy")
+        rows = {k: t.empty(n, dtype=t.float32, device=self.env.device) for k in names}
+        _lib.check(_lib.load().wab_policy_evaluate(
+            self._p, features.data_ptr(), None if actions is None else actions.data_ptr(), n,
+            *[rows[k].data_ptr() if k in rows else None for k in ("logp", "value", "entropy")],
+            self._grad_ws.data_ptr(), self._grad_ws.numel(), self.env._stream()), "wab_policy_evaluate")
+        lead = tuple(features.shape[:-1])
+        return {k: r.view(lead) for k, r in rows.items()}
+
+    def ppo_loss_and_grad(self, features, actions, advantage, target, old_logp, *, clip=0.2, old_value=None,
+                          value_clip=None, value_coef=1.0, entropy_coef=0.0, value_loss="smooth_l1", reduction="sum",
+                          into=None, accumulate=False, return_rows=False, chunk_rows=0, scale=None):
+        """loss_and_grad with PPO's clipped surrogate (wab_policy_grad_ppo; the contract is
+        reference_ppo_loss_and_grad): old_logp from evaluate() before the first step, float32 of
+        the leading shape; value_clip > 0 clips the value loss around old_value (the rollout's
+        value).  A minibatch is a contiguous row range, features[t0:t1] of a [T, B, F] segment (a
+        view); accumulate=True sums several ranges into one step.  Returns loss_and_grad's keys
+        and 0-d device tensors "clip_fraction", "approx_kl" (Schulman's k3), "value_clip_fraction"
+        and "ratio_mean", each a sum over the rows divided by N on the device ("ppo_sums": the
+        four sums themselves); with return_rows also "ratio"."""
+        t = self._torch
+        n = check_ppo_args(self.shape, features, actions, advantage, target, old_logp, clip, old_value, value_clip,
+                           value_loss, reduction, into, accumulate)
+        if features.device != self.env.device:
+            raise ValueError("features must be on %s" % (self.env.device,))
+        # (no rows: nothing to clip, and an empty old_value has no address to pass)
+        vclip = float(value_clip) if value_clip is not None and float(value_clip) > 0 and n > 0 else 0.0
+        grads = self._grad_targets(into, accumulate)
+        cfg = _lib.WabPolicyLoss(float(value_coef), float(entropy_coef), _lib.VALUE_LOSS[value_loss],
+                                 float(scale) if scale is not None else (1.0 / n if reduction == "mean" and n > 0
+                                                                         else 1.0), 1 if accumulate else 0,
+                                 int(chunk_rows))
+        ppo = _lib.WabPpoConfig(float(clip), vclip)
+        ws = self._workspace(n, chunk_rows)
+        sums = t.zeros(8, dtype=t.float32, device=self.env.device)  # loss_out[4], ppo_out[4]
+        rows = [t.empty(n, dtype=t.float32, device=self.env.device) for _ in range(4)] if return_rows else [None] * 4
+        gw = _lib.WabPolicyWeights(*[grads["%s.%s" % (nm, part)].data_ptr() for nm in LAYERS
+                                     for part in ("weight", "bias")])
+        _lib.check(_lib.load().wab_policy_grad_ppo(
+            self._p, features.data_ptr(), actions.data_ptr(), advantage.data_ptr(), target.data_ptr(),
+            old_logp.data_ptr(), old_value.data_ptr() if vclip > 0 else None, n, ctypes.addressof(cfg),
+            ctypes.addressof(ppo), ctypes.addressof(gw), sums.data_ptr(), sums[4:].data_ptr(),
+            *[None if r is None else r.data_ptr() for r in rows], ws.data_ptr(), ws.numel(), self.env._stream()),
+            "wab_policy_grad_ppo")
+        out = {"loss": sums[3], "loss_policy": sums[0], "loss_value": sums[1], "entropy": sums[2]}
+        diag = sums[4:] / float(max(n, 1))
+        out["clip_fraction"], out["approx_kl"], out["value_clip_fraction"], out["ratio_mean"] = diag.unbind(0)
+        out["ppo_sums"] = sums[4:]
+        if into is None:
+            out["grads"] = grads
+        if return_rows:
+            lead = tuple(features.shape[:-1])
+            out["logp"], out["value"], out["entropy_rows"], out["ratio"] = [r.view(lead) for r in rows]
         return out
 
     def check(self):
