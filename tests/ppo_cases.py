@@ -1,7 +1,9 @@
 """Inputs shared by tests/test_ppo_host.py (CPU) and tests/test_gpu_ppo.py: tests/policy_grad_cases.py's
 nets, rows, actions, weights (as advantages) and targets, plus old_logp = logp_ref + delta and
 old_value = v_ref + eps, the rows kept clear of the clipped loss's own kinks, and the stock fp32
-autograd of the textbook PPO loss that E is measured against.  Everything here runs on the CPU."""
+autograd of the textbook PPO loss that E is measured against; and for
+tests/test_gpu_ppo_edges.py the head in numpy float32 (predict_head) and the builders that put rows
+on the head's ties from float32 logp and value bits.  Everything here runs on the CPU."""
 from __future__ import annotations
 
 import functools
@@ -133,3 +135,168 @@ def contract_and_cost(net, n, value_coef, entropy_coef, value_loss, value_clip_o
             entropy_coef, value_loss)
     ref = reference_ppo_loss_and_grad(*args)
     return ref, cost_of(ref, fp32_ppo_loss_and_grad(*args))
+
+
+# ------------------------------------------------------------------ the head in float32, and rows on its ties
+# (tests/test_gpu_ppo_edges.py; tests/test_ppo_host.py holds all of it to the contract on the CPU)
+F32 = np.float32
+
+
+def ordered(x):
+    """float32 -> int64 that rises with the value (one step per unit in the last place)."""
+    a = np.asarray(x, dtype=np.float32)
+    i = a.reshape(-1).view(np.int32).astype(np.int64).reshape(a.shape)
+    return np.where(i >= 0, i, -(i & 0x7FFFFFFF))
+
+
+def move_units(x, k):
+    """The float32 array x moved k units in the last place (k an int or an int array)."""
+    o = ordered(x) + np.asarray(k, np.int64)
+    return np.where(o >= 0, o, (-o) | 0x80000000).astype(np.uint32).view(np.float32).reshape(np.shape(x))
+
+
+def units_apart(a, b):
+    """How many float32 values lie between two float32 results, as a count of steps."""
+    return np.abs(ordered(F32(a)) - ordered(F32(b)))
+
+
+def value_loss32(dl, value_loss):
+    """(l(dl), l'(dl)) in float32 as grad_value_loss forms them: 0.5f * dl * dl is two multiplies."""
+    ad = np.abs(dl)
+    quad = np.full(dl.shape, True) if value_loss == "mse" else ad < F32(1.0)
+    dv = np.where(quad, dl, np.where(dl > F32(0.0), F32(1.0), F32(-1.0)))
+    return np.where(quad, (F32(0.5) * dl) * dl, ad - F32(0.5)), dv
+
+
+def predict_head(logp, value, ratio, adv, target, old_logp, old_value, clip, value_clip, value_loss):
+    """The head of wab_policy_grad_ppo (include/wab.h) in numpy float32, one operation per contract
+    operation, from the float32 logp, value and ratio a run returned: every decision the kernel
+    makes is a float32 function of those bits and of the inputs, so this predicts it exactly, on
+    the ties too.  d = clamp(fl32(logp - old_logp)) by comparisons (a NaN stays a NaN); lo, hi =
+    float32(1) -+ float32(clip); clipped from the given ratio; w_eff = fl32(ratio A).  value_clip
+    None or <= 0: no value clipping (old_value is not read).
+    Returns the rows "d", "clipped", "lpol", "w_eff", "outside", "l1", "l2", "value_clipped", "lv",
+    "dv" (l'(v - t), 0 where value_clipped; not yet times value_coef) and "k3" (float64), the counts
+    "n_clipped" and "n_value_clipped", and "sums": float64 sums of lpol, lv, ratio and k3."""
+    logp, value, ratio = (np.asarray(x) for x in (logp, value, ratio))
+    assert logp.dtype == value.dtype == ratio.dtype == np.float32, "the head is predicted from float32 bits"
+    A, t, olp = (np.ascontiguousarray(x, dtype=np.float32) for x in (adv, target, old_logp))
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = logp - olp
+        d = np.where(d < F32(-30.0), F32(-30.0), np.where(d > F32(30.0), F32(30.0), d))
+        lo, hi = F32(1.0) - F32(clip), F32(1.0) + F32(clip)
+        clipped = ((A > F32(0.0)) & (ratio > hi)) | ((A < F32(0.0)) & (ratio < lo))
+        ra = ratio * A
+        lpol = np.where(clipped, -(A * np.where(A > F32(0.0), hi, lo)), -ra)
+        w_eff = np.where(clipped, F32(0.0), ra)
+        l1, dv = value_loss32(value - t, value_loss)
+        outside = np.zeros(len(A), bool)
+        l2, vcl, lv = l1.copy(), np.zeros(len(A), bool), l1
+        if value_clip is not None and float(value_clip) > 0:
+            c, ov = F32(value_clip), np.ascontiguousarray(old_value, dtype=np.float32)
+            u = value - ov
+            outside = ~(np.abs(u) <= c)
+            vc = ov + np.where(u > F32(0.0), c, -c)
+            l2 = np.where(outside, value_loss32(vc - t, value_loss)[0], l1)
+            vcl = outside & (l2 > l1)
+            lv = np.where(vcl, l2, l1)
+        dv = np.where(vcl, F32(0.0), dv)
+        d64 = d.astype(np.float64)
+        k3 = np.expm1(d64) - d64
+    out = {"d": d, "clipped": clipped, "lpol": lpol, "w_eff": w_eff, "outside": outside, "l1": l1, "l2": l2,
+           "value_clipped": vcl, "lv": lv, "dv": dv, "k3": k3, "lo": lo, "hi": hi}
+    assert all(out[k].dtype == np.float32 for k in ("d", "lpol", "w_eff", "l1", "l2", "lv", "dv"))
+    out["n_clipped"], out["n_value_clipped"] = int(clipped.sum()), int(vcl.sum())
+    out["sums"] = {"lpol": float(lpol.astype(np.float64).sum()), "lv": float(lv.astype(np.float64).sum()),
+                   "ratio": float(ratio.astype(np.float64).sum()), "k3": float(k3.sum())}
+    return out
+
+
+def tie_old_logp(logp, bound):
+    """old_logp = fl32(logp - ln bound) moved k units, k cycling over -4 .. 4 by row: the ratios of
+    these rows lie within a few units of `bound` (1.25, 0.75), several rows to a value."""
+    logp = np.asarray(logp, np.float32)
+    base = (logp.astype(np.float64) - np.log(bound)).astype(np.float32)
+    return move_units(base, np.arange(len(logp)) % 9 - 4)
+
+
+def tie_advantages(ratio):
+    """Advantages for rows of the given ratios: in the order of (ratio, row) the signs cycle
+    + - 0 + -, so two fifths are positive, two fifths negative, a fifth exactly 0, and any five
+    rows that share a ratio hold all three; the magnitudes are dyadic, the first zero is -0.0."""
+    ratio = np.asarray(ratio, np.float32)
+    order = np.lexsort((np.arange(len(ratio)), ratio))
+    sign = np.array([1.0, -1.0, 0.0, 1.0, -1.0], np.float32)
+    adv = np.empty(len(ratio), np.float32)
+    adv[order] = sign[np.arange(len(ratio)) % 5] * ((np.arange(len(ratio)) % 7 + 1) / 4.0).astype(np.float32)
+    zeros = np.nonzero(adv == 0)[0]
+    if len(zeros):
+        adv[zeros[0]] = F32(-0.0)
+    return adv
+
+
+def clip_for_bound(bound, upper):
+    """The float32 clip (as a Python float) with fl32(1.0f + clip) == bound (upper) or
+    fl32(1.0f - clip) == bound, found within a few float32 steps of |bound - 1|."""
+    bound = F32(bound)
+    start = np.abs(bound - F32(1.0))
+    for k in (0, 1, -1, 2, -2, 3, -3, 4, -4):
+        clip = move_units(start, k)
+        got = F32(1.0) + clip if upper else F32(1.0) - clip
+        if got == bound and 0.0 < float(clip) < 1.0:
+            return float(clip)
+    raise AssertionError("no float32 clip gives the bound %r" % (bound,))
+
+
+def tie_bound(ratio, adv, upper):
+    """The median of the distinct ratios among the rows the bound can clip (A > 0: upper)."""
+    r = np.unique(np.asarray(ratio)[(adv > 0) if upper else (adv < 0)])
+    return F32(r[len(r) // 2])
+
+
+def groups(x, bound):
+    """(#x < bound, #x == bound, #x > bound)."""
+    return int((x < bound).sum()), int((x == bound).sum()), int((x > bound).sum())
+
+
+def tie_value_rows(value, target, value_clip, value_loss):
+    """(old_value, target, info) with the value term's rows on its ties, from float32 `value` bits.
+    old_value = fl32(value -+ c) moved -2 .. 2 units (every sixth row 3 c away), so |u| <, ==, > c
+    all occur.  A row outside the clip gets for its target the float32 midpoint of value and vc
+    moved some of -3 .. 3 units, two rows of three the first such move at which the float32 losses
+    tie (l2 == l1), the third its own move whatever it gives.  Every fourth row (outside: of vc;
+    inside: of value) has its target 1 away, moved -1, 0, 1 units: smooth_l1's kink.  info counts
+    the rows per group."""
+    value = np.asarray(value, np.float32)
+    n, c = len(value), F32(value_clip)
+    i = np.arange(n)
+    sgn = np.where((i // 5) % 2 == 0, F32(1.0), F32(-1.0))
+    far = i % 6 == 5
+    old_value = move_units(value - sgn * np.where(far, F32(3.0) * c, c), i % 5 - 2)
+    u = value - old_value
+    outside = ~(np.abs(u) <= c)
+    vc = old_value + np.where(u > F32(0.0), c, -c)
+    t = np.asarray(target, np.float32).copy()
+    mid = ((value.astype(np.float64) + vc.astype(np.float64)) / 2.0).astype(np.float32)
+    kinks = 0
+    for j, row in enumerate(np.nonzero(outside)[0]):
+        if j % 4 == 3:
+            t[row] = move_units(vc[row] + (F32(1.0) if j % 8 == 3 else F32(-1.0)), (j // 8) % 3 - 1)
+            kinks += 1
+            continue
+        moves = [(row + m) % 7 - 3 for m in range(7 if j % 3 else 1)]
+        for m in moves:
+            cand = move_units(mid[row], m)
+            la, lb = (value_loss32(np.array([x - cand], np.float32), value_loss)[0][0] for x in (value[row], vc[row]))
+            if la == lb:
+                break
+        else:
+            cand = move_units(mid[row], moves[0])
+        t[row] = cand
+    for j, row in enumerate(np.nonzero(~outside)[0]):
+        if j % 4 == 3:
+            t[row] = move_units(value[row] + (F32(1.0) if j % 8 == 3 else F32(-1.0)), (j // 8) % 3 - 1)
+            kinks += 1
+    au = np.abs(u)
+    info = {"u": groups(au, c), "kink_rows": kinks}
+    return old_value, t, info

@@ -1,8 +1,9 @@
 """wab_policy_grad_ppo's numeric contract on the CPU (wab_gym_amd.policy.reference_ppo_loss_and_grad):
 the hand-written clipped loss and backward pass against float64 autograd of the textbook formula
 on the straight-through forward, the anchor old_logp = logp, the test rows' own guarantees
-(tests/ppo_cases.py), the header and its mirror at ABI 14, and ppo_loss_and_grad's argument checks
-that need no device."""
+(tests/ppo_cases.py), the float32 head predictor and the tie builders that
+tests/test_gpu_ppo_edges.py relies on, the header and its mirror at ABI 14, and
+ppo_loss_and_grad's argument checks that need no device."""
 import os
 import re
 
@@ -111,6 +112,132 @@ def test_case_rows_cover_every_kind_and_the_pool_suffices(net, n):
     assert (cl & (r > ppc.HI)).any() and (cl & (r < ppc.LO)).any() and (~cl & (r != 1.0)).any()
     assert vcl.any() and (clamped & ~vcl).any()
     assert [float(x) for x in ref["ppo"]][0::2] == [float(cl.sum()), float(vcl.sum())]
+
+
+# ------------------------------------------------------------------ the float32 head predictor (ppc.predict_head)
+@pytest.mark.parametrize("net", pgc.NETS, ids=str)
+@pytest.mark.parametrize("n", ppc.ROWS)
+@pytest.mark.parametrize("value_loss", ("smooth_l1", "mse"))
+def test_predictor_decides_as_the_contract_on_clear_rows(net, n, value_loss):
+    """The case rows are 8 E clear of every kink, so float32 and float64 decide alike."""
+    c = ppc.case(net, n)
+    ref, _ = ppc.contract_and_cost(net, n, 0.5, 0.0, value_loss)
+    f32 = [ref[k].numpy().astype(np.float32) for k in ("logp", "value", "ratio")]
+    p = ppc.predict_head(*f32, c["adv"], c["t"], c["old_logp"], c["old_value"], ppc.CLIP, ppc.VALUE_CLIP, value_loss)
+    assert np.array_equal(p["clipped"], ref["clipped"].numpy())
+    assert np.array_equal(p["value_clipped"], ref["value_clipped"].numpy())
+    assert [p["n_clipped"], p["n_value_clipped"]] == [int(ref["ppo"][0]), int(ref["ppo"][2])]
+    want = {"lpol": float(ref["loss"][0]), "lv": float(ref["loss"][1]), "k3": float(ref["ppo"][1]),
+            "ratio": float(ref["ppo"][3])}
+    for k in ("lpol", "lv", "ratio"):
+        assert abs(p["sums"][k] - want[k]) <= 1e-6 * abs(want[k]), (k, p["sums"][k], want[k])
+    # k3 = expm1(d) - d is about d^2 / 2, and rounding logp to float32 moves d by up to 2^-24 |logp|
+    # (the float32 difference adds 2^-24 |d|), so k3 by |expm1(d)| times that: relative to k3 that is
+    # 2^-23 |logp| / |d|, which at d = 0.0625 is already 2e-6.  So 1e-6 of the sum holds where rows
+    # with |d| = 0.5 carry the sum, which is every case of 128 rows and more (at most 7.9e-8), and
+    # cannot hold for a single row of small d: the four random-weight single rows give 1.8e-6
+    # ((449,128,150,128,5)), 1.6e-6 (ref), 2.9e-6 (odd) and, with delta = 0 where the contract's own
+    # d is the 1e-8 that rounding removes, 1 (wide).  Those are held to the mean-value bound
+    # instead, per row, summed: |k3'| = |expm1| <= expm1(|d| + delta) between the two d, delta the move
+    d64 = np.abs(p["d"].astype(np.float64))
+    delta = 2.0 ** -24 * (np.abs(f32[0].astype(np.float64)) + d64)
+    room = float((np.expm1(d64 + delta) * delta).sum())
+    err = abs(p["sums"]["k3"] - want["k3"])
+    print("%s n=%d k3: err %.3e, 1e-6 of the sum %.3e, rounding's room %.3e" % (net, n, err, 1e-6 * abs(want["k3"]), room))
+    assert err <= 1e-6 * abs(want["k3"]) or (n == 1 and err <= 1.01 * room), (p["sums"]["k3"], want["k3"], room)
+    # the effective weight and the value gradient are the contract's, to float32's rounding
+    w_ref = np.where(ref["clipped"].numpy(), 0.0, ref["ratio"].numpy() * c["adv"])
+    assert np.abs(p["w_eff"] - w_ref).max() <= 2.0 ** -22 * max(np.abs(w_ref).max(), 1e-30)
+    off = ppc.predict_head(*f32, c["adv"], c["t"], c["old_logp"], None, ppc.CLIP, None, value_loss)
+    assert off["n_value_clipped"] == 0 and not off["outside"].any() and np.array_equal(off["lv"], off["l1"])
+
+
+def one_row(ratio=1.0, adv=1.0, value=0.0, target=0.0, old_value=0.0, clip=0.25, value_clip=0.25,
+            value_loss="smooth_l1", logp=-1.0, old_logp=-1.0):
+    f = lambda x: np.array([x], np.float32)
+    return ppc.predict_head(f(logp), f(value), f(ratio), f(adv), f(target), f(old_logp), f(old_value), clip, value_clip,
+                            value_loss)
+
+
+def test_predictor_is_strict_on_every_tie():
+    """include/wab.h: clipped = (A > 0 && r > hi) || (A < 0 && r < lo); |u| <= c is inside;
+    value_clipped = l2 > l1; smooth_l1 is quadratic for |d| < 1.  One row per tie and its
+    neighbours one unit in the last place away."""
+    up, down = (lambda x: float(ppc.move_units(np.float32(x), 1))), (lambda x: float(ppc.move_units(np.float32(x), -1)))
+    hi, lo = 1.25, 0.75
+    # r == hi, r == lo: not clipped, the weight is r A; one unit past: clipped, weight 0, the loss at the bound
+    for r, adv, clipped in ((hi, 2.0, False), (up(hi), 2.0, True), (down(hi), 2.0, False), (up(hi), -2.0, False),
+                            (lo, -2.0, False), (down(lo), -2.0, True), (up(lo), -2.0, False), (down(lo), 2.0, False)):
+        p = one_row(ratio=r, adv=adv)
+        assert bool(p["clipped"][0]) == clipped, (r, adv)
+        assert p["w_eff"][0] == (0.0 if clipped else np.float32(r) * np.float32(adv))
+        assert p["lpol"][0] == (-(np.float32(adv) * np.float32(hi if adv > 0 else lo)) if clipped
+                                else -(np.float32(r) * np.float32(adv)))
+    # A == 0, of either sign, outside the clip range: not clipped, weight (-)0
+    for r in (2.0, 0.5):
+        for adv in (0.0, -0.0):
+            p = one_row(ratio=r, adv=adv)
+            assert not p["clipped"][0] and p["w_eff"][0] == 0.0 and p["n_clipped"] == 0
+            assert np.signbit(p["w_eff"][0]) == np.signbit(np.float32(adv))
+    # |u| == c: inside, the plain loss (old_value 0, c = 0.25: u = value, exact)
+    for v, outside in ((0.25, False), (up(0.25), True), (-0.25, False), (down(-0.25), True), (down(0.25), False)):
+        p = one_row(value=v, target=v, value_clip=0.25)  # (l1 = 0, l2 = l(+-c - v) > 0 once outside)
+        assert bool(p["outside"][0]) == outside and bool(p["value_clipped"][0]) == outside, v
+        assert p["dv"][0] == 0.0
+    # l2 == l1: value 1, old_value 0, c 0.25 -> vc 0.25; the target at the midpoint 0.625 ties, and
+    # the loss and its gradient are the unclipped row's
+    for value_loss in ("smooth_l1", "mse"):
+        for t, vcl in ((0.625, False), (up(0.625), True), (down(0.625), False)):
+            p = one_row(value=1.0, target=t, value_loss=value_loss)
+            assert p["outside"][0] and bool(p["value_clipped"][0]) == vcl, (value_loss, t)
+            assert (p["l1"][0] == p["l2"][0]) == (t == 0.625)
+            assert p["dv"][0] == (0.0 if vcl else np.float32(1.0) - np.float32(t))
+            assert p["lv"][0] == max(p["l1"][0], p["l2"][0])
+    # |vc - t| == 1 and |v - t| == 1: linear from 1 on (0.5 either way at 1), quadratic one unit below
+    for vc_t, quad in ((1.0, False), (down(1.0), True), (up(1.0), False), (-1.0, False), (up(-1.0), True)):
+        p = one_row(value=4.0, old_value=-0.25, target=-vc_t)  # vc = 0, vc - t = vc_t exactly
+        want = np.float32(0.5) * np.float32(vc_t) * np.float32(vc_t) if quad else np.abs(np.float32(vc_t)) - np.float32(0.5)
+        assert p["l2"][0] == want, vc_t
+        q = one_row(value=vc_t, target=0.0, value_clip=None)
+        assert q["l1"][0] == want and q["dv"][0] == (np.float32(vc_t) if quad else np.sign(np.float32(vc_t)))
+        assert one_row(value=vc_t, target=0.0, value_clip=None, value_loss="mse")["l1"][0] \
+            == np.float32(0.5) * np.float32(vc_t) * np.float32(vc_t)
+    # the clamp, by comparisons: +-30 exactly stays, beyond is cut, a NaN stays a NaN
+    for d, want in ((30.0, 30.0), (31.0, 30.0), (np.inf, 30.0), (-30.0, -30.0), (-1000.0, -30.0), (-np.inf, -30.0),
+                    (down(30.0), down(30.0))):
+        assert one_row(logp=0.0, old_logp=-d)["d"][0] == np.float32(want)
+    p = one_row(old_logp=np.nan, ratio=np.nan, adv=2.0)
+    assert np.isnan(p["d"][0]) and not p["clipped"][0] and np.isnan(p["w_eff"][0]) and np.isnan(p["sums"]["k3"])
+
+
+@pytest.mark.parametrize("net", ("ref", "odd"))
+def test_tie_builders_reach_every_group_from_the_contracts_values(net):
+    """tests/test_gpu_ppo_edges.py builds its rows from the device's bits with these; here from the
+    contract's logp and value rounded to float32, numpy's float32 exp for the ratio."""
+    n = 257
+    a, w, t = pgc.rows(net, n)
+    ref = policy.reference_loss_and_grad(pgc.state_dict(net), pgc.features(net, n), a, w, t)
+    logp, value = (ref[k].numpy().astype(np.float32) for k in ("logp", "value"))
+    for bound, upper in ((1.25, True), (0.75, False)):
+        old = ppc.tie_old_logp(logp, bound)
+        ratio = np.exp(logp - old)
+        assert ratio.dtype == np.float32
+        adv = ppc.tie_advantages(ratio)
+        assert [(adv > 0).sum(), (adv < 0).sum(), (adv == 0).sum()] == [103, 103, 51] and np.signbit(adv[adv == 0]).any()
+        b = ppc.tie_bound(ratio, adv, upper)
+        clip = ppc.clip_for_bound(b, upper)
+        assert (np.float32(1.0) + np.float32(clip) if upper else np.float32(1.0) - np.float32(clip)) == b
+        for rows in (adv > 0, adv < 0, adv == 0):
+            assert min(ppc.groups(ratio[rows], b)) >= 1, (bound, ppc.groups(ratio[rows], b))
+    for c in (0.25, 0.2):
+        for value_loss in ("smooth_l1", "mse"):
+            ov, t2, info = ppc.tie_value_rows(value, t, c, value_loss)
+            p = ppc.predict_head(logp, value, np.ones(n, np.float32), w, t2, logp, ov, 0.2, c, value_loss)
+            out = p["outside"]
+            print(net, c, value_loss, info, "l2 <, ==, > l1:", ppc.groups(p["l2"][out], p["l1"][out]))
+            assert min(info["u"]) >= 8 and info["u"][2] == out.sum()
+            assert min(ppc.groups(p["l2"][out], p["l1"][out])) >= 8
+            assert min(ppc.groups(np.abs(value - t2), np.float32(1.0))) >= 2
 
 
 def test_header_and_mirror_carry_the_ppo_abi():
