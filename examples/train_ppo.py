@@ -3,11 +3,14 @@ segment.  Per update: one closed-loop rollout with GAE advantages, whitened (wab
 wab_gae, wab_whiten), one evaluate pass for old_logp (wab_policy_evaluate; old_value is the
 rollout's value), then K x M passes of the clipped loss and its gradients (wab_policy_grad_ppo)
 over contiguous row ranges features[t0:t1] of the [T, B, F] segment, each followed by
-DeviceAdam.step() (wab_policy_adam_step).  Everything is HIP launches on one stream; the one host
-read per epoch (the printed loss, clip fraction and KL) is optional: --quiet leaves it out.
+DeviceAdam.step() (wab_policy_adam_step).  With --shuffle every epoch draws a fresh permutation of
+the segment's T B rows on the device and minibatch m is its slice perm[m n : (m + 1) n], read by
+the kernels through the index (wab_policy_grad_ppo_gather): no row is copied.  Everything is HIP
+launches on one stream; the one host read per epoch (the printed loss, clip fraction and KL) is
+optional: --quiet leaves it out.
 
     python examples/train_ppo.py [--envs 4096] [--steps 64] [--updates 20] [--epochs 4]
-                                 [--minibatches 4] [--clip 0.2] [--value-clip 0.2] [--quiet]
+                                 [--minibatches 4] [--clip 0.2] [--value-clip 0.2] [--shuffle] [--quiet]
 """
 import argparse
 import os
@@ -26,20 +29,35 @@ from train_actor_critic import Policy  # noqa: E402,F401
 
 
 def update(wrapper, policy, model, opt, T, epochs=4, minibatches=4, clip=0.2, value_clip=0.2, entropy_coef=0.0,
-           report=None):
+           report=None, shuffle=False, perm=None):
     """One rollout segment and epochs x minibatches clipped steps (opt: a DeviceAdam, whose step()
     re-packs the policy's weights).  Minibatch m is the steps [m T / M, (m + 1) T / M) of the
-    segment, a view.  Returns the ppo_loss_and_grad results as a list of lists [epoch][minibatch]
+    segment, a view; with shuffle, the rows perm[m n : (m + 1) n] of a permutation of the segment's
+    T B rows drawn afresh each epoch into `perm` (an int32 [T B] device buffer, made here when not
+    given), n = T B / M.  Returns the ppo_loss_and_grad results as a list of lists [epoch][minibatch]
     (device tensors: nothing here reads them); report(epoch, results) is called after each epoch."""
     if T % minibatches != 0:
         raise ValueError("the segment's %d steps do not split into %d minibatches" % (T, minibatches))
     r = wrapper.rollout_policy(policy, T, bootstrap_value=True, gae_lambda=0.95, whiten=True)
     old_logp = policy.evaluate(r["features"], r["actions"])["logp"]
     step = T // minibatches
+    rows_all = r["actions"].numel()
+    n = rows_all // minibatches
+    if shuffle and perm is None:
+        perm = torch.empty(rows_all, dtype=torch.int32, device=r["features"].device)
     results = []
     for e in range(epochs):
         outs = []
+        if shuffle:
+            torch.randperm(rows_all, device=perm.device, dtype=torch.int32, out=perm)
         for m in range(minibatches):
+            if shuffle:
+                outs.append(policy.ppo_loss_and_grad(r["features"], r["actions"], r["advantage"], r["target"],
+                                                     old_logp, clip=clip, old_value=r["value"],
+                                                     value_clip=value_clip, into=model, reduction="mean",
+                                                     entropy_coef=entropy_coef, rows=perm[m * n:(m + 1) * n]))
+                opt.step()
+                continue
             s = slice(m * step, (m + 1) * step)
             outs.append(policy.ppo_loss_and_grad(r["features"][s], r["actions"][s], r["advantage"][s], r["target"][s],
                                                  old_logp[s], clip=clip, old_value=r["value"][s],
@@ -67,6 +85,7 @@ def main():
     ap.add_argument("--minibatches", type=int, default=4)
     ap.add_argument("--clip", type=float, default=0.2)
     ap.add_argument("--value-clip", type=float, default=0.2, help="0: no value clipping")
+    ap.add_argument("--shuffle", action="store_true", help="minibatches from a fresh permutation of the rows per epoch")
     ap.add_argument("--quiet", action="store_true", help="no host read per epoch")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -77,11 +96,12 @@ def main():
     model = Policy(n_actions=env.n_actions).to(dev)
     policy = DevicePolicy(model, env)
     opt = DeviceAdam(policy, model, lr=3e-4, max_grad_norm=0.5)
+    perm = torch.empty(args.steps * args.envs, dtype=torch.int32, device=dev) if args.shuffle else None
     for i in range(args.updates):
         if not args.quiet:
             print("update %d" % i)
         update(wrapper, policy, model, opt, args.steps, args.epochs, args.minibatches, args.clip, args.value_clip,
-               report=None if args.quiet else print_epoch)
+               report=None if args.quiet else print_epoch, shuffle=args.shuffle, perm=perm)
     policy.check()
     print("optimizer: %s" % (opt.stats(),))
 

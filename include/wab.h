@@ -615,6 +615,49 @@ int wab_policy_evaluate(wab_policy* p, const float* features, const int8_t* acti
                         float* logp, float* value, float* entropy,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- device policy: rows gathered by an index (PPO's shuffled minibatches) --------------- */
+
+/* Defined where the four entry points below exist (they were added without a change of
+ * WAB_ABI_VERSION: nothing older changed). */
+#define WAB_HAS_POLICY_GATHER 1
+
+/* wab_policy_grad, wab_policy_grad_ppo and wab_policy_evaluate with their rows taken through an
+ * index: rows [N] int32 on the device, M the rows of the source.  Row i of the call takes every
+ * input from source row rows[i]: features is [M][in_features], and actions, weight / advantage,
+ * target, old_logp and old_value are [M].  The row outputs logp, value, entropy and ratio stay [N],
+ * written at i (nothing is scattered).  The row blocks, the slabs and every sum order are those of
+ * rows 0 .. N - 1, so each call is, bit for bit, its contiguous counterpart on gathered copies
+ * (all ten gradients, loss_out, ppo_out and the row outputs).  An index may occur more than once,
+ * and N may exceed M.  The index is read on the device at its place in the stream: a captured
+ * graph replays correctly after a new permutation has been written into the same buffer.
+ * An index outside [0, M) never becomes an address: it is clamped into [0, M - 1] before the
+ * first load that uses it, and its row is treated as a bad-action row is (left out of every sum
+ * and gradient, logp = ratio = 0, value and entropy those of the clamped source row) and counted
+ * for wab_policy_grad_bad_rows; wab_policy_grad_bad_actions keeps counting bad actions only.
+ * Launches, workspace and errors are the contiguous calls'; WAB_E_INVALID also for rows == NULL
+ * with N > 0, M outside [1, 2^31) or a rows pointer that is not 4-byte aligned. */
+int wab_policy_grad_gather(wab_policy* p, const float* features, const int8_t* actions, const float* weight,
+                           const float* target, int64_t N, const wab_policy_loss* loss,
+                           const wab_policy_weights* grads_out, float loss_out[4], float* logp, float* value,
+                           float* entropy, void* workspace, size_t workspace_bytes, void* stream,
+                           const int32_t* rows, int64_t M);
+int wab_policy_grad_ppo_gather(wab_policy* p, const float* features, const int8_t* actions, const float* advantage,
+                               const float* target, const float* old_logp, const float* old_value, int64_t N,
+                               const wab_policy_loss* loss, const wab_ppo_config* ppo,
+                               const wab_policy_weights* grads_out, float loss_out[4], float ppo_out[4],
+                               float* logp, float* value, float* entropy, float* ratio,
+                               void* workspace, size_t workspace_bytes, void* stream,
+                               const int32_t* rows, int64_t M);
+int wab_policy_evaluate_gather(wab_policy* p, const float* features, const int8_t* actions, int64_t N,
+                               float* logp, float* value, float* entropy,
+                               void* workspace, size_t workspace_bytes, void* stream,
+                               const int32_t* rows, int64_t M);
+
+/* The number of rows the latest call on this workspace left out for their index (synchronises
+ * `stream`; 0 after a contiguous call).  WAB_E_INVALID, with the count in the message, when it is
+ * not 0. */
+int wab_policy_grad_bad_rows(const wab_policy* p, const void* workspace, void* stream, uint64_t* out);
+
 /* ---- device policy: the optimizer step (actor_critic.py:104, 165) ----------------------- */
 
 /* torch.optim.Adam's step (AdamW's with `decoupled`) over the ten parameter tensors, with a

@@ -16,6 +16,20 @@ JSON line.  On a tree whose DevicePolicy has no ppo_loss_and_grad (an earlier re
 A/B of loss_and_grad in the same visit) it times loss_and_grad alone.  Exits non-zero when
 ppo_loss_and_grad's median exceeds loss_and_grad's by more than loss_and_grad's own spread
 (max - min), or when evaluate's median is not below loss_and_grad's.
+
+    python tools/ppo_time.py --gather [--parent parent.json] [--out new.json]
+
+times one minibatch of T B / 4 rows of the same segment instead, the variants alternating in the
+same way:
+    a   ppo_loss_and_grad on the contiguous quarter features[t0:t1]
+    b   ppo_loss_and_grad(rows=perm[:n]), perm a random permutation of all T B rows
+    c   what a caller without rows= has to do, all of it inside the timed span: index_select of the
+        features and of the five per-row arrays into preallocated buffers, then the contiguous call
+    d   b with rows = arange(n): the index's own cost, without the scattered rows
+    eval_a, eval_b, eval_d   the same three for evaluate
+On a tree without rows= it times a, c and eval_a alone (the parent's side of an A/B; --out keeps
+its JSON line for --parent).  Exits non-zero when b's median is not below c's, or, with --parent,
+when a's median exceeds the parent's a by more than the parent's own spread (max - min).
 """
 from __future__ import annotations
 
@@ -39,6 +53,9 @@ def main():
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--batches", type=int, default=7)
+    ap.add_argument("--gather", action="store_true", help="one minibatch of T B / 4 rows: contiguous, by index, by copies")
+    ap.add_argument("--parent", help="--gather: the JSON line of the parent's run (its --out)")
+    ap.add_argument("--out", help="write the JSON line to this file too")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ppo_time needs a GPU: a time measured anywhere else says nothing")
@@ -69,7 +86,13 @@ def main():
 
     variants = {"loss_and_grad": lambda: pol.loss_and_grad(feats, acts, adv, tgt, into=model, reduction="mean")}
     res = {"envs": B, "steps": T, "rows": N, "batches": args.batches}
-    if hasattr(pol, "ppo_loss_and_grad"):
+    if args.gather:
+        import inspect
+
+        variants = gather_variants(torch, pol, model, r, T, B,
+                                   "rows" in inspect.signature(pol.ppo_loss_and_grad).parameters)
+        res["minibatch_rows"] = N // 4
+    elif hasattr(pol, "ppo_loss_and_grad"):
         rows = torch.arange(N, device=dev).view(T, B)
         old_logp = (pol.evaluate(feats, acts)["logp"] + ((rows % 5) - 2).float() * 0.125).contiguous()
         old_value = (val + ((rows % 4).float() - 1.5) * 0.2).contiguous()
@@ -102,12 +125,70 @@ def main():
         print("%-18s median %9.3f ms  (min %9.3f, max %9.3f)" % (k, statistics.median(v), min(v), max(v)))
     pol.check()
     print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(res) + "\n")
+    if args.gather:
+        med = {k: res[k + "_ms"]["median"] for k in variants}
+        if "b" in med:
+            for pair in (("b", "a"), ("d", "a"), ("eval_b", "eval_a"), ("eval_d", "eval_a"), ("b", "c")):
+                print("%s / %s = %.4f" % (pair + (med[pair[0]] / med[pair[1]],)))
+            if not med["b"] < med["c"]:
+                raise SystemExit("rows= (b) is not faster than index_select copies and the contiguous call (c)")
+        if args.parent:
+            base = json.loads(open(args.parent).read().strip().splitlines()[-1])["a_ms"]
+            print("a: %.3f ms, the parent's %.3f (min %.3f, max %.3f)" % (med["a"], base["median"], base["min"], base["max"]))
+            if med["a"] > base["median"] + (base["max"] - base["min"]):
+                raise SystemExit("the contiguous call (a) is slower than the parent's by more than the parent's spread")
+        return
     if "ppo_loss_and_grad" in variants:
         base = res["loss_and_grad_ms"]
         if res["ppo_loss_and_grad_ms"]["median"] > base["median"] + (base["max"] - base["min"]):
             raise SystemExit("ppo_loss_and_grad is slower than loss_and_grad by more than its spread")
         if not res["evaluate_ms"]["median"] < base["median"]:
             raise SystemExit("evaluate is not faster than loss_and_grad")
+
+
+def gather_variants(torch, pol, model, r, T, B, has_rows):
+    """The --gather variants over one minibatch of T B / 4 rows of the segment r."""
+    feats, acts, adv, tgt, val = r["features"], r["actions"], r["advantage"], r["target"], r["value"]
+    dev, N = feats.device, T * B
+    n, t1 = N // 4, T // 4
+    i = torch.arange(N, device=dev).view(T, B)
+    old_logp = (pol.evaluate(feats, acts)["logp"] + ((i % 5) - 2).float() * 0.125).contiguous()
+    old_value = (val + ((i % 4).float() - 1.5) * 0.2).contiguous()
+    kw = dict(clip=0.2, value_clip=0.2, into=model, reduction="mean")
+    per_row = (acts, adv, tgt, old_logp, old_value)
+
+    def contiguous():
+        return pol.ppo_loss_and_grad(feats[:t1], acts[:t1], adv[:t1], tgt[:t1], old_logp[:t1], old_value=old_value[:t1],
+                                     **kw)
+
+    torch.manual_seed(1)
+    perm = torch.randperm(N, device=dev, dtype=torch.int32)
+    idx64 = perm[:n].long()  # (index_select's index type; made once, outside the timed span)
+    bufs = [torch.empty((n,) + tuple(x.shape[2:]), dtype=x.dtype, device=dev) for x in (feats,) + per_row]
+
+    def copies():
+        torch.index_select(feats.view(N, -1), 0, idx64, out=bufs[0])
+        for x, b in zip(per_row, bufs[1:]):
+            torch.index_select(x.view(N), 0, idx64, out=b)
+        return pol.ppo_loss_and_grad(bufs[0], bufs[1], bufs[2], bufs[3], bufs[4], old_value=bufs[5], **kw)
+
+    variants = {"a": contiguous, "c": copies, "eval_a": lambda: pol.evaluate(feats[:t1], acts[:t1])}
+    if has_rows:
+        ident = torch.arange(n, device=dev, dtype=torch.int32)
+
+        def by_index(rows):
+            return lambda: pol.ppo_loss_and_grad(feats, acts, adv, tgt, old_logp, old_value=old_value, rows=rows, **kw)
+
+        variants = {"a": contiguous, "b": by_index(perm[:n]), "c": copies, "d": by_index(ident),
+                    "eval_a": variants["eval_a"], "eval_b": lambda: pol.evaluate(feats, acts, rows=perm[:n]),
+                    "eval_d": lambda: pol.evaluate(feats, acts, rows=ident)}
+        # b and c compute the same thing
+        want, got = copies(), variants["b"]()
+        assert all(torch.equal(want[k], got[k]) for k in ("loss", "ppo_sums")), "rows= differs from the copies"
+    return variants
 
 
 if __name__ == "__main__":

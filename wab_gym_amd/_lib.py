@@ -26,6 +26,7 @@ EXPORTED = [
     "wab_gae", "wab_whiten_workspace", "wab_whiten", "wab_debug_gae_plan",
     "wab_policy_grad_workspace", "wab_policy_grad", "wab_policy_grad_bad_actions", "wab_debug_policy_grad_plan",
     "wab_policy_grad_ppo", "wab_policy_evaluate",
+    "wab_policy_grad_gather", "wab_policy_grad_ppo_gather", "wab_policy_evaluate_gather", "wab_policy_grad_bad_rows",
     "wab_policy_adam_workspace", "wab_policy_adam_step",
     # include/wab_torus.h: the Environment 2.0 torus world
     "wab2_abi_version", "wab2_last_error", "wab2_record_size", "wab2_create", "wab2_destroy",
@@ -172,6 +173,11 @@ def load():
     L.wab_policy_grad_bad_actions.argtypes = [P, P, P, P]
     L.wab_policy_grad_ppo.argtypes = [P, P, P, P, P, P, P, I64, P, P, P, P, P, P, P, P, P, P, ctypes.c_size_t, P]
     L.wab_policy_evaluate.argtypes = [P, P, P, I64, P, P, P, P, ctypes.c_size_t, P]
+    # the contiguous calls' arguments, then rows (int32 [N]) and M
+    L.wab_policy_grad_gather.argtypes = L.wab_policy_grad.argtypes + [P, I64]
+    L.wab_policy_grad_ppo_gather.argtypes = L.wab_policy_grad_ppo.argtypes + [P, I64]
+    L.wab_policy_evaluate_gather.argtypes = L.wab_policy_evaluate.argtypes + [P, I64]
+    L.wab_policy_grad_bad_rows.argtypes = [P, P, P, P]
     L.wab_debug_policy_grad_plan.argtypes = [P, I32, P]
     L.wab_policy_adam_workspace.argtypes = [P]
     L.wab_policy_adam_workspace.restype = ctypes.c_size_t

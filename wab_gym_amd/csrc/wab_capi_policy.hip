@@ -35,16 +35,25 @@ const void* policy_kernel(const wab::PolicyDims& d) {
   return policy_two_tiles(d) ? reinterpret_cast<const void*>(&wab::wab_policy_kernel<true>)
                              : reinterpret_cast<const void*>(&wab::wab_policy_kernel<false>);
 }
-template <int MODE>
+template <int MODE, bool GATHER>
 const void* policy_bwd_instance(bool two) {
-  return two ? reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<true, MODE>)
-             : reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<false, MODE>);
+  return two ? reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<true, MODE, GATHER>)
+             : reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<false, MODE, GATHER>);
 }
-const void* policy_bwd_kernel(const wab::PolicyDims& d, int mode) {
+template <bool GATHER>
+const void* policy_bwd_mode(bool two, int mode) {
+  return mode == wab::kGradModePpo    ? policy_bwd_instance<wab::kGradModePpo, GATHER>(two)
+         : mode == wab::kGradModeEval ? policy_bwd_instance<wab::kGradModeEval, GATHER>(two)
+                                      : policy_bwd_instance<wab::kGradModeGrad, GATHER>(two);
+}
+// (gather: the rows come through an index, wab_policy_*_gather)
+const void* policy_bwd_kernel(const wab::PolicyDims& d, int mode, bool gather) {
   const bool two = policy_two_tiles(d);
-  return mode == wab::kGradModePpo    ? policy_bwd_instance<wab::kGradModePpo>(two)
-         : mode == wab::kGradModeEval ? policy_bwd_instance<wab::kGradModeEval>(two)
-                                      : policy_bwd_instance<wab::kGradModeGrad>(two);
+  return gather ? policy_bwd_mode<true>(two, mode) : policy_bwd_mode<false>(two, mode);
+}
+const void* policy_wgrad_kernel(bool gather) {
+  return gather ? reinterpret_cast<const void*>(&wab::wab_policy_wgrad_kernel<true>)
+                : reinterpret_cast<const void*>(&wab::wab_policy_wgrad_kernel<false>);
 }
 
 // What a call on a handle and a policy together needs of the pair: always the same device; with
@@ -244,14 +253,18 @@ size_t wab_policy_grad_workspace(const wab_policy* p, int64_t N, int32_t chunk_r
 
 namespace {
 
-// What the three calls on wab_policy_bwd_kernel differ in: wab_policy_grad leaves the ppo fields
-// NULL, wab_policy_evaluate loss and grads_out as well.
+// What the calls on wab_policy_bwd_kernel differ in: wab_policy_grad leaves the ppo fields NULL,
+// wab_policy_evaluate loss and grads_out as well; the _gather calls set gather, rows and M
+// (features and the per-row inputs are then [M], read through rows [N]).
 struct GradCall {
   const char* name;
   int mode;  // wab::GradMode
   const float *features, *weight, *target, *old_logp, *old_value;
   const int8_t* actions;
   int64_t N;
+  bool gather;
+  const int32_t* rows;
+  int64_t M;
   const wab_policy_loss* loss;
   const wab_ppo_config* ppo;
   const wab_policy_weights* grads_out;
@@ -262,7 +275,7 @@ struct GradCall {
 };
 
 // The checks, the parameter blocks and the chunk loop of wab_policy_grad, wab_policy_grad_ppo and
-// wab_policy_evaluate.
+// wab_policy_evaluate, and of their _gather forms.
 int policy_grad_run(wab_policy* p, const GradCall& c) {
   const std::string w = std::string(c.name) + ": ";
   const bool eval = c.mode == wab::kGradModeEval, ppo = c.mode == wab::kGradModePpo;
@@ -270,6 +283,11 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
     return fail(WAB_E_INVALID, w + "NULL argument");
   const int64_t N = c.N;
   if (N < 0 || N > INT32_MAX) return fail(WAB_E_INVALID, w + "N outside [0, 2^31)");
+  if (c.gather) {
+    if (N > 0 && !c.rows) return fail(WAB_E_INVALID, w + "NULL argument (rows is required)");
+    if (c.M < 1 || c.M > INT32_MAX) return fail(WAB_E_INVALID, w + "M outside [1, 2^31)");
+    if ((reinterpret_cast<uintptr_t>(c.rows) & 3u) != 0) return fail(WAB_E_INVALID, w + "rows must be 4-byte aligned");
+  }
   if (eval) {
     if (N > 0 && (!c.features || (c.logp && !c.actions)))
       return fail(WAB_E_INVALID, w + "NULL argument (features are required, and actions with logp)");
@@ -297,7 +315,7 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
   if (!p->loaded) return fail(WAB_E_STATE, w + "call wab_policy_load first");
   const wab::GradPlan g = wab::grad_plan(p->dims);
   const wab::GradWorkspace lay = wab::grad_workspace(g, cr);
-  // (evaluate keeps nothing in the workspace but the bad-action count, its first word)
+  // (evaluate keeps nothing in the workspace but the two counts, its first two words)
   const size_t need = eval ? (size_t)256 : lay.total;
   if (c.workspace_bytes < need)
     return fail(WAB_E_INVALID, w + "the workspace has " + std::to_string(c.workspace_bytes) + " bytes, " +
@@ -314,7 +332,7 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
     if ((reinterpret_cast<uintptr_t>(q) & 3u) != 0) return fail(WAB_E_INVALID, w + "float arrays must be 4-byte aligned");
   DeviceGuard guard(p->device);
   // wab_policy_bwd_kernel's dynamic LDS can exceed the 64 KB default: as wab_policy_create's
-  const void* const bwd = policy_bwd_kernel(p->dims, c.mode);
+  const void* const bwd = policy_bwd_kernel(p->dims, c.mode, c.gather);
   HIP_TRY(raise_lds(p->device, bwd, p->lds_max));
   unsigned char* const base = static_cast<unsigned char*>(c.workspace);
   uint32_t* const bad = reinterpret_cast<uint32_t*>(base + lay.bad);
@@ -326,7 +344,7 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
   hipStream_t st = (hipStream_t)c.stream;
 
   if (eval) {
-    HIP_TRY(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(bad, 0, 2 * sizeof(uint32_t), st));
     cr = ((std::max<int64_t>(N, 1) + wab::kGradRows - 1) / wab::kGradRows) * wab::kGradRows;  // one pass
   } else {
     // the transposed image, from the packed weights as they are at this point of the stream (every
@@ -351,6 +369,8 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
   bp.target = c.target;
   bp.old_logp = c.old_logp;
   bp.old_value = ppo && c.ppo->value_clip > 0.0f ? c.old_value : nullptr;
+  bp.rows = c.gather ? c.rows : nullptr;
+  bp.M = c.gather ? c.M : 0;
   bp.clip = ppo ? c.ppo->clip : 0.0f;
   bp.value_clip = ppo ? c.ppo->value_clip : 0.0f;
   bp.w = p->w;
@@ -372,6 +392,8 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
   wp.chunk_rows = cr;
   wp.n_terms = ppo ? wab::kGradPpoTerms : wab::kGradLossTerms;
   wp.features = c.features;
+  wp.rows = bp.rows;
+  wp.M = bp.M;
   wp.ws = ws;
   wp.part = part;
   wp.slab = slab;
@@ -386,8 +408,9 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
     wp.row0 = row0;
     wp.n_blocks = (int32_t)blocks;
     wp.first = row0 == 0 ? 1 : 0;
-    hipLaunchKernelGGL(wab::wab_policy_wgrad_kernel, dim3((unsigned)g.n_tasks + 1u, (unsigned)g.slabs), dim3(64), 0,
-                       st, wp);
+    void* wargs[] = {&wp};
+    (void)hipLaunchKernel(policy_wgrad_kernel(c.gather), dim3((unsigned)g.n_tasks + 1u, (unsigned)g.slabs), dim3(64),
+                          wargs, 0, st);
     HIP_TRY(hipGetLastError());
   }
   if (eval) return WAB_OK;
@@ -461,6 +484,72 @@ int wab_policy_evaluate(wab_policy* p, const float* features, const int8_t* acti
   c.logp = logp; c.value = value; c.entropy = entropy;
   c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
   return policy_grad_run(p, c);
+}
+
+int wab_policy_grad_gather(wab_policy* p, const float* features, const int8_t* actions, const float* weight,
+                           const float* target, int64_t N, const wab_policy_loss* loss,
+                           const wab_policy_weights* grads_out, float loss_out[4], float* logp, float* value,
+                           float* entropy, void* workspace, size_t workspace_bytes, void* stream, const int32_t* rows,
+                           int64_t M) {
+  g_err.clear();
+  GradCall c = {};
+  c.name = "wab_policy_grad_gather";
+  c.mode = wab::kGradModeGrad;
+  c.features = features; c.actions = actions; c.weight = weight; c.target = target;
+  c.N = N; c.gather = true; c.rows = rows; c.M = M;
+  c.loss = loss; c.grads_out = grads_out; c.loss_out = loss_out;
+  c.logp = logp; c.value = value; c.entropy = entropy;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  return policy_grad_run(p, c);
+}
+
+int wab_policy_grad_ppo_gather(wab_policy* p, const float* features, const int8_t* actions, const float* advantage,
+                               const float* target, const float* old_logp, const float* old_value, int64_t N,
+                               const wab_policy_loss* loss, const wab_ppo_config* ppo,
+                               const wab_policy_weights* grads_out, float loss_out[4], float ppo_out[4], float* logp,
+                               float* value, float* entropy, float* ratio, void* workspace, size_t workspace_bytes,
+                               void* stream, const int32_t* rows, int64_t M) {
+  g_err.clear();
+  GradCall c = {};
+  c.name = "wab_policy_grad_ppo_gather";
+  c.mode = wab::kGradModePpo;
+  c.features = features; c.actions = actions; c.weight = advantage; c.target = target;
+  c.old_logp = old_logp; c.old_value = old_value;
+  c.N = N; c.gather = true; c.rows = rows; c.M = M;
+  c.loss = loss; c.ppo = ppo; c.grads_out = grads_out; c.loss_out = loss_out; c.ppo_out = ppo_out;
+  c.logp = logp; c.value = value; c.entropy = entropy; c.ratio = ratio;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  return policy_grad_run(p, c);
+}
+
+int wab_policy_evaluate_gather(wab_policy* p, const float* features, const int8_t* actions, int64_t N, float* logp,
+                               float* value, float* entropy, void* workspace, size_t workspace_bytes, void* stream,
+                               const int32_t* rows, int64_t M) {
+  g_err.clear();
+  GradCall c = {};
+  c.name = "wab_policy_evaluate_gather";
+  c.mode = wab::kGradModeEval;
+  c.features = features; c.actions = actions;
+  c.N = N; c.gather = true; c.rows = rows; c.M = M;
+  c.logp = logp; c.value = value; c.entropy = entropy;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  return policy_grad_run(p, c);
+}
+
+int wab_policy_grad_bad_rows(const wab_policy* p, const void* workspace, void* stream, uint64_t* out) {
+  g_err.clear();
+  if (!p || !workspace || !out) return fail(WAB_E_INVALID, "wab_policy_grad_bad_rows: NULL argument");
+  DeviceGuard guard(p->device);
+  uint32_t v = 0;
+  HIP_TRY(hipMemcpyAsync(&v, static_cast<const unsigned char*>(workspace) + 4, sizeof(v), hipMemcpyDeviceToHost,
+                         (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  *out = v;
+  if (v != 0)
+    return fail(WAB_E_INVALID, "wab_policy_grad_gather: " + std::to_string(v) +
+                                   " rows had an index outside the source's rows; they were left out of the loss "
+                                   "and the gradients");
+  return WAB_OK;
 }
 
 int wab_policy_grad_bad_actions(const wab_policy* p, const void* workspace, void* stream, uint64_t* out) {

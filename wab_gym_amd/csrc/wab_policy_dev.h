@@ -116,9 +116,12 @@ __device__ __forceinline__ void pol_store(const pol_f32x16 (&acc)[MT], const flo
 // the 16 loads issued together (addresses clamped into the batch, so none is conditional; rows
 // past the batch and the pad columns are stored as zeros).  each(e, k, v, inside) sees every
 // element after its store, with whether it is inside the array.
-template <int ROWS, class Each>
+// src(j, e) is where tile row e = wave + 4 j starts, in floats from `rows`: the overload below
+// takes the rows as they lie; a caller with an index hands in its own (wave-uniform: it depends on
+// the wave and j alone).
+template <int ROWS, class Src, class Each>
 __device__ __forceinline__ void pol_stage_rows(const float* __restrict__ rows, int F, int n_env, int k0, int kn,
-                                               uint16_t* x, int pitch, int wave, int lane, Each each) {
+                                               uint16_t* x, int pitch, int wave, int lane, Src src, Each each) {
   for (int kl = lane; kl < kn; kl += 64) {
     const int k = k0 + kl;
     const bool kin = k < F;
@@ -129,7 +132,7 @@ __device__ __forceinline__ void pol_stage_rows(const float* __restrict__ rows, i
 #pragma unroll
       for (int i = 0; i < kRows; ++i) {
         const int e = wave + 4 * (eb + i);
-        v[i] = col[(size_t)(e < n_env ? e : n_env - 1) * (size_t)F];
+        v[i] = col[src(eb + i, e)];
       }
 #pragma unroll
       for (int i = 0; i < kRows; ++i) {
@@ -140,6 +143,13 @@ __device__ __forceinline__ void pol_stage_rows(const float* __restrict__ rows, i
       }
     }
   }
+}
+
+template <int ROWS, class Each>
+__device__ __forceinline__ void pol_stage_rows(const float* __restrict__ rows, int F, int n_env, int k0, int kn,
+                                               uint16_t* x, int pitch, int wave, int lane, Each each) {
+  pol_stage_rows<ROWS>(rows, F, n_env, k0, kn, x, pitch, wave, lane,
+                       [=](int, int e) { return (size_t)(e < n_env ? e : n_env - 1) * (size_t)F; }, each);
 }
 
 // Layer 1: the input in chunks of L.KC columns through the LDS image x (region A); wave w keeps

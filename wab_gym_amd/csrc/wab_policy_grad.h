@@ -110,7 +110,9 @@ inline GradWorkspace grad_workspace(const GradPlan& g, int64_t chunk_rows) {
   auto up = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
   GradWorkspace w;
   size_t o = 0;
-  w.bad = o; o = up(o + 4u);  // uint32: rows of the latest call whose action was outside [0, A)
+  // two uint32: rows of the latest call whose action was outside [0, A); at offset 4, rows of a
+  // gathered call whose index was outside the source [0, M) (such a row counts there alone)
+  w.bad = o; o = up(o + 8u);
   w.wt = o; o = up(o + (size_t)g.wt_total * 2u);
   w.ws = o; o = up(o + (size_t)g.u_total * (size_t)chunk_rows * 2u);
   w.slab = o; o = up(o + (size_t)g.slabs * (size_t)g.n_tasks * (size_t)(kGradTiles * 1024) * 4u);
@@ -124,15 +126,15 @@ struct GradPackParams {
   GradPlan g;
   const uint16_t* w;  // the forward image (PolicyDims::w*)
   uint16_t* wt;
-  uint32_t* bad;      // zeroed for the call
+  uint32_t* bad;      // both counts, zeroed for the call
 };
 
 struct GradBwdParams {
   GradPlan g;
   int64_t N, row0;         // all rows; the chunk's first row (a multiple of 128)
   int64_t chunk_rows;      // the workspace's row pitch
-  const float* features;   // [N][F]
-  const int8_t* actions;   // [N]
+  const float* features;   // [N][F]; GATHER: the source, [M][F]
+  const int8_t* actions;   // [N]; GATHER: this and the next four [M], read at the row's source row
   const float* weight;     // [N]: the weight, or the advantage of the clipped surrogate
   const float* target;     // [N]
   const float* old_logp;   // [N] (clipped surrogate)
@@ -149,7 +151,10 @@ struct GradBwdParams {
   float* ratio;            // [N] or null (clipped surrogate)
   uint16_t* ws;            // bf16 workspace of the chunk (null: evaluate)
   double* part;            // [chunk block][wave][8]: the waves' sums of the rows' loss terms
-  uint32_t* bad;           // count of rows whose action is outside [0, A)
+  uint32_t* bad;           // bad[0]: count of rows whose action is outside [0, A); bad[1] (GATHER): of
+                           // rows whose index is outside [0, M), which are left out in the same way
+  const int32_t* rows;     // GATHER: [N], the source row of each row (null otherwise)
+  int64_t M;               // GATHER: the source's rows, in [1, 2^31)
 };
 
 struct GradWgradParams {
@@ -164,6 +169,8 @@ struct GradWgradParams {
   const double* part;
   float* slab;
   double* loss;
+  const int32_t* rows;     // GATHER: as GradBwdParams'
+  int64_t M;
 };
 
 struct GradReduceParams {
@@ -180,8 +187,10 @@ struct GradReduceParams {
 
 // the kernels (wab_policy_grad.hip), launched from wab_capi_policy.hip
 __global__ void wab_policy_grad_pack(GradPackParams p);
-template <bool TWO, int MODE = kGradModeGrad>
+// (GATHER: the rows are taken through GradBwdParams::rows, wab_policy_*_gather)
+template <bool TWO, int MODE = kGradModeGrad, bool GATHER = false>
 __global__ void wab_policy_bwd_kernel(GradBwdParams p);
+template <bool GATHER = false>
 __global__ void wab_policy_wgrad_kernel(GradWgradParams p);
 __global__ void wab_policy_grad_reduce_kernel(GradReduceParams p);
 

@@ -57,7 +57,7 @@ __device__ __forceinline__ uint16_t grad_wt_elem(const GradPackParams& p, int im
 __global__ __launch_bounds__(256) void wab_policy_grad_pack(GradPackParams p) {
   const GradPlan& g = p.g;
   const uint32_t stride = gridDim.x * 256u;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *p.bad = 0u;
+  if (blockIdx.x == 0 && threadIdx.x < 2u) p.bad[threadIdx.x] = 0u;
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < g.wt_total; i += stride) {
     if (i < g.wt2) p.wt[i] = grad_wt_elem(p, 1, i - g.wt1);
     else if (i < g.wt3) p.wt[i] = grad_wt_elem(p, 2, i - g.wt2);
@@ -130,10 +130,29 @@ __device__ __forceinline__ float grad_value_loss(float dl, bool mse, float& dv) 
   return quad ? 0.5f * dl * dl : ad - 0.5f;
 }
 
+// ------------------------------------------------------------------------ rows through an index
+// The source row of an index (wab_policy_*_gather): clamped into [0, M) before anything is loaded
+// through it.  A row whose index was outside is left out as a bad-action row is, and counted in
+// bad[1] by the head.
+__device__ __forceinline__ int64_t grad_src_row(int32_t idx, int64_t M) {
+  const int64_t i = idx;
+  return i < 0 ? 0 : (i < M ? i : M - 1);
+}
+
+// lane j's 64-bit value, the same in every lane (j wave-uniform)
+__device__ __forceinline__ size_t grad_lane_u64(size_t v, int j) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+  return (size_t)lo | ((size_t)hi << 32);
+}
+
 // ------------------------------------------------------------------------ forward, head, backward chain
 // MODE (wab_policy_grad.h): kGradModePpo changes the head's weight, value gradient and sums alone;
-// kGradModeEval ends after the head's row outputs and touches no workspace but the bad count.
-template <bool TWO, int MODE>
+// kGradModeEval ends after the head's row outputs and touches no workspace but the bad counts.
+// GATHER: row i of the call is row rows[i] of the source (features and the head's per-row inputs);
+// the blocks, the workspace, the sums and the row outputs are those of rows 0 .. N - 1 all the
+// same, so the results are the bits of the plain instance on gathered copies.
+template <bool TWO, int MODE, bool GATHER>
 __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBwdParams p) {
   constexpr bool PPO = MODE == kGradModePpo, EVAL = MODE == kGradModeEval;
   constexpr int TERMS = PPO ? kGradPpoTerms : kGradLossTerms;
@@ -155,12 +174,26 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBw
 
   uint32_t s1[2][2] = {}, s2[2][2] = {}, s3[2][2] = {}, c3[2][2] = {}, cx[2] = {};
 
+  // GATHER: lane (j, .) of wave w keeps where tile row w + 4 j (the rows the wave stages; past the
+  // batch, the batch's last) starts in the source, one index load per row and launch; the staging
+  // reads it lane to scalar, once per 16 loads
+  [[maybe_unused]] size_t src_off = 0;
+  if constexpr (GATHER) {
+    const int e = wave + 4 * r;
+    src_off = (size_t)grad_src_row(p.rows[env0 + (e < n_env ? e : n_env - 1)], p.M) * (size_t)d.F;
+  }
+
   // ---- layer 1: chunks of KC input columns through region A -> X1 (region B)
   pol_layer1<4, TWO>(
       d, L, wimg, regA, wave, lane,
       [&](int k0, int kn) {
-        pol_stage_rows<kGradRows>(p.features + (size_t)env0 * (size_t)d.F, d.F, n_env, k0, kn, regA, L.pitch_in, wave,
-                                  lane, [](int, int, float, bool) {});
+        if constexpr (GATHER)
+          pol_stage_rows<kGradRows>(p.features, d.F, n_env, k0, kn, regA, L.pitch_in, wave, lane,
+                                    [&](int j, int) { return grad_lane_u64(src_off, j); },
+                                    [](int, int, float, bool) {});
+        else
+          pol_stage_rows<kGradRows>(p.features + (size_t)env0 * (size_t)d.F, d.F, n_env, k0, kn, regA, L.pitch_in,
+                                    wave, lane, [](int, int, float, bool) {});
       },
       [] { __syncthreads(); },
       [&](const pol_f32x16(&acc)[4], int t, int j) {
@@ -216,20 +249,35 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBw
       }
       int a = 0;
       float wgt = 0.0f, tgt = 0.0f, olp = 0.0f, ov = 0.0f;
-      if (live) {
-        if (!EVAL || p.actions) a = (int)p.actions[row];
-        if (!EVAL) {
-          wgt = p.weight[row];
-          tgt = p.target[row];
-        }
-        if (PPO) {
-          olp = p.old_logp[row];
-          if (p.value_clip > 0.0f) ov = p.old_value[row];
+      // the row the head's inputs are read at: the call's row, or (GATHER) its source row
+      int64_t in = row;
+      [[maybe_unused]] bool bad_row = false;
+      if constexpr (GATHER) {
+        if (live) {
+          const int32_t idx = p.rows[row];
+          bad_row = idx < 0 || (int64_t)idx >= p.M;
+          in = grad_src_row(idx, p.M);
         }
       }
+      if (live) {
+        if (!EVAL || p.actions) a = (int)p.actions[in];
+        if (!EVAL) {
+          wgt = p.weight[in];
+          tgt = p.target[in];
+        }
+        if (PPO) {
+          olp = p.old_logp[in];
+          if (p.value_clip > 0.0f) ov = p.old_value[in];
+        }
+      }
+      if constexpr (GATHER) a = bad_row ? -1 : a;  // (from here on a bad-action row)
       const bool bad = a < 0 || a >= A;
       const bool use = live && !bad;
-      if (live && bad) atomicAdd(p.bad, 1u);
+      if constexpr (GATHER) {
+        if (live && bad) atomicAdd(bad_row ? p.bad + 1 : p.bad, 1u);
+      } else {
+        if (live && bad) atomicAdd(p.bad, 1u);
+      }
       float la = 0.0f;
       if constexpr (EVAL) {
         // (a chain of selects on `a` alone is turned into an indexed load from a scratch copy of z)
@@ -345,16 +393,23 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBw
                       });
 }
 
-template __global__ void wab_policy_bwd_kernel<false, kGradModeGrad>(GradBwdParams p);
-template __global__ void wab_policy_bwd_kernel<true, kGradModeGrad>(GradBwdParams p);
-template __global__ void wab_policy_bwd_kernel<false, kGradModePpo>(GradBwdParams p);
-template __global__ void wab_policy_bwd_kernel<true, kGradModePpo>(GradBwdParams p);
-template __global__ void wab_policy_bwd_kernel<false, kGradModeEval>(GradBwdParams p);
-template __global__ void wab_policy_bwd_kernel<true, kGradModeEval>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModeGrad, false>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModeGrad, false>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModePpo, false>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModePpo, false>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModeEval, false>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModeEval, false>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModeGrad, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModeGrad, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModePpo, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModePpo, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModeEval, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModeEval, true>(GradBwdParams p);
 
 // ------------------------------------------------------------------------ dW, db
 // the slab's row blocks of this chunk, ascending: acc[i] += D_l[rows, tile i]^T . [X_{l-1} | 1][rows, tile kt]
-template <bool FEAT>
+// (GATHER, on the FEAT path alone: a lane's eight feature rows are the source rows of its eight rows)
+template <bool FEAT, bool GATHER>
 __device__ __forceinline__ void grad_wgrad_blocks(const GradWgradParams& p, int K, int n_d, int u_d, int u_x, int grp,
                                                   int kt, int tiles, int slab, int lane,
                                                   pol_f32x16 (&acc)[kGradTiles]) {
@@ -383,6 +438,15 @@ __device__ __forceinline__ void grad_wgrad_blocks(const GradWgradParams& p, int 
   for (int i = 0; i < kGradTiles; ++i) a_and[i] = a_ok[i] ? 0xFFFFFFFFu : 0u;
   for (int64_t b = B0 + ((int64_t)slab - B0 % S + S) % S; b < B0 + p.n_blocks; b += S) {
     const size_t rb = (size_t)(b - B0) * kGradRows;
+    // GATHER: the block's 128 source rows, one index load per row and block: lane l holds those of
+    // rows l and 64 + l (a row past N clamped to N - 1 first, then its index into the source); a
+    // k-step's eight come from there lane to lane, so no feature load waits for an index load
+    [[maybe_unused]] int32_t src_lo = 0, src_hi = 0;
+    if constexpr (FEAT && GATHER) {
+      const int64_t r0 = p.row0 + (int64_t)rb + lane, r1 = r0 + 64;
+      src_lo = (int32_t)grad_src_row(p.rows[r0 < p.N ? r0 : p.N - 1], p.M);
+      src_hi = (int32_t)grad_src_row(p.rows[r1 < p.N ? r1 : p.N - 1], p.M);
+    }
 #pragma unroll 4
     for (int ks = 0; ks < kGradRows / 16; ++ks) {
       const size_t rc = rb + (size_t)(16 * ks + 8 * h);
@@ -393,6 +457,7 @@ __device__ __forceinline__ void grad_wgrad_blocks(const GradWgradParams& p, int 
         for (int j = 0; j < 8; ++j) {
           int64_t row = p.row0 + (int64_t)rc + j;
           row = row < p.N ? row : p.N - 1;  // (rows past N have D = 0)
+          if constexpr (GATHER) row = __shfl(ks < 4 ? src_lo : src_hi, (16 * ks + 8 * h + j) & 63, 64);
           v[j] = fcol[(size_t)row * (size_t)K];
         }
         bv.x = pol_bf16(v[0]) | (pol_bf16(v[1]) << 16);
@@ -416,6 +481,7 @@ __device__ __forceinline__ void grad_wgrad_blocks(const GradWgradParams& p, int 
   }
 }
 
+template <bool GATHER>
 __global__ __launch_bounds__(64) void wab_policy_wgrad_kernel(GradWgradParams p) {
   const GradPlan& g = p.g;
   const int lane = (int)threadIdx.x, task = (int)blockIdx.x, slab = (int)blockIdx.y;
@@ -452,13 +518,16 @@ __global__ __launch_bounds__(64) void wab_policy_wgrad_kernel(GradWgradParams p)
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[i][q] = sl[(size_t)((i * 16 + q) * 64)];
   }
-  if (layer == 1) grad_wgrad_blocks<true>(p, K, n_d, u_d, u_x, grp, kt, tiles, slab, lane, acc);
-  else grad_wgrad_blocks<false>(p, K, n_d, u_d, u_x, grp, kt, tiles, slab, lane, acc);
+  if (layer == 1) grad_wgrad_blocks<true, GATHER>(p, K, n_d, u_d, u_x, grp, kt, tiles, slab, lane, acc);
+  else grad_wgrad_blocks<false, false>(p, K, n_d, u_d, u_x, grp, kt, tiles, slab, lane, acc);
 #pragma unroll
   for (int i = 0; i < kGradTiles; ++i)
 #pragma unroll
     for (int q = 0; q < 16; ++q) sl[(size_t)((i * 16 + q) * 64)] = acc[i][q];
 }
+
+template __global__ void wab_policy_wgrad_kernel<false>(GradWgradParams p);
+template __global__ void wab_policy_wgrad_kernel<true>(GradWgradParams p);
 
 // ------------------------------------------------------------------------ slabs -> gradients
 __global__ __launch_bounds__(256) void wab_policy_grad_reduce_kernel(GradReduceParams p) {

@@ -9,6 +9,8 @@ action sampled in the same launch (wab_policy_act, wab_gym_amd/csrc/wab_policy.h
     old = policy.evaluate(features, actions)["logp"]                      # (wab_policy_evaluate)
     policy.ppo_loss_and_grad(features, actions, advantage, target, old, clip=0.2, into=model)
                                                  # PPO's clipped loss (wab_policy_grad_ppo)
+    policy.ppo_loss_and_grad(..., rows=perm[a:b])  # the minibatch's rows picked from the whole segment
+                                                 # by an int32 index, no copy (wab_policy_grad_ppo_gather)
 
     opt = DeviceAdam(policy, model, lr=3e-4)     # optimizer.step() and the re-pack in HIP
     opt.step()                                   # (wab_policy_adam_step): no policy.load after it
@@ -107,8 +109,10 @@ def _value_loss(d, value_loss):
 
 def _reference_head_and_backward(state_dict, features, actions, head, entropy_coef, scale, round_grads):
     """What reference_loss_and_grad and reference_ppo_loss_and_grad share: the forward, p, log p,
-    H, then head(logp, v) -> (w rows, g_v rows, loss_policy, loss_value, extras), then G_4 and the
-    straight-through backward.  Returns (loss parts, logp, v, H, grads, extras)."""
+    H, then head(logp, v, ok) -> (w rows, g_v rows, loss_policy, loss_value, extras), then G_4 and
+    the straight-through backward.  ok: the rows whose action is inside [0, A); the others are left
+    out of every sum and gradient and have logp 0 (the kernels' bad-action rule).  Returns (loss
+    parts, logp, v, H, grads, extras)."""
     import torch
 
     sd = {k: v.detach().to("cpu", torch.float32) for k, v in _state_dict(state_dict).items()}
@@ -130,14 +134,17 @@ def _reference_head_and_backward(state_dict, features, actions, head, entropy_co
     logp_all = zc - torch.log(torch.exp(zc).sum(dim=-1, keepdim=True))
     p = torch.exp(logp_all)
     H = -(p * logp_all).sum(dim=-1)
+    ok = (a >= 0) & (a < p.shape[1])
     onehot = torch.zeros_like(p)
-    onehot[torch.arange(len(a)), a] = 1.0
-    logp = (logp_all * onehot).sum(dim=-1)
-    w, gv, loss_policy, loss_value, extras = head(logp, v)
-    loss_entropy = H.sum()
+    onehot[torch.arange(len(a)), torch.where(ok, a, torch.zeros_like(a))] = 1.0
+    zero = torch.zeros_like(H)
+    logp = torch.where(ok, (logp_all * onehot).sum(dim=-1), zero)
+    w, gv, loss_policy, loss_value, extras = head(logp, v, ok)
+    loss_entropy = torch.where(ok, H, zero).sum()
 
     Da = rd(w[:, None] * (p - onehot) + entropy_coef * p * (logp_all + H[:, None]))
-    Dv = rd(gv)[:, None]
+    Da = torch.where(ok[:, None], Da, torch.zeros_like(Da))
+    Dv = rd(torch.where(ok, gv, zero))[:, None]
     grads = {"action_head.weight": Da.T @ xs[3], "action_head.bias": Da.sum(dim=0),
              "value_head.weight": Dv.T @ xs[3], "value_head.bias": Dv.sum(dim=0)}
     dx = Da @ wq["action_head"] + Dv @ wq["value_head"]
@@ -156,8 +163,28 @@ def _reference_head_and_backward(state_dict, features, actions, head, entropy_co
     return (loss_policy, loss_value, loss_entropy), logp, v, H, grads, extras
 
 
+def _reference_gather(features, rows, actions, **per_row):
+    """The host side of `rows=`: (features, actions, per-row arrays) of call rows 0 .. N - 1, row i
+    from source row rows[i] of features [M, F] or [T, B, F] (M = T B).  An index outside [0, M) is
+    clamped into it and its row given action -1: the bad-row rule is the bad-action rule."""
+    import torch
+
+    r = torch.as_tensor(rows).detach().to("cpu", torch.int64).reshape(-1)
+    x = torch.as_tensor(features).detach().to("cpu")
+    x = x.reshape(-1, x.shape[-1])
+    M = x.shape[0]
+    if M < 1:
+        raise ValueError("rows= needs a source of at least one row")
+    bad = (r < 0) | (r >= M)
+    rc = r.clamp(0, M - 1)
+    a = torch.as_tensor(actions).detach().to("cpu", torch.int64).reshape(-1)[rc]
+    a = torch.where(bad, torch.full_like(a, -1), a)
+    out = {k: None if v is None else torch.as_tensor(v).detach().to("cpu").reshape(-1)[rc] for k, v in per_row.items()}
+    return x[rc], a, out
+
+
 def reference_loss_and_grad(state_dict, features, actions, weight, target, value_coef=1.0, entropy_coef=0.0,
-                            value_loss="smooth_l1", scale=1.0, round_grads=True):
+                            value_loss="smooth_l1", scale=1.0, round_grads=True, rows=None):
     """wab_policy_grad's numeric contract in torch on the CPU, float64, written out by hand (no
     autograd).  The forward is reference_forward.  Per row, p = softmax(logits), H = -sum p log p:
 
@@ -170,17 +197,25 @@ def reference_loss_and_grad(state_dict, features, actions, weight, target, value
     (G_l itself without round_grads): dW_l = D_l^T x_{l-1}, db_l = sum_i D_l[i], dx_{l-1} = D_l
     bf16(W_l), G_{l-1} = dx_{l-1} * (z >= 0 ? 1 : float32(0.01)) * (layer 3: -4 <= leaky_relu(z) <= 4).
     Returns {"loss": (policy, value, entropy, total), "logp", "value", "entropy": [N] rows,
-    "grads": the ten tensors in torch Linear layout}, all float64."""
+    "grads": the ten tensors in torch Linear layout}, all float64.
+    A row whose action is outside [0, A) takes no part in any sum or gradient and has logp 0.
+    rows (int [N]): the call's row i is source row rows[i] of features and of every per-row array
+    (wab_policy_grad_gather); an index outside the source is clamped into it and its row treated
+    as a bad-action row."""
     import torch
 
     if value_loss not in ("smooth_l1", "mse"):
         raise ValueError("value_loss must be 'smooth_l1' or 'mse'")
+    if rows is not None:
+        features, actions, g = _reference_gather(features, rows, actions, weight=weight, target=target)
+        weight, target = g["weight"], g["target"]
     w = torch.as_tensor(weight).detach().to("cpu", torch.float64)
     tg = torch.as_tensor(target).detach().to("cpu", torch.float64)
 
-    def head(logp, v):
+    def head(logp, v, ok):
         lv, dv = _value_loss(v - tg, value_loss)
-        return w, value_coef * dv, -(w * logp).sum(), lv.sum(), None
+        zero = torch.zeros_like(v)
+        return w, value_coef * dv, torch.where(ok, -(w * logp), zero).sum(), torch.where(ok, lv, zero).sum(), None
 
     (lp, lvs, le), logp, v, H, grads, _ = _reference_head_and_backward(state_dict, features, actions, head,
                                                                        entropy_coef, scale, round_grads)
@@ -190,7 +225,7 @@ def reference_loss_and_grad(state_dict, features, actions, weight, target, value
 
 def reference_ppo_loss_and_grad(state_dict, features, actions, advantage, target, old_logp, clip=0.2, old_value=None,
                                 value_clip=None, value_coef=1.0, entropy_coef=0.0, value_loss="smooth_l1", scale=1.0,
-                                round_grads=True):
+                                round_grads=True, rows=None):
     """wab_policy_grad_ppo's numeric contract (include/wab.h) in torch on the CPU, float64, by
     hand: reference_loss_and_grad with the clipped surrogate's effective weight and the clipped
     value loss.  Per row, A the advantage, lo = float32(1) - float32(clip), hi = float32(1) +
@@ -205,11 +240,16 @@ def reference_ppo_loss_and_grad(state_dict, features, actions, advantage, target
 
     value_clip None or <= 0: no value clipping.  Returns reference_loss_and_grad's dict plus
     "ratio", "clipped", "value_clipped" rows and "ppo" = (clipped rows, sum of k3 = expm1(d) - d,
-    value-clipped rows, sum of r)."""
+    value-clipped rows, sum of r).  Bad-action rows and `rows` as reference_loss_and_grad's (a row
+    left out has ratio 0 and counts in none of the four)."""
     import torch
 
     if value_loss not in ("smooth_l1", "mse"):
         raise ValueError("value_loss must be 'smooth_l1' or 'mse'")
+    if rows is not None:
+        features, actions, g = _reference_gather(features, rows, actions, advantage=advantage, target=target,
+                                                 old_logp=old_logp, old_value=old_value)
+        advantage, target, old_logp, old_value = g["advantage"], g["target"], g["old_logp"], g["old_value"]
     A = torch.as_tensor(advantage).detach().to("cpu", torch.float64)
     tg = torch.as_tensor(target).detach().to("cpu", torch.float64)
     olp = torch.as_tensor(old_logp).detach().to("cpu", torch.float64)
@@ -220,10 +260,11 @@ def reference_ppo_loss_and_grad(state_dict, features, actions, advantage, target
         raise ValueError("value_clip > 0 needs old_value")
     c = float(np.float32(value_clip)) if vclip_on else 0.0
 
-    def head(logp, v):
+    def head(logp, v, ok):
+        zero = torch.zeros_like(v)
         d = (logp - olp).clamp(-30.0, 30.0)
-        r = torch.exp(d)
-        clipped = ((A > 0) & (r > hi)) | ((A < 0) & (r < lo))
+        r = torch.where(ok, torch.exp(d), zero)
+        clipped = ok & (((A > 0) & (r > hi)) | ((A < 0) & (r < lo)))
         bound = torch.where(A > 0, hi, lo)
         lpol = torch.where(clipped, -(A * bound), -(r * A))
         w_eff = torch.where(clipped, torch.zeros_like(A), r * A)
@@ -235,11 +276,13 @@ def reference_ppo_loss_and_grad(state_dict, features, actions, advantage, target
             vc = ov + torch.where(u > 0, c, -c)
             l2, _ = _value_loss(vc - tg, value_loss)
             outside = ~(u.abs() <= c)
-            vcl = outside & (l2 > l1)
+            vcl = ok & outside & (l2 > l1)
             lv = torch.where(vcl, l2, l1)
         gv = torch.where(vcl, torch.zeros_like(dv), value_coef * dv)
-        ppo = (clipped.to(torch.float64).sum(), (torch.expm1(d) - d).sum(), vcl.to(torch.float64).sum(), r.sum())
-        return w_eff, gv, lpol.sum(), lv.sum(), {"ratio": r, "clipped": clipped, "value_clipped": vcl, "ppo": ppo}
+        ppo = (clipped.to(torch.float64).sum(), torch.where(ok, torch.expm1(d) - d, zero).sum(),
+               vcl.to(torch.float64).sum(), r.sum())
+        return (w_eff, gv, torch.where(ok, lpol, zero).sum(), torch.where(ok, lv, zero).sum(),
+                {"ratio": r, "clipped": clipped, "value_clipped": vcl, "ppo": ppo})
 
     (lp, lvs, le), logp, v, H, grads, extra = _reference_head_and_backward(state_dict, features, actions, head,
                                                                            entropy_coef, scale, round_grads)
@@ -271,6 +314,27 @@ def check_rows(shape, features, **rows):
     if n >= 1 << 31:
         raise ValueError("loss_and_grad takes fewer than 2^31 rows")
     return n
+
+
+def check_row_index(rows, device):
+    """The checks of a `rows=` index that need no device: a 1-d contiguous int32 or int64 tensor
+    (a slice such as perm[a:b] is one) on `device`, fewer than 2^31 entries.  Returns N, its
+    length.  The values are checked on the device, by the kernels."""
+    import torch
+
+    if not isinstance(rows, torch.Tensor):
+        raise ValueError("rows must be a torch tensor of int32 (or int64) source rows")
+    if rows.dtype not in (torch.int32, torch.int64):
+        raise ValueError("rows must be int32 (or int64, converted), not %s" % str(rows.dtype).replace("torch.", ""))
+    if rows.dim() != 1:
+        raise ValueError("rows must be 1-d [N], not of shape %s" % (tuple(rows.shape),))
+    if not rows.is_contiguous():
+        raise ValueError("rows must be contiguous (stride %s): take a slice of a contiguous index" % (rows.stride(),))
+    if rows.device != torch.device(device):
+        raise ValueError("rows must be on the features' device %s, not %s" % (device, rows.device))
+    if rows.numel() >= 1 << 31:
+        raise ValueError("rows must have fewer than 2^31 entries")
+    return int(rows.numel())
 
 
 def check_loss_args(shape, features, actions, weight, target, value_loss="smooth_l1", reduction="sum", into=None,
@@ -617,7 +681,7 @@ class DevicePolicy:
 
     def loss_and_grad(self, features, actions, weight, target, *, value_coef=1.0, entropy_coef=0.0,
                       value_loss="smooth_l1", reduction="sum", into=None, accumulate=False, return_rows=False,
-                      chunk_rows=0, scale=None):
+                      chunk_rows=0, scale=None, rows=None):
         """finish_episode()'s loss and loss.backward() (actor_critic.py:148-165) on the env's stream,
         no host synchronisation: features [N, F] or [T, B, F] (viewed, not copied), actions int8,
         weight (the reference's R - value.item(), or an advantage; a constant) and target float32
@@ -627,11 +691,19 @@ class DevicePolicy:
         into=model writes (accumulate=True: adds to) each parameter's .grad; otherwise the result
         holds "grads", the ten tensors by name.  Returns 0-d device tensors "loss", "loss_policy",
         "loss_value", "entropy", and with return_rows "logp", "value", "entropy_rows" [N].
-        Rows whose action is out of range are left out and counted: check() raises for them."""
+        Rows whose action is out of range are left out and counted: check() raises for them.
+        rows (wab_policy_grad_gather): a 1-d contiguous int32 tensor [N] on the features' device (a
+        slice such as perm[a:b] is one; int64 is converted with .to(torch.int32), one small launch,
+        no synchronisation).  features and the per-row tensors are then the source ([M, F] or
+        [T, B, F], M = T B) and row i of the call is source row rows[i]; an index may repeat.  No
+        copy is made: the result is, bit for bit, that of the call on index_select copies.
+        N = rows.numel() is what "mean" divides by, and the row outputs are [N].  An index outside
+        [0, M) is never followed: its row is left out and counted, and check() raises for it."""
         t = self._torch
         n = check_loss_args(self.shape, features, actions, weight, target, value_loss, reduction, into, accumulate)
         if features.device != self.env.device:
             raise ValueError("features must be on %s" % (self.env.device,))
+        n, gather = self._row_index(rows, n)
         grads = self._grad_targets(into, accumulate)
         L = _lib.load()
         cfg = _lib.WabPolicyLoss(float(value_coef), float(entropy_coef), _lib.VALUE_LOSS[value_loss],
@@ -643,18 +715,34 @@ class DevicePolicy:
         rows = [t.empty(n, dtype=t.float32, device=self.env.device) for _ in range(3)] if return_rows else [None] * 3
         gw = _lib.WabPolicyWeights(*[grads["%s.%s" % (nm, part)].data_ptr() for nm in LAYERS
                                      for part in ("weight", "bias")])
-        _lib.check(L.wab_policy_grad(self._p, features.data_ptr(), actions.data_ptr(), weight.data_ptr(),
-                                     target.data_ptr(), n, ctypes.addressof(cfg), ctypes.addressof(gw),
-                                     loss.data_ptr(), *[None if r is None else r.data_ptr() for r in rows],
-                                     self._grad_ws.data_ptr(), self._grad_ws.numel(), self.env._stream()),
-                   "wab_policy_grad")
+        call = L.wab_policy_grad_gather if gather else L.wab_policy_grad
+        _lib.check(call(self._p, features.data_ptr(), actions.data_ptr(), weight.data_ptr(),
+                        target.data_ptr(), n, ctypes.addressof(cfg), ctypes.addressof(gw),
+                        loss.data_ptr(), *[None if r is None else r.data_ptr() for r in rows],
+                        self._grad_ws.data_ptr(), self._grad_ws.numel(), self.env._stream(), *gather),
+                   "wab_policy_grad_gather" if gather else "wab_policy_grad")
         out = {"loss": loss[3], "loss_policy": loss[0], "loss_value": loss[1], "entropy": loss[2]}
         if into is None:
             out["grads"] = grads
         if return_rows:
-            lead = tuple(features.shape[:-1])
+            lead = (n,) if gather else tuple(features.shape[:-1])
             out["logp"], out["value"], out["entropy_rows"] = [r.view(lead) for r in rows]
         return out
+
+    def _row_index(self, rows, m):
+        """(N, the _gather calls' trailing arguments) of a call whose checked source has m rows:
+        (m, ()) without an index; with one (rows.numel(), (its address, m)), an int64 index
+        converted on the stream (the copy is kept until the next call, so nothing allocated before
+        the launch can take its memory)."""
+        if rows is None:
+            return m, ()
+        n = check_row_index(rows, self.env.device)
+        if m < 1:
+            raise ValueError("rows= needs a source of at least one row")
+        if rows.dtype != self._torch.int32:
+            rows = rows.to(self._torch.int32)
+        self._rows_keep = rows
+        return n, (rows.data_ptr() if n > 0 else None, m)
 
     def _workspace(self, n, chunk_rows):
         L = _lib.load()
@@ -665,36 +753,42 @@ class DevicePolicy:
             self._grad_ws = self._torch.empty(need, dtype=self._torch.uint8, device=self.env.device)
         return self._grad_ws
 
-    def evaluate(self, features, actions=None):
+    def evaluate(self, features, actions=None, rows=None):
         """Forward and head alone (wab_policy_evaluate), one launch on the env's stream, no host
         synchronisation: {"value", "entropy"} float32 of features' leading shape ([N, F] or
         [T, B, F], viewed), and "logp" with `actions` (int8 of that shape).  The bits are those
         loss_and_grad(return_rows=True) returns, so under unchanged weights a PPO ratio built from
         this logp is exactly 1.  A row whose action is out of range has logp 0 and is counted:
-        check() raises for it."""
+        check() raises for it.  rows: as loss_and_grad's (wab_policy_evaluate_gather); the results
+        are then [N], in the index's order."""
         t = self._torch
         n = check_rows(self.shape, features, **({} if actions is None else {"actions": actions}))
         if features.device != self.env.device:
             raise ValueError("features must be on %s" % (self.env.device,))
+        n, gather = self._row_index(rows, n)
         if self._grad_ws is None:
             self._grad_ws = t.empty(256, dtype=t.uint8, device=self.env.device)
         names = (("logp",) if actions is not None else ()) + ("value", "entropy")
         rows = {k: t.empty(n, dtype=t.float32, device=self.env.device) for k in names}
-        _lib.check(_lib.load().wab_policy_evaluate(
+        L = _lib.load()
+        _lib.check((L.wab_policy_evaluate_gather if gather else L.wab_policy_evaluate)(
             self._p, features.data_ptr(), None if actions is None else actions.data_ptr(), n,
             *[rows[k].data_ptr() if k in rows else None for k in ("logp", "value", "entropy")],
-            self._grad_ws.data_ptr(), self._grad_ws.numel(), self.env._stream()), "wab_policy_evaluate")
-        lead = tuple(features.shape[:-1])
+            self._grad_ws.data_ptr(), self._grad_ws.numel(), self.env._stream(), *gather),
+            "wab_policy_evaluate_gather" if gather else "wab_policy_evaluate")
+        lead = (n,) if gather else tuple(features.shape[:-1])
         return {k: r.view(lead) for k, r in rows.items()}
 
     def ppo_loss_and_grad(self, features, actions, advantage, target, old_logp, *, clip=0.2, old_value=None,
                           value_clip=None, value_coef=1.0, entropy_coef=0.0, value_loss="smooth_l1", reduction="sum",
-                          into=None, accumulate=False, return_rows=False, chunk_rows=0, scale=None):
+                          into=None, accumulate=False, return_rows=False, chunk_rows=0, scale=None, rows=None):
         """loss_and_grad with PPO's clipped surrogate (wab_policy_grad_ppo; the contract is
         reference_ppo_loss_and_grad): old_logp from evaluate() before the first step, float32 of
         the leading shape; value_clip > 0 clips the value loss around old_value (the rollout's
         value).  A minibatch is a contiguous row range, features[t0:t1] of a [T, B, F] segment (a
-        view); accumulate=True sums several ranges into one step.  Returns loss_and_grad's keys
+        view), or with rows= (as loss_and_grad's; wab_policy_grad_ppo_gather) any rows of the whole
+        segment, such as a slice of a fresh permutation per epoch: every per-row tensor is then the
+        segment's.  accumulate=True sums several minibatches into one step.  Returns loss_and_grad's keys
         and 0-d device tensors "clip_fraction", "approx_kl" (Schulman's k3), "value_clip_fraction"
         and "ratio_mean", each a sum over the rows divided by N on the device ("ppo_sums": the
         four sums themselves); with return_rows also "ratio"."""
@@ -703,6 +797,7 @@ class DevicePolicy:
                            value_loss, reduction, into, accumulate)
         if features.device != self.env.device:
             raise ValueError("features must be on %s" % (self.env.device,))
+        n, gather = self._row_index(rows, n)
         # (no rows: nothing to clip, and an empty old_value has no address to pass)
         vclip = float(value_clip) if value_clip is not None and float(value_clip) > 0 and n > 0 else 0.0
         grads = self._grad_targets(into, accumulate)
@@ -716,12 +811,13 @@ class DevicePolicy:
         rows = [t.empty(n, dtype=t.float32, device=self.env.device) for _ in range(4)] if return_rows else [None] * 4
         gw = _lib.WabPolicyWeights(*[grads["%s.%s" % (nm, part)].data_ptr() for nm in LAYERS
                                      for part in ("weight", "bias")])
-        _lib.check(_lib.load().wab_policy_grad_ppo(
+        L = _lib.load()
+        _lib.check((L.wab_policy_grad_ppo_gather if gather else L.wab_policy_grad_ppo)(
             self._p, features.data_ptr(), actions.data_ptr(), advantage.data_ptr(), target.data_ptr(),
             old_logp.data_ptr(), old_value.data_ptr() if vclip > 0 else None, n, ctypes.addressof(cfg),
             ctypes.addressof(ppo), ctypes.addressof(gw), sums.data_ptr(), sums[4:].data_ptr(),
-            *[None if r is None else r.data_ptr() for r in rows], ws.data_ptr(), ws.numel(), self.env._stream()),
-            "wab_policy_grad_ppo")
+            *[None if r is None else r.data_ptr() for r in rows], ws.data_ptr(), ws.numel(), self.env._stream(),
+            *gather), "wab_policy_grad_ppo_gather" if gather else "wab_policy_grad_ppo")
         out = {"loss": sums[3], "loss_policy": sums[0], "loss_value": sums[1], "entropy": sums[2]}
         diag = sums[4:] / float(max(n, 1))
         out["clip_fraction"], out["approx_kl"], out["value_clip_fraction"], out["ratio_mean"] = diag.unbind(0)
@@ -729,21 +825,23 @@ class DevicePolicy:
         if into is None:
             out["grads"] = grads
         if return_rows:
-            lead = tuple(features.shape[:-1])
+            lead = (n,) if gather else tuple(features.shape[:-1])
             out["logp"], out["value"], out["entropy_rows"], out["ratio"] = [r.view(lead) for r in rows]
         return out
 
     def check(self):
         """Synchronises; raises IndexError if the latest loss_and_grad left rows out because their
-        action was outside [0, n_actions)."""
+        action was outside [0, n_actions), or (rows=) their index outside the source's rows."""
         if self._grad_ws is None:
             return
-        bad = ctypes.c_uint64(0)
-        rc = _lib.load().wab_policy_grad_bad_actions(self._p, self._grad_ws.data_ptr(), self.env._stream(),
-                                                     ctypes.byref(bad))
-        if bad.value:
-            raise IndexError(_lib.load().wab_last_error().decode(errors="replace"))
-        _lib.check(rc, "wab_policy_grad_bad_actions")
+        L = _lib.load()
+        for call, name in ((L.wab_policy_grad_bad_actions, "wab_policy_grad_bad_actions"),
+                           (L.wab_policy_grad_bad_rows, "wab_policy_grad_bad_rows")):
+            bad = ctypes.c_uint64(0)
+            rc = call(self._p, self._grad_ws.data_ptr(), self.env._stream(), ctypes.byref(bad))
+            if bad.value:
+                raise IndexError(L.wab_last_error().decode(errors="replace"))
+            _lib.check(rc, name)
 
     def close(self):
         if getattr(self, "_p", None) is not None and self._p.value:
