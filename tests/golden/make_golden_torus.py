@@ -10,7 +10,7 @@ Drives the unmodified `WAB_Environment2` / `World` (`Environment 2.0/WAB_Environ
     per turn:  for entity i in id order:  obs = env.get_obs(i);  a = policy(obs);
                                           reward, done = env.take_action(i, a)
                "autoreset" sets: reset_environment() after a turn in which every ostrich is done
-               or the world's turn count reached options["max_turns"] (the batched surface's
+               or the world's turn count reached options["max_turns"] (0: no cap; the batched surface's
                episode rule; the reference itself never resets on its own)
 
 Recorded per turn and world: every entity's get_obs() (visible-objects frame + internal obs)
@@ -23,7 +23,8 @@ Actions are inputs: ostriches walk to the nearest visible bush or at random (rol
 included), wolves chase the nearest visible ostrich or walk at random, bushes send 0; a few
 actions outside every branch of the act functions (World.py:25-43, 61-73) are mixed in.
 
-Usage:  python tests/golden/make_golden_torus.py [set ...]
+Usage:  python tests/golden/make_golden_torus.py [set ... | edge]
+(no argument: the five sets of SETS; "edge": every set of EDGE_SETS)
 """
 from __future__ import annotations
 
@@ -79,8 +80,63 @@ SETS = {
                                          "wolf_view_radius": 6, "max_turns": 40},
                      list(range(500, 504)), 90, "autoreset"),
 }
+# Worlds at the edges of what include/wab_torus.h accepts: two worlds each, short episodes so that
+# resets fall inside the run.  World ids and turn counts were chosen so that the reference meets
+# what tests/test_torus_oracle.py::test_edge_sets_hold_what_they_are_for asks of them.
+EDGE_SETS = {
+    # the largest of everything: sides 127 (deltas up to +-63 through the wrap), N = 32 with 8
+    # ostriches (R = 112), a lookout radius of 2^20 (the wrap rule's `if` branch alone, every
+    # entity a row), a gatherer radius of 0 (the ostrich sees its own tile only), both food
+    # values 255 (one eat empties a bush)
+    "torus_edge_largest": (127, 127, (8, 8, 16), {"lookout_view_radius": 1 << 20, "gatherer_view_radius": 0,
+                                                  "wolf_view_radius": 90, "food_per_bush": 255,
+                                                  "food_given_per_turn": 255, "max_turns": 12},
+                           [700, 701], 24, "autoreset"),
+    # a line: H = 1 (every Delta_Y is 0, y wraps every move), one radius on the half side (63),
+    # one a step past it (64), bushes that are empty from the start
+    "torus_edge_line": (127, 1, (1, 2, 2), {"lookout_view_radius": 63, "gatherer_view_radius": 64,
+                                            "wolf_view_radius": 64, "food_per_bush": 0, "max_turns": 9},
+                        [710, 711], 40, "autoreset"),
+    # the unit world: everything on the one tile, every move wraps back onto it
+    "torus_edge_unit": (1, 1, (1, 1, 1), {"lookout_view_radius": 1, "gatherer_view_radius": 0,
+                                          "wolf_view_radius": 2, "max_turns": 7},
+                        [720, 721], 30, "autoreset"),
+    # small odd sides: the wrap's shorter-way choice has no tie.  In 5x3 the radius 2 reaches
+    # past the half side along y (1.5) and not along x (2.5); in 9x13 the radii (5, 6) reach past
+    # it along x (4.5) and not along y (6.5).  A bush's food goes in one eat in both.
+    "torus_edge_odd5x3": (5, 3, (2, 2, 3), {"lookout_view_radius": 2, "gatherer_view_radius": 1,
+                                            "wolf_view_radius": 2, "food_per_bush": 5, "max_turns": 11},
+                          [730, 731], 40, "autoreset"),
+    "torus_edge_odd9x13": (9, 13, (3, 3, 4), {"lookout_view_radius": 6, "gatherer_view_radius": 5,
+                                              "wolf_view_radius": 5, "food_per_bush": 7,
+                                              "food_given_per_turn": 7, "max_turns": 13},
+                           [740, 741], 40, "autoreset"),
+    # empty classes: a lone ostrich (N = 1, R = 32), no ostriches, no bushes, bushes only
+    "torus_edge_lone_ostrich": (7, 5, (1, 0, 0), {"lookout_view_radius": 3, "max_turns": 8,
+                                                  "ostrich_starting_food": 5.5},
+                                [750, 751], 30, "autoreset"),
+    "torus_edge_no_ostriches": (7, 5, (0, 3, 2), {"wolf_view_radius": 3, "max_turns": 10},
+                                [760, 761], 30, "autoreset"),
+    "torus_edge_no_bushes": (7, 5, (2, 3, 0), {"lookout_view_radius": 4, "gatherer_view_radius": 2,
+                                               "wolf_view_radius": 3, "max_turns": 10},
+                             [770, 771], 30, "autoreset"),
+    "torus_edge_bushes_only": (7, 5, (0, 0, 3), {"max_turns": 7}, [780, 781], 20, "autoreset"),
+    # max_turns = 0 is "no cap": only a turn that leaves every ostrich done (starved or killed)
+    # resets the world (nothing in Environment 2.0 lowers an ostrich's food, so the small
+    # ostrich_starting_food starves nobody: the resets are the kills of world 791's hunting wolves)
+    "torus_edge_no_cap": (5, 3, (2, 3, 2), {"max_turns": 0, "ostrich_starting_food": 4.5,
+                                            "lookout_view_radius": 3, "gatherer_view_radius": 2,
+                                            "wolf_view_radius": 3, "food_per_bush": 3,
+                                            "food_given_per_turn": 2},
+                          [790, 791], 40, "autoreset"),
+    # R = 128, the largest record: 29 bushes
+    "torus_edge_r128": (11, 7, (1, 2, 29), {"lookout_view_radius": 5, "gatherer_view_radius": 3,
+                                            "wolf_view_radius": 6, "food_per_bush": 10, "max_turns": 15},
+                        [800, 801], 30, "autoreset"),
+}
+ALL_SETS = dict(SETS, **EDGE_SETS)
 # per-set extras: the hunt worlds' policy; the placed set's explicit resets (turn -> positions)
-POLICIES = {"torus_c3": {g: HUNT for g in range(400, 406)}}
+POLICIES = {"torus_c3": {g: HUNT for g in range(400, 406)}, "torus_edge_no_cap": {791: HUNT}}
 PLACED_RESETS = {"torus_placed": (0, 30, 61)}
 
 
@@ -153,7 +209,7 @@ def choose_action(rng, kind, rec, off, types, policy=POLICY):
 
 
 def run_set(name):
-    W, H, (no, nw, nb), opts, world_ids, T, protocol = SETS[name]
+    W, H, (no, nw, nb), opts, world_ids, T, protocol = ALL_SETS[name]
     N = no + nw + nb
     types = ["Ostrich"] * no + ["Wolf"] * nw + ["Bush"] * nb
     R, off = th.record_layout(N, nb)
@@ -218,8 +274,10 @@ def run_set(name):
                 out["done"][t, e, i] = bool(d)
             objs = list(ents["Entity_Object"])
             st = [o.get_status() for o in objs[:no]]
+            # (max_turns = 0 is "no cap", as include/wab_torus.h has it)
             if protocol == "autoreset" and ((no > 0 and all(s != 0 for s in st)) or
-                                            env._world._current_turn >= full["max_turns"]):
+                                            (full["max_turns"] > 0 and
+                                             env._world._current_turn >= full["max_turns"])):
                 env.reset_environment()
                 out["world_reset"][t, e] = True
                 resets += 1
@@ -248,4 +306,5 @@ def run_set(name):
 
 if __name__ == "__main__":
     for n in sys.argv[1:] or list(SETS):
-        run_set(n)
+        for m in (list(EDGE_SETS) if n == "edge" else [n]):
+            run_set(m)

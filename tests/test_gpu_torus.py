@@ -3,7 +3,9 @@ real Environment 2.0 reference and against the C oracle, bit for bit.
 
 Sizes: every golden world replayed turn by turn and as one rollout launch; lockstep against the
 oracle at B = 4096 and at the bench's configuration (B = 65536, 32x32, 1/8/16, 64-turn rollout
-launches); ragged batches, misaligned action slices, masked resets, no autoreset."""
+launches); ragged batches, misaligned action slices, masked resets, no autoreset; the edge
+sets, an 18-split sweep of the kernel instances, record sizes and empty classes at B = 193, the
+entity windows on four of them, and a world on and past each limit of include/wab_torus.h."""
 from __future__ import annotations
 
 import json
@@ -16,6 +18,11 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SETS = ["torus_c3", "torus_multi", "torus_tiny", "torus_continue", "torus_placed"]
+# worlds at the edges of what include/wab_torus.h accepts (tests/test_torus_oracle.py pins the
+# oracle on them too): two worlds each, at most 40 turns
+EDGE_SETS = ["torus_edge_largest", "torus_edge_line", "torus_edge_unit", "torus_edge_odd5x3",
+             "torus_edge_odd9x13", "torus_edge_lone_ostrich", "torus_edge_no_ostriches",
+             "torus_edge_no_bushes", "torus_edge_bushes_only", "torus_edge_no_cap", "torus_edge_r128"]
 
 
 def load_set(name):
@@ -60,7 +67,7 @@ def check_state(env, d, t, e, where):
     assert np.array_equal(s["status"][0, :NO], d["status"][t, e, :NO]), where + " status"
 
 
-@pytest.mark.parametrize("name", SETS)
+@pytest.mark.parametrize("name", SETS + EDGE_SETS)
 def test_torus_steps_match_reference_golden(name):
     import torch
 
@@ -87,7 +94,7 @@ def test_torus_steps_match_reference_golden(name):
                 check_state(env, d, t, e, where)
 
 
-@pytest.mark.parametrize("name", SETS)
+@pytest.mark.parametrize("name", SETS + EDGE_SETS)
 def test_torus_rollout_matches_reference_golden(name):
     """Every golden world's whole run as ONE rollout launch (state on chip between turns)."""
     import torch
@@ -115,7 +122,31 @@ def test_torus_rollout_matches_reference_golden(name):
         check_state(env, d, T - 1, e, "%s world %d after the rollout" % (name, g))
 
 
-def _lockstep(meta, B, T, rollout_T=0, base=0, seed_actions=7, check_every=1):
+def _note(seen, meta, records, done, world_reset):
+    """What one turn of the oracle held, added to seen: world resets; visible rows other than the
+    observer's own; ostriches done.  An ostrich's done flag is written when it acts, and the
+    wolves act after it: the kill of a world's last ostrich resets the world in the same turn
+    and never reaches a done flag (with one ostrich, none ever does).  It shows as a reset
+    before the turn cap, which the oracle does only when every ostrich is done: those count."""
+    B, N = records.shape[:2]
+    NO, cap = meta["num_ostriches"], meta["options"]["max_turns"]
+    vis = records[..., 16:20].copy().view(np.uint32)[..., 0]
+    not_self = ~(np.uint32(1) << np.arange(N, dtype=np.uint32))
+    age = seen.setdefault("_age", np.zeros(B, np.int64))
+    age += 1
+    wr = world_reset.astype(bool)
+    early = int((wr & (age < cap)).sum()) if cap > 0 else int(wr.sum())
+    age[wr] = 0
+    seen["resets"] = seen.get("resets", 0) + int(wr.sum())
+    seen["others"] = seen.get("others", 0) + int(np.count_nonzero(vis & not_self))
+    seen["ostrich_done"] = seen.get("ostrich_done", 0) + int(done[:, :NO].sum()) + early
+
+
+def _lockstep(meta, B, T, rollout_T=0, base=0, seed_actions=7, check_every=1, tail_rollout=0, seen=None):
+    """T turns of B worlds against the oracle, as single-turn launches or (rollout_T) as rollout
+    launches of that many turns; tail_rollout > 0 adds one more rollout launch of that many turns
+    at the end.  seen (a dict) collects, from the ORACLE's outputs alone, what the run held:
+    world resets, visible rows other than the observer, ostrich dones."""
     import torch
 
     env = make_env(meta, base, batch=B)
@@ -125,14 +156,18 @@ def _lockstep(meta, B, T, rollout_T=0, base=0, seed_actions=7, check_every=1):
     rng = np.random.RandomState(seed_actions)
     N = env.N
     hi = np.array([6] * meta["num_ostriches"] + [5] * meta["num_wolves"] + [1] * meta["num_bushes"])
+    T_single, T = T, T + tail_rollout
     t = 0
     while t < T:
+        rollout_T = tail_rollout if t >= T_single else rollout_T
         n = rollout_T or 1
         acts = (rng.randint(0, 1 << 30, size=(n, B, N)) % hi).astype(np.int8)
         if rollout_T:
             obs, rew, done, wr = env.rollout(torch.as_tensor(acts))  # (device; one turn at a time to host)
         for k in range(n):
             r_o, rw_o, d_o, wr_o = orc.step(acts[k], nthreads=16)
+            if seen is not None:
+                _note(seen, meta, r_o, d_o, wr_o)
             if rollout_T:
                 g = (obs[k].cpu().numpy(), rew[k].cpu().numpy(), done[k].cpu().numpy(), wr[k].cpu().numpy())
             else:
@@ -151,6 +186,8 @@ def _lockstep(meta, B, T, rollout_T=0, base=0, seed_actions=7, check_every=1):
         assert np.array_equal(s[key], so[key]), key
     c = env.counters()
     assert c["turns"] == B * T
+    if seen is not None:  # the B resets of reset_environment() and the oracle's autoresets
+        assert c["resets"] == B + seen["resets"], (c, seen)
     return env
 
 
@@ -185,6 +222,74 @@ def test_torus_rollout_misaligned_actions():
 def test_torus_tiny_worlds_lockstep():
     _, meta = load_set("torus_tiny")
     _lockstep(meta, 640, 100, rollout_T=25)
+
+
+# ---------------------------------------------------------------- the instance sweep
+# (NO, NW, NB): between them NKK = ceil(N / 4) = 1, 2, 3, 5, 6, 7, 8 for whole turns (4 is torus_multi's;
+# the generic <7> at N = 25, 26 and 28), R / 16 = 2..8, records with and without padding, every empty class, NO = 8, N = 32
+SWEEP_SPLITS = [(1, 0, 0), (0, 0, 3), (2, 1, 1), (0, 3, 2), (8, 0, 0), (3, 4, 5), (1, 3, 8), (2, 8, 10),
+                (4, 9, 8), (8, 8, 8), (2, 8, 16), (1, 16, 8), (1, 9, 18), (8, 8, 13), (8, 8, 16), (1, 2, 29),
+                (0, 1, 31), (8, 24, 0)]
+# the world each split meets with a side that is odd, and the one larger than any radius of its
+# case ("roomy"); between them 6x6, 12x10, 127x127, 127x1, 1x127, 1x1, 2x3, 32x32 and 64x5.  The
+# thin splits stay off 127x127, where they would meet nothing.
+SWEEP_SHAPES = {
+    (1, 0, 0): ((127, 127), (6, 6)), (0, 0, 3): ((127, 1), (12, 10)), (2, 1, 1): ((1, 1), (32, 32)),
+    (0, 3, 2): ((1, 127), (127, 127)), (8, 0, 0): ((2, 3), (6, 6)), (3, 4, 5): ((64, 5), (6, 6)),
+    (1, 3, 8): ((127, 1), (6, 6)), (2, 8, 10): ((127, 1), (6, 6)), (4, 9, 8): ((1, 127), (127, 127)),
+    (8, 8, 8): ((1, 1), (12, 10)), (2, 8, 16): ((2, 3), (32, 32)), (1, 16, 8): ((64, 5), (12, 10)),
+    (1, 9, 18): ((1, 127), (6, 6)), (8, 8, 13): ((2, 3), (12, 10)), (8, 8, 16): ((127, 127), (32, 32)),
+    (1, 2, 29): ((2, 3), (12, 10)), (0, 1, 31): ((64, 5), (6, 6)), (8, 24, 0): ((64, 5), (127, 127)),
+}
+SWEEP_FOOD = [0, 7, 255]
+# max_turns = 0 (no cap, with ostrich_starting_food = 3.5) needs every ostrich of a world killed
+# for a reset: cases whose world is small and whose split has both ostriches and wolves
+SWEEP_NO_CAP = {((2, 1, 1), "odd"), ((1, 16, 8), "odd"), ((8, 8, 13), "odd"), ((3, 4, 5), "roomy"),
+                ((1, 3, 8), "roomy"), ((2, 8, 10), "roomy"), ((1, 9, 18), "roomy")}
+
+
+def _sweep_case(k, kind, B):
+    """The k-th split on its odd or its roomy shape: radii, food values and starting_role
+    rotate with k.  An odd case draws its three radii from {0, 3, the half side, 2^20}, a roomy
+    one from {0, 3, the half side} (the shorter side's, so the world is larger than each)."""
+    split = SWEEP_SPLITS[k]
+    W, H = SWEEP_SHAPES[split][kind != "odd"]
+    radii = [0, 3, max(W, H) // 2, 1 << 20] if kind == "odd" else [0, 3, min(W, H) // 2]
+    j = k + (kind != "odd")
+    opts = {"lookout_view_radius": radii[j % len(radii)], "gatherer_view_radius": radii[(j + 1) % len(radii)],
+            "wolf_view_radius": radii[(j + 2) % len(radii)], "food_per_bush": SWEEP_FOOD[j % 3],
+            "food_given_per_turn": SWEEP_FOOD[(j // 3) % 3], "starting_role": j % 2, "max_turns": 17}
+    if (split, kind) in SWEEP_NO_CAP:
+        opts.update(max_turns=0, ostrich_starting_food=3.5)
+    return {"width": W, "height": H, "num_ostriches": split[0], "num_wolves": split[1],
+            "num_bushes": split[2], "options": opts, "seed": 0x5EED + k, "protocol": "autoreset"}, B
+
+
+# every split at B = 193 (four workgroups, the last with one world; B * N odd for odd N: the
+# per-byte action path) on an odd and on a roomy shape; the splits with an even N once more at
+# B = 196, whose [B, N] action slices are 4-byte aligned (the scalar action loads)
+SWEEP_CASES = [(k, kind, 193) for k in range(len(SWEEP_SPLITS)) for kind in ("odd", "roomy")] + \
+              [(k, "odd" if k % 2 else "roomy", 196) for k, s in enumerate(SWEEP_SPLITS) if sum(s) % 2 == 0]
+
+
+@pytest.mark.parametrize("k,kind,B", SWEEP_CASES,
+                         ids=["%d-%d-%d_%s_b%d" % (SWEEP_SPLITS[k] + (kind, B)) for k, kind, B in SWEEP_CASES])
+def test_torus_instance_sweep_vs_oracle(k, kind, B):
+    """Every kernel instance, record size and empty class against the oracle: 24 single-turn
+    launches, then one rollout launch of 21 turns (an odd T: each of the two action buffers ends
+    a launch), every turn's records, rewards, dones and resets, the final state and the counters.
+    The run must also have held something, by the oracle's outputs alone."""
+    meta, B = _sweep_case(k, kind, B)
+    seen = {}
+    _lockstep(meta, B, 24, base=1000 * k, seed_actions=100 + k, tail_rollout=21, seen=seen)
+    del seen["_age"]
+    print("sweep", SWEEP_SPLITS[k], kind, B, meta["width"], meta["height"], meta["options"], seen)
+    NO, NW, NB = SWEEP_SPLITS[k]
+    assert seen["resets"] > 0, seen
+    if NO + NW + NB > 1:
+        assert seen["others"] > 0, seen
+    if NO and NW:  # (no ostrich starves in Environment 2.0: a done ostrich is a killed one)
+        assert seen["ostrich_done"] > 0, seen
 
 
 def test_torus_masked_reset_and_no_autoreset():
@@ -315,6 +420,40 @@ def test_torus_per_entity_equals_turn_launch_at_scale():
         assert np.array_equal(sa[k], sb[k]), k
 
 
+@pytest.mark.parametrize("split", [(2, 1, 1), (8, 8, 8), (8, 8, 16), (0, 1, 31)], ids=lambda s: "%d-%d-%d" % s)
+def test_torus_entity_windows_equal_turn_launch(split):
+    """N get_obs + take_action launches per turn (the generic instance with one-entity windows,
+    magic_m / magic_b recomputed from the window) == one whole-turn launch, on instances other
+    than the benched one: windows of a single mover, a single bush, the last entity of 32, and
+    a first bush that is entity 1."""
+    import torch
+
+    k = SWEEP_SPLITS.index(split)
+    meta, B = _sweep_case(k, "roomy", 193)
+    a_env = make_env(meta, 50 * k, batch=B)
+    b_env = make_env(meta, 50 * k, batch=B)
+    a_env.reset_environment()
+    b_env.reset_environment()
+    N = a_env.N
+    rng = np.random.RandomState(40 + k)
+    hi = np.array([6] * split[0] + [5] * split[1] + [1] * split[2])
+    resets = 0
+    for t in range(6):
+        acts = torch.as_tensor((rng.randint(0, 1 << 20, size=(B, N)) % hi).astype(np.int8), device="cuda:0")
+        obs, rew, done, info = a_env.step(acts)
+        for i in range(N):
+            rec = b_env.get_obs(i)
+            assert torch.equal(rec, obs[:, i]), (t, i)
+            r, dn, inf = b_env.take_action(i, acts[:, i].contiguous())
+            assert torch.equal(r, rew[:, i]) and torch.equal(dn, done[:, i]), (t, i)
+        assert torch.equal(inf["world_reset"], info["world_reset"]), t
+        resets += int(info["world_reset"].sum())
+    sa, sb = a_env.state(), b_env.state()
+    for key in sa:
+        assert np.array_equal(sa[key], sb[key]), key
+    assert a_env.counters() == b_env.counters() == {"turns": 6 * B, "resets": B + resets}
+
+
 def test_torus_rejects_bad_options():
     from wab_gym_amd.torus import BatchedWABEnvironment2
 
@@ -323,6 +462,97 @@ def test_torus_rejects_bad_options():
                {"game_options": {"lookout_view_radius": 4.5}}):
         with pytest.raises(ValueError):
             BatchedWABEnvironment2(num_worlds=64, device="cuda:0", **kw)
+
+
+# (constructor arguments) on each limit of include/wab_torus.h, and one step past it
+TORUS_ON_LIMIT = [
+    dict(world_width=127, world_height=127), dict(world_width=127, world_height=1),
+    dict(world_width=1, world_height=127), dict(world_width=1, world_height=1),
+    dict(num_ostriches=8, num_wolves=8, num_bushes=16),   # N = 32, NO = 8
+    dict(num_ostriches=0, num_wolves=0, num_bushes=32), dict(num_ostriches=0, num_wolves=32, num_bushes=0),
+    dict(num_ostriches=8, num_wolves=0, num_bushes=0),
+    dict(num_ostriches=1, num_wolves=0, num_bushes=0), dict(num_ostriches=0, num_wolves=1, num_bushes=0),
+    dict(num_ostriches=0, num_wolves=0, num_bushes=1),    # N = 1 of each class
+    dict(game_options={"food_per_bush": 255, "food_given_per_turn": 255}),
+    dict(game_options={"food_per_bush": 0, "food_given_per_turn": 0}),
+    dict(game_options={"lookout_view_radius": 1 << 20, "gatherer_view_radius": 1 << 20,
+                       "wolf_view_radius": 1 << 20}),
+    dict(game_options={"lookout_view_radius": 0, "gatherer_view_radius": 0, "wolf_view_radius": 0}),
+    dict(game_options={"max_turns": 0}),
+]
+TORUS_PAST_LIMIT = [
+    dict(world_width=128), dict(world_height=128), dict(world_width=0), dict(world_height=0),
+    dict(world_width=-1),
+    dict(num_ostriches=8, num_wolves=8, num_bushes=17),   # N = 33
+    dict(num_ostriches=0, num_wolves=33, num_bushes=0), dict(num_ostriches=0, num_wolves=0, num_bushes=33),
+    dict(num_ostriches=0, num_wolves=0, num_bushes=0),    # N = 0
+    dict(num_ostriches=9, num_wolves=0, num_bushes=0), dict(num_ostriches=9, num_wolves=8, num_bushes=15),
+    dict(num_ostriches=-1), dict(num_wolves=-1), dict(num_bushes=-1),
+    dict(num_ostriches=-1, num_wolves=9, num_bushes=17),  # a negative count inside an N of 25
+    dict(game_options={"food_per_bush": 256}), dict(game_options={"food_given_per_turn": 256}),
+    dict(game_options={"food_per_bush": -1}), dict(game_options={"food_given_per_turn": -1}),
+    dict(game_options={"lookout_view_radius": (1 << 20) + 1}),
+    dict(game_options={"gatherer_view_radius": (1 << 20) + 1}),
+    dict(game_options={"wolf_view_radius": (1 << 20) + 1}), dict(game_options={"wolf_view_radius": -1}),
+    dict(game_options={"max_turns": -1}),
+]
+
+
+@pytest.mark.parametrize("kw", TORUS_ON_LIMIT, ids=lambda kw: json.dumps(kw, separators=(",", ":")))
+def test_torus_accepts_options_on_the_limit(kw):
+    """A world on a limit constructs and steps once, and the turn equals the oracle's."""
+    import torch
+
+    from oracle.torus_oracle import OracleTorus
+    from wab_gym_amd.torus import BatchedWABEnvironment2
+
+    B = 65  # two workgroups, the second with one world
+    args = dict(world_width=9, world_height=7, game_options=None, num_ostriches=2, num_wolves=3, num_bushes=4)
+    args.update(kw)
+    env = BatchedWABEnvironment2(num_worlds=B, device="cuda:0", **args)
+    orc = OracleTorus(args["world_width"], args["world_height"], args["num_ostriches"], args["num_wolves"],
+                      args["num_bushes"], args["game_options"], batch=B)
+    env.reset_environment()
+    orc.reset()
+    hi = np.array([6] * env.num_ostriches + [5] * env.num_wolves + [1] * env.num_bushes)
+    acts = (np.random.RandomState(1).randint(0, 1 << 20, size=(B, env.N)) % hi).astype(np.int8)
+    obs, rew, done, info = env.step(torch.as_tensor(acts))
+    r_o, rw_o, d_o, wr_o = orc.step(acts)
+    assert np.array_equal(obs.cpu().numpy(), r_o)
+    assert np.array_equal(rew.cpu().numpy(), rw_o)
+    assert np.array_equal(done.cpu().numpy().astype(np.uint8), d_o)
+    assert np.array_equal(info["world_reset"].cpu().numpy().astype(np.uint8), wr_o)
+    s, so = env.state(), orc.state()
+    for key in so:
+        assert np.array_equal(s[key], so[key]), key
+    assert env.counters()["turns"] == B
+
+
+@pytest.mark.parametrize("kw", TORUS_PAST_LIMIT, ids=lambda kw: json.dumps(kw, separators=(",", ":")))
+def test_torus_rejects_options_past_the_limit(kw):
+    """One step outside each limit raises, in the Python surface and (where a config can be
+    built at all) in the C-ABI's own validation."""
+    import ctypes
+
+    from wab_gym_amd import _lib
+    from wab_gym_amd.torus import BatchedWABEnvironment2
+    from wab_gym_amd.torus_options import make_config
+
+    args = dict(world_width=9, world_height=7, game_options=None, num_ostriches=2, num_wolves=3, num_bushes=4)
+    args.update(kw)
+    with pytest.raises(ValueError):
+        BatchedWABEnvironment2(num_worlds=64, device="cuda:0", **args)
+    # the same values written into a valid config: wab2_record_size / wab2_create refuse them
+    cfg, _ = make_config(9, 7, 2, 3, 4, None, True)
+    names = {"world_width": "width", "world_height": "height"}
+    for key, v in list(kw.items()) + list((kw.get("game_options") or {}).items()):
+        if key != "game_options":
+            setattr(cfg, names.get(key, key), v)
+    lib = _lib.load()
+    assert lib.wab2_record_size(ctypes.addressof(cfg)) < 0
+    h = ctypes.c_void_p()
+    assert lib.wab2_create_at(ctypes.addressof(cfg), 64, 1, 0, 0, None, ctypes.byref(h)) != 0
+    assert not h.value
 
 
 def _kat_env(W, H, counts, radius, positions):

@@ -13,6 +13,11 @@ from oracle.torus_oracle import OracleTorus
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SETS = ["torus_c3", "torus_multi", "torus_tiny", "torus_continue", "torus_placed"]
+# worlds at the edges of what include/wab_torus.h accepts (make_golden_torus.py EDGE_SETS): two
+# worlds each, at most 40 turns
+EDGE_SETS = ["torus_edge_largest", "torus_edge_line", "torus_edge_unit", "torus_edge_odd5x3",
+             "torus_edge_odd9x13", "torus_edge_lone_ostrich", "torus_edge_no_ostriches",
+             "torus_edge_no_bushes", "torus_edge_bushes_only", "torus_edge_no_cap", "torus_edge_r128"]
 
 
 def load_set(name):
@@ -37,7 +42,7 @@ def placed_schedule(d, meta, e):
     return d["create_pos"][e], {t: d["reset_pos"][k, e] for k, t in enumerate(turns)}
 
 
-@pytest.mark.parametrize("name", SETS)
+@pytest.mark.parametrize("name", SETS + EDGE_SETS)
 def test_oracle_reproduces_reference(name):
     d, meta = load_set(name)
     T, NO = meta["T"], meta["num_ostriches"]
@@ -94,6 +99,16 @@ def wrapped_rows(d, meta):
     return int(((dl != plain).any(-1) & vis).sum())
 
 
+def visible_rows(d):
+    """(visible [T, E, i, j] bool, deltas [T, E, i, j, 2] int64) of a set's records."""
+    rec = d["records"]
+    N = rec.shape[2]
+    j_idx = np.arange(N, dtype=np.uint32)
+    vis = ((rec[..., 16:20].copy().view(np.uint32)[..., 0][..., None] >> j_idx) & 1).astype(bool)
+    dl = rec[..., 24:24 + 2 * N].view(np.int8).astype(np.int64).reshape(rec.shape[:3] + (N, 2))
+    return vis, dl
+
+
 def early_resets(d, meta):
     """World resets before max_turns turns of an episode: with one ostrich and no ostrich hunger,
     each is a kill (the kill, its loc[j] label quirk and the reset in one turn)."""
@@ -141,6 +156,78 @@ def test_golden_sets_exercise_the_quirks():
     assert seen["stale"] > 100 and seen["x_eq_w"] > 0 and seen["empty_eat"] > 0, seen
     assert seen["wrapped"] > 10000, seen
     assert seen["label_quirk"] > 0, seen
+
+
+def test_edge_sets_hold_what_they_are_for():
+    """The edge fixtures, from their arrays alone: every visible row obeys the wrap rule, and
+    together the sets hold the cases they were generated for.  (Counts found when the sets were
+    generated are in the comments; the floors are well below them.)
+
+    Nothing in Environment 2.0 lowers an ostrich's food, so no ostrich starves (status 1 never
+    occurs): the resets of the max_turns = 0 set are all kill-triggered.  The reference's surface
+    does allow a bushes-only world (create_ostriches(0), create_wolves(0)):
+    torus_edge_bushes_only."""
+    wrapped = {}
+    for name in EDGE_SETS:
+        d, meta = load_set(name)
+        wrapped[name] = wrapped_rows(d, meta)  # asserts the per-row rule
+        assert d["records"].shape[:2] == (meta["T"], 2) and 20 <= meta["T"] <= 40, name
+        assert os.path.getsize(os.path.join(GOLDEN, name + ".npz")) < 150 * 1024, name
+    # rows on an odd side whose delta went through the wrap: 311 in 5x3, 1333 in 9x13, 5150 in
+    # 127x127, 238 on the line (the unit world, the lone ostrich and the bushes have none)
+    assert wrapped["torus_edge_odd5x3"] >= 100 and wrapped["torus_edge_odd9x13"] >= 500, wrapped
+    assert wrapped["torus_edge_largest"] >= 2000 and wrapped["torus_edge_line"] >= 100, wrapped
+    assert wrapped["torus_edge_unit"] == 0, wrapped
+    # a delta of +-63, the longest shorter way round a side of 127: 464 rows in 127x127 (where
+    # the 2^20 radius also leaves plain deltas up to 125), 16 on the line (where none is longer)
+    for name, floor in (("torus_edge_largest", 100), ("torus_edge_line", 5)):
+        d, meta = load_set(name)
+        vis, dl = visible_rows(d)
+        n63 = {s: int(((dl[..., 0] == s) & vis).sum()) for s in (-63, 63)}
+        assert n63[-63] + n63[63] >= floor and min(n63.values()) > 0, (name, n63)
+    d, meta = load_set("torus_edge_line")
+    vis, dl = visible_rows(d)
+    assert np.abs(dl[vis]).max() == 63 and not dl[..., 1].any()
+    # resets in every set (4 to 60 each), and N > 1 sets see others than themselves
+    for name in EDGE_SETS:
+        d, meta = load_set(name)
+        assert d["world_reset"].sum() >= 4, name
+        vis, _ = visible_rows(d)
+        N = vis.shape[2]
+        if N > 1:
+            assert (vis & ~np.eye(N, dtype=bool)).sum() >= 15, name
+    # an eat that takes a bush to 0: one in 127x127 (255 in one eat), 22 and 15 on the odd sides
+    emptied = {}
+    for name in ("torus_edge_largest", "torus_edge_odd5x3", "torus_edge_odd9x13"):
+        d, meta = load_set(name)
+        N, NB, NO = d["records"].shape[2], meta["num_bushes"], meta["num_ostriches"]
+        bf = d["food"][..., N - NB:]
+        before = np.concatenate([np.full_like(bf[:1], meta["options"]["food_per_bush"]), bf[:-1]], 0)
+        emptied[name] = int(((bf == 0) & (before > 0)).sum())
+        if name == "torus_edge_largest":  # 255 taken at once: an ostrich's food rose by 255
+            f = d["food"][..., :NO]
+            assert (np.diff(f, axis=0) == 255).any()
+    assert emptied["torus_edge_largest"] >= 1 and emptied["torus_edge_odd5x3"] >= 10, emptied
+    assert emptied["torus_edge_odd9x13"] >= 5, emptied
+    # the line's bushes hold 0 from the start and are rows of the frame all the same
+    d, meta = load_set("torus_edge_line")
+    assert not d["food"][..., 3:].any() and d["visible"][..., 3:].all()
+    # max_turns = 0: no turn cap, so every reset (9, eight of them in the hunt world) follows a
+    # turn that left both ostriches killed; and a run of more turns than any cap of the other sets
+    d, meta = load_set("torus_edge_no_cap")
+    assert meta["options"]["max_turns"] == 0
+    wr = d["world_reset"]
+    assert wr.sum() >= 5 and wr.any(0).all()
+    gaps = np.diff(np.concatenate([[-1], np.nonzero(wr[:, 0])[0], [meta["T"]]]))
+    assert gaps.max() > 20, gaps  # world 790 runs its last 36 turns without a reset
+    # (the state after a reset turn is the fresh one, so the last kill itself is not in it: the
+    # first kills are, status 2 in 56 ostrich-turns, and the episodes' lengths differ as no cap's would)
+    assert (d["status"] == 2).sum() >= 20
+    assert len(set(np.diff(np.nonzero(wr[:, 1])[0]).tolist())) > 1
+    # the sizes the sets are there for
+    sizes = {name: load_set(name)[1] for name in EDGE_SETS}
+    assert sizes["torus_edge_largest"]["record_size"] == 112 and sizes["torus_edge_r128"]["record_size"] == 128
+    assert sizes["torus_edge_lone_ostrich"]["record_size"] == 32 and sizes["torus_edge_unit"]["record_size"] == 32
 
 
 def test_world_tests_no_wrap_kat():
