@@ -161,3 +161,32 @@ def test_exact_certificate_refuses_an_ordinary_net():
     with pytest.raises(AssertionError):
         pc.exact_certificate(pc.weights("odd"), pc.odd_features(65))
     assert pc._low_bit_exponent(np.array([0.0, 1.0, 0.75, -96.0, 2.0 ** -20])).tolist() == [1 << 20, 0, -2, 5, -20]
+
+
+def test_policy_still_exports_every_name_it_had():
+    """The numeric contracts live in wab_gym_amd/policy_reference.py; policy.py re-exports them by
+    name.  Every public name policy.py had before the split resolves on it, and each moved one is
+    the very object of policy_reference.  Neither module imports torch when it is imported, and
+    either can be the first of the two to be imported."""
+    import subprocess
+    import sys
+
+    from wab_gym_amd import policy_reference
+
+    kept = ["LAYERS", "SITE_POLICY", "ADAM_TENSORS", "shape_of", "check_rows", "check_row_index", "check_loss_args",
+            "check_ppo_args", "check_adam_args", "adam_beta_powers", "adam_state_dict", "parse_adam_state_dict",
+            "DevicePolicy", "DeviceAdam"]
+    moved = ["reference_forward", "reference_loss_and_grad", "reference_ppo_loss_and_grad", "pair_tree_sum",
+             "adam_fresh_state", "reference_adam_step", "keyed_u", "sample_reference"]
+    for name in kept + moved:
+        assert hasattr(policy, name), name
+    for name in moved:
+        assert getattr(policy, name) is getattr(policy_reference, name), name
+        assert getattr(policy, name).__module__ == "wab_gym_amd.policy_reference", name
+    for name in kept[3:]:  # (the functions and classes)
+        assert getattr(policy, name).__module__ == "wab_gym_amd.policy", name
+    assert policy_reference.adam_beta_powers is policy.adam_beta_powers
+    for first, second in (("policy", "policy_reference"), ("policy_reference", "policy")):
+        code = ("import sys; import wab_gym_amd.%s as a; import wab_gym_amd.%s as b; "
+                "assert 'torch' not in sys.modules; assert a.keyed_u is b.keyed_u" % (first, second))
+        subprocess.run([sys.executable, "-c", code], check=True, cwd=policy.__file__.rsplit("/", 2)[0])

@@ -20,7 +20,7 @@ def main(srcs):
                            capture_output=True, text=True)
         cur = None
         for line in r.stderr.splitlines():
-            m = re.search(r"remark:\s+(Function Name|VGPRs|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\S+)", line)
+            m = re.search(r"remark:\s+(Function Name|VGPRs|SGPRs Spill|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]|Occupancy \[waves/SIMD\]): (\S+)", line)
             if not m:
                 continue
             k, v = m.group(1), m.group(2)

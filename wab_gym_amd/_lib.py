@@ -117,7 +117,6 @@ def load():
         raise WabError("%s is a diagnostic build (wab_diagnostic_build); the product library is "
                        "wab_gym_amd/_lib/libwab_hip.so (set WAB_DIAGNOSTIC_OK=1 only in tools/)" % LIB_PATH)
     P, I64, U64, I32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32
-    L.wab_abi_version.restype = ctypes.c_int
     L.wab_last_error.restype = ctypes.c_char_p
     L.wab_num_actions.argtypes = [P]
     L.wab_create.argtypes = [P, I64, U64, I64, ctypes.c_int, ctypes.POINTER(P)]
@@ -182,7 +181,6 @@ def load():
     L.wab_policy_adam_workspace.argtypes = [P]
     L.wab_policy_adam_workspace.restype = ctypes.c_size_t
     L.wab_policy_adam_step.argtypes = [P, P, P, P, P, P, P, P, ctypes.c_size_t, P]
-    L.wab2_abi_version.restype = ctypes.c_int
     L.wab2_last_error.restype = ctypes.c_char_p
     L.wab2_record_size.argtypes = [P]
     L.wab2_create.argtypes = [P, I64, U64, I64, ctypes.c_int, ctypes.POINTER(P)]
@@ -198,10 +196,8 @@ def load():
     L.wab2_get_counters.argtypes = [P, P, P]
     L.wab2_get_obs.argtypes = [P, I32, P, P]
     L.wab2_take_action.argtypes = [P, I32, P, P, P, P, P]
-    for name in EXPORTED:
-        if name not in ("wab_abi_version", "wab_last_error", "wab_batch", "wab_step_kernel", "wab_snapshot_hash",
-                        "wab_episode_stats_workspace", "wab_whiten_workspace", "wab_policy_grad_workspace", "wab_policy_adam_workspace", "wab2_abi_version", "wab2_last_error", "wab2_batch"):
-            getattr(L, name).restype = ctypes.c_int
+    for name in EXPORTED:  # (all there; c_int, ctypes' default, stands where no restype is given above)
+        getattr(L, name)
     if L.wab_abi_version() != ABI_VERSION:
         raise WabError("libwab_hip.so ABI %d != %d" % (L.wab_abi_version(), ABI_VERSION))
     if L.wab2_abi_version() != ABI2_VERSION:

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cstring>
 #include <new>
 
 #include "wab_host.h"
@@ -54,6 +55,31 @@ const void* policy_bwd_kernel(const wab::PolicyDims& d, int mode, bool gather) {
 const void* policy_wgrad_kernel(bool gather) {
   return gather ? reinterpret_cast<const void*>(&wab::wab_policy_wgrad_kernel<true>)
                 : reinterpret_cast<const void*>(&wab::wab_policy_wgrad_kernel<false>);
+}
+
+// wab_policy_weights as the kernels' set of the ten tensors; P = float* for a set a kernel writes
+// (the public struct is const float* throughout: this is the one const_cast)
+template <class P>
+wab::PolicyTensors<P> tensor_set(const wab_policy_weights& w) {
+  const auto c = [](const float* x) { return const_cast<P>(x); };
+  return {c(w.w1), c(w.b1), c(w.w2), c(w.b2), c(w.w3), c(w.b3), c(w.wa), c(w.ba), c(w.wv), c(w.bv)};
+}
+
+// The check of a set: every pointer set, every pointer 4-byte aligned.  `first`: the first fault in
+// the tensors' order (a pointer's NULL before its alignment); `any_null`: a NULL anywhere in the set.
+enum SetFault { SET_OK, SET_NULL, SET_MISALIGNED };
+struct SetCheck {
+  SetFault first;
+  bool any_null;
+};
+SetCheck check_set(const wab_policy_weights& w) {
+  SetCheck r = {SET_OK, false};
+  for (const float* q : {w.w1, w.b1, w.w2, w.b2, w.w3, w.b3, w.wa, w.ba, w.wv, w.bv}) {
+    const SetFault f = !q ? SET_NULL : (reinterpret_cast<uintptr_t>(q) & 3u) != 0 ? SET_MISALIGNED : SET_OK;
+    if (r.first == SET_OK) r.first = f;
+    r.any_null = r.any_null || !q;
+  }
+  return r;
 }
 
 // What a call on a handle and a policy together needs of the pair: always the same device; with
@@ -181,13 +207,11 @@ int wab_policy_destroy(wab_policy* p) {
 int wab_policy_load(wab_policy* p, const wab_policy_weights* wts, void* stream) {
   g_err.clear();
   if (!p || !wts) return fail(WAB_E_INVALID, "wab_policy_load: NULL argument");
-  if (!wts->w1 || !wts->b1 || !wts->w2 || !wts->b2 || !wts->w3 || !wts->b3 || !wts->wa || !wts->ba || !wts->wv ||
-      !wts->bv)
+  if (check_set(*wts).any_null)
     return fail(WAB_E_INVALID, "wab_policy_load: every weight and bias pointer must be set");
   wab::PolicyPackParams pp;
   pp.d = p->dims;
-  pp.w1 = wts->w1; pp.b1 = wts->b1; pp.w2 = wts->w2; pp.b2 = wts->b2; pp.w3 = wts->w3; pp.b3 = wts->b3;
-  pp.wa = wts->wa; pp.ba = wts->ba; pp.wv = wts->wv; pp.bv = wts->bv;
+  pp.src = tensor_set<const float*>(*wts);
   pp.w = p->w;
   pp.b = p->b;
   DeviceGuard guard(p->device);
@@ -297,9 +321,7 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
   }
   int64_t cr = wab::kGradRows;
   if (!eval) {
-    const wab_policy_weights& go = *c.grads_out;
-    if (!go.w1 || !go.b1 || !go.w2 || !go.b2 || !go.w3 || !go.b3 || !go.wa || !go.ba || !go.wv || !go.bv)
-      return fail(WAB_E_INVALID, w + "every gradient pointer must be set");
+    if (check_set(*c.grads_out).any_null) return fail(WAB_E_INVALID, w + "every gradient pointer must be set");
     if (c.loss->value_loss != WAB_VALUE_LOSS_SMOOTH_L1 && c.loss->value_loss != WAB_VALUE_LOSS_MSE)
       return fail(WAB_E_INVALID, w + "value_loss must be WAB_VALUE_LOSS_SMOOTH_L1 or WAB_VALUE_LOSS_MSE");
     cr = grad_chunk_rows(c.loss->chunk_rows);
@@ -323,13 +345,11 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
                                          : "wab_policy_grad_workspace asks for " + std::to_string(need)));
   if ((reinterpret_cast<uintptr_t>(c.workspace) & 255u) != 0)
     return fail(WAB_E_INVALID, w + "the workspace must be 256-byte aligned");
-  const wab_policy_weights none = {};
-  const wab_policy_weights& go = eval ? none : *c.grads_out;
+  bool misaligned = !eval && check_set(*c.grads_out).first == SET_MISALIGNED;  // (no NULL in it by now)
   const void* f32s[] = {c.features, c.weight, c.target, c.old_logp, c.old_value, c.loss_out, c.ppo_out, c.logp,
-                        c.value, c.entropy, c.ratio, go.w1, go.b1, go.w2, go.b2, go.w3, go.b3, go.wa, go.ba,
-                        go.wv, go.bv};
-  for (const void* q : f32s)
-    if ((reinterpret_cast<uintptr_t>(q) & 3u) != 0) return fail(WAB_E_INVALID, w + "float arrays must be 4-byte aligned");
+                        c.value, c.entropy, c.ratio};
+  for (const void* q : f32s) misaligned = misaligned || (reinterpret_cast<uintptr_t>(q) & 3u) != 0;
+  if (misaligned) return fail(WAB_E_INVALID, w + "float arrays must be 4-byte aligned");
   DeviceGuard guard(p->device);
   // wab_policy_bwd_kernel's dynamic LDS can exceed the 64 KB default: as wab_policy_create's
   const void* const bwd = policy_bwd_kernel(p->dims, c.mode, c.gather);
@@ -424,11 +444,7 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
   rp.entropy_coef = c.loss->entropy_coef;
   rp.slab = slab;
   rp.loss = lsum;
-  rp.w1 = const_cast<float*>(go.w1); rp.b1 = const_cast<float*>(go.b1);
-  rp.w2 = const_cast<float*>(go.w2); rp.b2 = const_cast<float*>(go.b2);
-  rp.w3 = const_cast<float*>(go.w3); rp.b3 = const_cast<float*>(go.b3);
-  rp.wa = const_cast<float*>(go.wa); rp.ba = const_cast<float*>(go.ba);
-  rp.wv = const_cast<float*>(go.wv); rp.bv = const_cast<float*>(go.bv);
+  rp.out = tensor_set<float*>(*c.grads_out);
   rp.loss_out = c.loss_out;
   rp.ppo_out = ppo ? c.ppo_out : nullptr;
   const wab::PolicyDims& d = p->dims;
@@ -442,47 +458,45 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
 
 }  // namespace
 
+namespace {
+
+// Starts an entry point's call: clears the error and fills what every GradCall has (all of
+// wab_policy_evaluate's).  A _gather form is its twin's fill, then gather, rows and M.
+GradCall grad_call(const char* name, int mode, const float* features, const int8_t* actions, int64_t N, float* logp,
+                   float* value, float* entropy, void* workspace, size_t workspace_bytes, void* stream) {
+  g_err.clear();
+  GradCall c = {};
+  c.name = name;
+  c.mode = mode;
+  c.features = features; c.actions = actions; c.N = N;
+  c.logp = logp; c.value = value; c.entropy = entropy;
+  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  return c;
+}
+
+// one of the workspace's two counts (GradWorkspace::bad), read once the stream's work is done
+int grad_bad_count(const char* name, const wab_policy* p, const void* workspace, int word, void* stream,
+                   uint64_t* out) {
+  g_err.clear();
+  if (!p || !workspace || !out) return fail(WAB_E_INVALID, std::string(name) + ": NULL argument");
+  DeviceGuard guard(p->device);
+  uint32_t v = 0;
+  HIP_TRY(hipMemcpyAsync(&v, static_cast<const uint32_t*>(workspace) + word, sizeof(v), hipMemcpyDeviceToHost,
+                         (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  *out = v;
+  return WAB_OK;
+}
+
+}  // namespace
+
 int wab_policy_grad(wab_policy* p, const float* features, const int8_t* actions, const float* weight,
                     const float* target, int64_t N, const wab_policy_loss* loss, const wab_policy_weights* grads_out,
                     float loss_out[4], float* logp, float* value, float* entropy, void* workspace,
                     size_t workspace_bytes, void* stream) {
-  g_err.clear();
-  GradCall c = {};
-  c.name = "wab_policy_grad";
-  c.mode = wab::kGradModeGrad;
-  c.features = features; c.actions = actions; c.weight = weight; c.target = target;
-  c.N = N; c.loss = loss; c.grads_out = grads_out; c.loss_out = loss_out;
-  c.logp = logp; c.value = value; c.entropy = entropy;
-  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-  return policy_grad_run(p, c);
-}
-
-int wab_policy_grad_ppo(wab_policy* p, const float* features, const int8_t* actions, const float* advantage,
-                        const float* target, const float* old_logp, const float* old_value, int64_t N,
-                        const wab_policy_loss* loss, const wab_ppo_config* ppo, const wab_policy_weights* grads_out,
-                        float loss_out[4], float ppo_out[4], float* logp, float* value, float* entropy, float* ratio,
-                        void* workspace, size_t workspace_bytes, void* stream) {
-  g_err.clear();
-  GradCall c = {};
-  c.name = "wab_policy_grad_ppo";
-  c.mode = wab::kGradModePpo;
-  c.features = features; c.actions = actions; c.weight = advantage; c.target = target;
-  c.old_logp = old_logp; c.old_value = old_value;
-  c.N = N; c.loss = loss; c.ppo = ppo; c.grads_out = grads_out; c.loss_out = loss_out; c.ppo_out = ppo_out;
-  c.logp = logp; c.value = value; c.entropy = entropy; c.ratio = ratio;
-  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
-  return policy_grad_run(p, c);
-}
-
-int wab_policy_evaluate(wab_policy* p, const float* features, const int8_t* actions, int64_t N, float* logp,
-                        float* value, float* entropy, void* workspace, size_t workspace_bytes, void* stream) {
-  g_err.clear();
-  GradCall c = {};
-  c.name = "wab_policy_evaluate";
-  c.mode = wab::kGradModeEval;
-  c.features = features; c.actions = actions; c.N = N;
-  c.logp = logp; c.value = value; c.entropy = entropy;
-  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  GradCall c = grad_call("wab_policy_grad", wab::kGradModeGrad, features, actions, N, logp, value, entropy, workspace,
+                         workspace_bytes, stream);
+  c.weight = weight; c.target = target; c.loss = loss; c.grads_out = grads_out; c.loss_out = loss_out;
   return policy_grad_run(p, c);
 }
 
@@ -491,15 +505,22 @@ int wab_policy_grad_gather(wab_policy* p, const float* features, const int8_t* a
                            const wab_policy_weights* grads_out, float loss_out[4], float* logp, float* value,
                            float* entropy, void* workspace, size_t workspace_bytes, void* stream, const int32_t* rows,
                            int64_t M) {
-  g_err.clear();
-  GradCall c = {};
-  c.name = "wab_policy_grad_gather";
-  c.mode = wab::kGradModeGrad;
-  c.features = features; c.actions = actions; c.weight = weight; c.target = target;
-  c.N = N; c.gather = true; c.rows = rows; c.M = M;
-  c.loss = loss; c.grads_out = grads_out; c.loss_out = loss_out;
-  c.logp = logp; c.value = value; c.entropy = entropy;
-  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  GradCall c = grad_call("wab_policy_grad_gather", wab::kGradModeGrad, features, actions, N, logp, value, entropy,
+                         workspace, workspace_bytes, stream);
+  c.weight = weight; c.target = target; c.loss = loss; c.grads_out = grads_out; c.loss_out = loss_out;
+  c.gather = true; c.rows = rows; c.M = M;
+  return policy_grad_run(p, c);
+}
+
+int wab_policy_grad_ppo(wab_policy* p, const float* features, const int8_t* actions, const float* advantage,
+                        const float* target, const float* old_logp, const float* old_value, int64_t N,
+                        const wab_policy_loss* loss, const wab_ppo_config* ppo, const wab_policy_weights* grads_out,
+                        float loss_out[4], float ppo_out[4], float* logp, float* value, float* entropy, float* ratio,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  GradCall c = grad_call("wab_policy_grad_ppo", wab::kGradModePpo, features, actions, N, logp, value, entropy,
+                         workspace, workspace_bytes, stream);
+  c.weight = advantage; c.target = target; c.loss = loss; c.grads_out = grads_out; c.loss_out = loss_out;
+  c.old_logp = old_logp; c.old_value = old_value; c.ppo = ppo; c.ppo_out = ppo_out; c.ratio = ratio;
   return policy_grad_run(p, c);
 }
 
@@ -509,59 +530,42 @@ int wab_policy_grad_ppo_gather(wab_policy* p, const float* features, const int8_
                                const wab_policy_weights* grads_out, float loss_out[4], float ppo_out[4], float* logp,
                                float* value, float* entropy, float* ratio, void* workspace, size_t workspace_bytes,
                                void* stream, const int32_t* rows, int64_t M) {
-  g_err.clear();
-  GradCall c = {};
-  c.name = "wab_policy_grad_ppo_gather";
-  c.mode = wab::kGradModePpo;
-  c.features = features; c.actions = actions; c.weight = advantage; c.target = target;
-  c.old_logp = old_logp; c.old_value = old_value;
-  c.N = N; c.gather = true; c.rows = rows; c.M = M;
-  c.loss = loss; c.ppo = ppo; c.grads_out = grads_out; c.loss_out = loss_out; c.ppo_out = ppo_out;
-  c.logp = logp; c.value = value; c.entropy = entropy; c.ratio = ratio;
-  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  GradCall c = grad_call("wab_policy_grad_ppo_gather", wab::kGradModePpo, features, actions, N, logp, value, entropy,
+                         workspace, workspace_bytes, stream);
+  c.weight = advantage; c.target = target; c.loss = loss; c.grads_out = grads_out; c.loss_out = loss_out;
+  c.old_logp = old_logp; c.old_value = old_value; c.ppo = ppo; c.ppo_out = ppo_out; c.ratio = ratio;
+  c.gather = true; c.rows = rows; c.M = M;
   return policy_grad_run(p, c);
+}
+
+int wab_policy_evaluate(wab_policy* p, const float* features, const int8_t* actions, int64_t N, float* logp,
+                        float* value, float* entropy, void* workspace, size_t workspace_bytes, void* stream) {
+  return policy_grad_run(p, grad_call("wab_policy_evaluate", wab::kGradModeEval, features, actions, N, logp, value,
+                                      entropy, workspace, workspace_bytes, stream));
 }
 
 int wab_policy_evaluate_gather(wab_policy* p, const float* features, const int8_t* actions, int64_t N, float* logp,
                                float* value, float* entropy, void* workspace, size_t workspace_bytes, void* stream,
                                const int32_t* rows, int64_t M) {
-  g_err.clear();
-  GradCall c = {};
-  c.name = "wab_policy_evaluate_gather";
-  c.mode = wab::kGradModeEval;
-  c.features = features; c.actions = actions;
-  c.N = N; c.gather = true; c.rows = rows; c.M = M;
-  c.logp = logp; c.value = value; c.entropy = entropy;
-  c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.stream = stream;
+  GradCall c = grad_call("wab_policy_evaluate_gather", wab::kGradModeEval, features, actions, N, logp, value, entropy,
+                         workspace, workspace_bytes, stream);
+  c.gather = true; c.rows = rows; c.M = M;
   return policy_grad_run(p, c);
 }
 
 int wab_policy_grad_bad_rows(const wab_policy* p, const void* workspace, void* stream, uint64_t* out) {
-  g_err.clear();
-  if (!p || !workspace || !out) return fail(WAB_E_INVALID, "wab_policy_grad_bad_rows: NULL argument");
-  DeviceGuard guard(p->device);
-  uint32_t v = 0;
-  HIP_TRY(hipMemcpyAsync(&v, static_cast<const unsigned char*>(workspace) + 4, sizeof(v), hipMemcpyDeviceToHost,
-                         (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  *out = v;
-  if (v != 0)
-    return fail(WAB_E_INVALID, "wab_policy_grad_gather: " + std::to_string(v) +
+  if (int rc = grad_bad_count("wab_policy_grad_bad_rows", p, workspace, 1, stream, out)) return rc;
+  if (*out != 0)
+    return fail(WAB_E_INVALID, "wab_policy_grad_gather: " + std::to_string(*out) +
                                    " rows had an index outside the source's rows; they were left out of the loss "
                                    "and the gradients");
   return WAB_OK;
 }
 
 int wab_policy_grad_bad_actions(const wab_policy* p, const void* workspace, void* stream, uint64_t* out) {
-  g_err.clear();
-  if (!p || !workspace || !out) return fail(WAB_E_INVALID, "wab_policy_grad_bad_actions: NULL argument");
-  DeviceGuard guard(p->device);
-  uint32_t v = 0;
-  HIP_TRY(hipMemcpyAsync(&v, workspace, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-  *out = v;
-  if (v != 0)
-    return fail(WAB_E_INVALID, "wab_policy_grad: " + std::to_string(v) + " rows had an action outside [0, " +
+  if (int rc = grad_bad_count("wab_policy_grad_bad_actions", p, workspace, 0, stream, out)) return rc;
+  if (*out != 0)
+    return fail(WAB_E_INVALID, "wab_policy_grad: " + std::to_string(*out) + " rows had an action outside [0, " +
                                    std::to_string(p->dims.A) + "); they were left out of the loss and the gradients");
   return WAB_OK;
 }
@@ -601,13 +605,10 @@ int wab_policy_adam_step(wab_policy* p, const wab_policy_weights* params, const 
   const wab_policy_weights* const sets[4] = {params, grads, exp_avg, exp_avg_sq};
   const char* const set_names[4] = {"params", "grads", "exp_avg", "exp_avg_sq"};
   for (int s = 0; s < 4; ++s) {
-    const wab_policy_weights& w = *sets[s];
-    const float* const q[wab::kAdamTensors] = {w.w1, w.b1, w.w2, w.b2, w.w3, w.b3, w.wa, w.ba, w.wv, w.bv};
-    for (const float* x : q) {
-      if (!x) return fail(WAB_E_INVALID, std::string("wab_policy_adam_step: every pointer of ") + set_names[s] + " must be set");
-      if ((reinterpret_cast<uintptr_t>(x) & 3u) != 0)
-        return fail(WAB_E_INVALID, "wab_policy_adam_step: float arrays must be 4-byte aligned");
-    }
+    const SetFault f = check_set(*sets[s]).first;
+    if (f == SET_NULL)
+      return fail(WAB_E_INVALID, std::string("wab_policy_adam_step: every pointer of ") + set_names[s] + " must be set");
+    if (f == SET_MISALIGNED) return fail(WAB_E_INVALID, "wab_policy_adam_step: float arrays must be 4-byte aligned");
   }
   // (written so that a NaN is refused too)
   if (!(cfg->lr >= 0.0)) return fail(WAB_E_INVALID, "wab_policy_adam_step: lr must be >= 0");
@@ -646,11 +647,12 @@ int wab_policy_adam_step(wab_policy* p, const wab_policy_weights* params, const 
   DeviceGuard guard(p->device);
   hipStream_t st = (hipStream_t)stream;
   double* const part = static_cast<double*>(workspace);
+  wab::AdamUpdateParams up;
+  up.g = tensor_set<const float*>(*grads);
   wab::AdamNormParams np;
   np.flat = flat;
-  const float* const gs[wab::kAdamTensors] = {grads->w1, grads->b1, grads->w2, grads->b2, grads->w3,
-                                              grads->b3, grads->wa, grads->ba, grads->wv, grads->bv};
-  for (int t = 0; t < wab::kAdamTensors; ++t) np.flat.g[t] = gs[t];
+  static_assert(sizeof(np.flat.g) == sizeof(up.g), "the flat order is the set's field order");
+  std::memcpy(np.flat.g, &up.g, sizeof(up.g));
   np.part = part + lv.offset[0];
   hipLaunchKernelGGL(wab::wab_adam_norm_kernel, dim3(lv.count[0]), dim3(256), 0, st, np);
   HIP_TRY(hipGetLastError());
@@ -664,24 +666,14 @@ int wab_policy_adam_step(wab_policy* p, const wab_policy_weights* params, const 
   }
   const int last = lv.n_levels - 1;
 
-  wab::AdamUpdateParams up;
   up.d = p->dims;
   up.c = c;
   up.part = part + lv.offset[last];
   up.n_part = lv.count[last];
   up.state = reinterpret_cast<const wab::AdamState*>(state);
-  up.gw1 = grads->w1; up.gb1 = grads->b1; up.gw2 = grads->w2; up.gb2 = grads->b2; up.gw3 = grads->w3;
-  up.gb3 = grads->b3; up.gwa = grads->wa; up.gba = grads->ba; up.gwv = grads->wv; up.gbv = grads->bv;
-  const auto rw = [](const float* x) { return const_cast<float*>(x); };
-  up.w1 = rw(params->w1); up.b1 = rw(params->b1); up.w2 = rw(params->w2); up.b2 = rw(params->b2);
-  up.w3 = rw(params->w3); up.b3 = rw(params->b3); up.wa = rw(params->wa); up.ba = rw(params->ba);
-  up.wv = rw(params->wv); up.bv = rw(params->bv);
-  up.m1 = rw(exp_avg->w1); up.mb1 = rw(exp_avg->b1); up.m2 = rw(exp_avg->w2); up.mb2 = rw(exp_avg->b2);
-  up.m3 = rw(exp_avg->w3); up.mb3 = rw(exp_avg->b3); up.ma = rw(exp_avg->wa); up.mba = rw(exp_avg->ba);
-  up.mv = rw(exp_avg->wv); up.mbv = rw(exp_avg->bv);
-  up.v1 = rw(exp_avg_sq->w1); up.vb1 = rw(exp_avg_sq->b1); up.v2 = rw(exp_avg_sq->w2); up.vb2 = rw(exp_avg_sq->b2);
-  up.v3 = rw(exp_avg_sq->w3); up.vb3 = rw(exp_avg_sq->b3); up.va = rw(exp_avg_sq->wa); up.vba = rw(exp_avg_sq->ba);
-  up.vv = rw(exp_avg_sq->wv); up.vbv = rw(exp_avg_sq->bv);
+  up.p = tensor_set<float*>(*params);
+  up.m = tensor_set<float*>(*exp_avg);
+  up.v = tensor_set<float*>(*exp_avg_sq);
   up.w = p->w;
   up.b = p->b;
   // one thread per image element up to 2^16 workgroups (16 M elements), a grid-stride loop beyond

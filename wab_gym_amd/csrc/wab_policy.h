@@ -102,9 +102,16 @@ struct PolicyParams {
   const float* b;            // packed biases (PolicyDims::b*)
 };
 
+// A set of the policy's ten tensors (wab_policy_weights' fields, in its order): torch Linear
+// layout, device.  Kernels name the field they mean; no device code indexes a set.
+template <class P>
+struct PolicyTensors {
+  P w1, b1, w2, b2, w3, b3, wa, ba, wv, bv;
+};
+
 struct PolicyPackParams {
   PolicyDims d;
-  const float *w1, *b1, *w2, *b2, *w3, *b3, *wa, *ba, *wv, *bv;  // torch Linear layout, device
+  PolicyTensors<const float*> src;
   uint16_t* w;
   float* b;
 };

@@ -6,7 +6,7 @@
 // action head and a one-unit value head; F >= 1 inputs, widths h1, h2, h3 in 1..256, A = 2..8
 // actions, all runtime (zero padding to the MFMA tile).
 //
-// Numeric contract (wab_gym_amd/policy.py reference_forward states the same in torch):
+// Numeric contract (wab_gym_amd/policy_reference.py reference_forward states the same in torch):
 //   * every matmul operand is bf16, rounded to nearest even: the input features, the weights
 //     (once, by the pack kernel) and the hidden activations after bias, leaky_relu and clamp;
 //   * products are accumulated in fp32 by v_mfma_f32_32x32x16_bf16 (the order of the sum is the
@@ -50,30 +50,30 @@ __global__ __launch_bounds__(256) void wab_policy_pack(PolicyPackParams p) {
   const PolicyDims& d = p.d;
   const uint32_t stride = gridDim.x * 256u;
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < d.w_total; i += stride) {
-    if (i < d.w2) pack_layer(p.w1, d.h1, d.F, d.KS1, p.w + d.w1, i - d.w1);
-    else if (i < d.w3) pack_layer(p.w2, d.h2, d.h1, d.KS2, p.w + d.w2, i - d.w2);
-    else if (i < d.wh) pack_layer(p.w3, d.h3, d.h2, d.KS3, p.w + d.w3, i - d.w3);
+    if (i < d.w2) pack_layer(p.src.w1, d.h1, d.F, d.KS1, p.w + d.w1, i - d.w1);
+    else if (i < d.w3) pack_layer(p.src.w2, d.h2, d.h1, d.KS2, p.w + d.w2, i - d.w2);
+    else if (i < d.wh) pack_layer(p.src.w3, d.h3, d.h2, d.KS3, p.w + d.w3, i - d.w3);
     else {
       // the head tile: rows 0 .. A-1 of the action head, row 8 the value head
       const uint32_t e = i - d.wh, j = e & 7u, lane = (e >> 3) & 63u, ks = e >> 9;
       const int n = (int)(lane & 31u), k = 16 * (int)ks + 8 * (int)(lane >> 5) + (int)j;
       float v = 0.0f;
       if (k < d.h3) {
-        if (n < d.A) v = p.wa[(size_t)n * (size_t)d.h3 + (size_t)k];
-        else if (n == kPolicyMaxActions) v = p.wv[k];
+        if (n < d.A) v = p.src.wa[(size_t)n * (size_t)d.h3 + (size_t)k];
+        else if (n == kPolicyMaxActions) v = p.src.wv[k];
       }
       p.w[i] = (uint16_t)pol_bf16(v);
     }
   }
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < d.b_total; i += stride) {
     float v = 0.0f;
-    if (i < d.b2) { if ((int)(i - d.b1) < d.h1) v = p.b1[i - d.b1]; }
-    else if (i < d.b3) { if ((int)(i - d.b2) < d.h2) v = p.b2[i - d.b2]; }
-    else if (i < d.bh) { if ((int)(i - d.b3) < d.h3) v = p.b3[i - d.b3]; }
+    if (i < d.b2) { if ((int)(i - d.b1) < d.h1) v = p.src.b1[i - d.b1]; }
+    else if (i < d.b3) { if ((int)(i - d.b2) < d.h2) v = p.src.b2[i - d.b2]; }
+    else if (i < d.bh) { if ((int)(i - d.b3) < d.h3) v = p.src.b3[i - d.b3]; }
     else {
       const int n = (int)(i - d.bh);
-      if (n < d.A) v = p.ba[n];
-      else if (n == kPolicyMaxActions) v = p.bv[0];
+      if (n < d.A) v = p.src.ba[n];
+      else if (n == kPolicyMaxActions) v = p.src.bv[0];
     }
     p.b[i] = v;
   }

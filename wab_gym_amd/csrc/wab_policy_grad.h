@@ -180,7 +180,7 @@ struct GradReduceParams {
   float scale, value_coef, entropy_coef;
   const float* slab;
   const double* loss;
-  float *w1, *b1, *w2, *b2, *w3, *b3, *wa, *ba, *wv, *bv;  // torch Linear layout, device
+  PolicyTensors<float*> out;  // the ten gradients
   float* loss_out;         // {policy, value, entropy, total}
   float* ppo_out;          // {clipped rows, sum of k3, value-clipped rows, sum of r} or null
 };

@@ -2,7 +2,7 @@
 // for the device policy: the loss terms and the gradients of the ten parameter tensors over N
 // stored rows (features, action, weight, value target).  gfx950.
 //
-// Numeric contract (wab_gym_amd/policy.py reference_loss_and_grad states the same in torch):
+// Numeric contract (wab_gym_amd/policy_reference.py reference_loss_and_grad states the same in torch):
 //   * forward: wab_policy_act's, through the same pol_* functions (wab_policy_dev.h): the layer-1
 //     chunk loop, the tile passes, pol_store (the epilogue below is a hook on it) and pol_softmax,
 //     so x_l, the value and the probabilities have wab_policy_act's bits;
@@ -559,11 +559,11 @@ __global__ __launch_bounds__(256) void wab_policy_grad_reduce_kernel(GradReduceP
       for (int s = 0; s < g.slabs; ++s) v = v + p.slab[(size_t)s * slab_stride + idx];
     v = v * p.scale;
     float* dst;
-    if (layer == 1) dst = k < K ? p.w1 + (size_t)n * (size_t)K + k : p.b1 + n;
-    else if (layer == 2) dst = k < K ? p.w2 + (size_t)n * (size_t)K + k : p.b2 + n;
-    else if (layer == 3) dst = k < K ? p.w3 + (size_t)n * (size_t)K + k : p.b3 + n;
-    else if (n < d.A) dst = k < K ? p.wa + (size_t)n * (size_t)K + k : p.ba + n;
-    else dst = k < K ? p.wv + k : p.bv;
+    if (layer == 1) dst = k < K ? p.out.w1 + (size_t)n * (size_t)K + k : p.out.b1 + n;
+    else if (layer == 2) dst = k < K ? p.out.w2 + (size_t)n * (size_t)K + k : p.out.b2 + n;
+    else if (layer == 3) dst = k < K ? p.out.w3 + (size_t)n * (size_t)K + k : p.out.b3 + n;
+    else if (n < d.A) dst = k < K ? p.out.wa + (size_t)n * (size_t)K + k : p.out.ba + n;
+    else dst = k < K ? p.out.wv + k : p.out.bv;
     *dst = p.accumulate ? *dst + v : v;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0 && p.loss_out) {

@@ -84,10 +84,8 @@ struct AdamUpdateParams {
   const double* part;  // the last level
   uint32_t n_part;     // <= 1024
   const AdamState* state;
-  const float *gw1, *gb1, *gw2, *gb2, *gw3, *gb3, *gwa, *gba, *gwv, *gbv;
-  float *w1, *b1, *w2, *b2, *w3, *b3, *wa, *ba, *wv, *bv;            // parameters
-  float *m1, *mb1, *m2, *mb2, *m3, *mb3, *ma, *mba, *mv, *mbv;        // exp_avg
-  float *v1, *vb1, *v2, *vb2, *v3, *vb3, *va, *vba, *vv, *vbv;        // exp_avg_sq
+  PolicyTensors<const float*> g;  // gradients
+  PolicyTensors<float*> p, m, v;  // parameters, exp_avg, exp_avg_sq
   uint16_t* w;  // the policy's packed bf16 image
   float* b;     // its padded biases
 };

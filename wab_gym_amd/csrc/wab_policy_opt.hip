@@ -3,8 +3,8 @@
 // parameter, both moments and the packed bf16 image wab_policy_act reads (wab_policy_adam_step).
 // gfx950.
 //
-// Numeric contract (include/wab.h states it in full; wab_gym_amd/policy.py reference_adam_step is
-// the same in numpy; the library is built with -ffp-contract=off):
+// Numeric contract (include/wab.h states it in full; reference_adam_step of
+// wab_gym_amd/policy_reference.py is the same in numpy; the library is built with -ffp-contract=off):
 //   * S = the adjacent-pair tree sum of (double)g_i * (double)g_i over the flat order, zero-padded
 //     to a power of two; norm = sqrt(S); a non-finite S skips the step;
 //   * c = (float)min(1, max_grad_norm / (norm + 1e-6)) or 1; bias corrections from the running
@@ -173,27 +173,27 @@ __global__ __launch_bounds__(256) void wab_adam_update_kernel(AdamUpdateParams p
   const PolicyDims& d = p.d;
   const uint32_t stride = gridDim.x * 256u;
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < d.w_total; i += stride) {
-    if (i < d.w2) adam_layer(s, p.gw1, p.w1, p.m1, p.v1, d.h1, d.F, d.KS1, p.w + d.w1, i - d.w1);
-    else if (i < d.w3) adam_layer(s, p.gw2, p.w2, p.m2, p.v2, d.h2, d.h1, d.KS2, p.w + d.w2, i - d.w2);
-    else if (i < d.wh) adam_layer(s, p.gw3, p.w3, p.m3, p.v3, d.h3, d.h2, d.KS3, p.w + d.w3, i - d.w3);
+    if (i < d.w2) adam_layer(s, p.g.w1, p.p.w1, p.m.w1, p.v.w1, d.h1, d.F, d.KS1, p.w + d.w1, i - d.w1);
+    else if (i < d.w3) adam_layer(s, p.g.w2, p.p.w2, p.m.w2, p.v.w2, d.h2, d.h1, d.KS2, p.w + d.w2, i - d.w2);
+    else if (i < d.wh) adam_layer(s, p.g.w3, p.p.w3, p.m.w3, p.v.w3, d.h3, d.h2, d.KS3, p.w + d.w3, i - d.w3);
     else {
       // the head tile: rows 0 .. A-1 of the action head, row 8 the value head
       const uint32_t e = i - d.wh, j = e & 7u, lane = (e >> 3) & 63u, ks = e >> 9;
       const int n = (int)(lane & 31u), k = 16 * (int)ks + 8 * (int)(lane >> 5) + (int)j;
       if (k < d.h3) {
-        if (n < d.A) p.w[i] = (uint16_t)pol_bf16(adam_element(s, p.gwa, p.wa, p.ma, p.va, (size_t)n * (size_t)d.h3 + (size_t)k));
-        else if (n == kPolicyMaxActions) p.w[i] = (uint16_t)pol_bf16(adam_element(s, p.gwv, p.wv, p.mv, p.vv, (size_t)k));
+        if (n < d.A) p.w[i] = (uint16_t)pol_bf16(adam_element(s, p.g.wa, p.p.wa, p.m.wa, p.v.wa, (size_t)n * (size_t)d.h3 + (size_t)k));
+        else if (n == kPolicyMaxActions) p.w[i] = (uint16_t)pol_bf16(adam_element(s, p.g.wv, p.p.wv, p.m.wv, p.v.wv, (size_t)k));
       }
     }
   }
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < d.b_total; i += stride) {
-    if (i < d.b2) { if ((int)(i - d.b1) < d.h1) p.b[i] = adam_element(s, p.gb1, p.b1, p.mb1, p.vb1, i - d.b1); }
-    else if (i < d.b3) { if ((int)(i - d.b2) < d.h2) p.b[i] = adam_element(s, p.gb2, p.b2, p.mb2, p.vb2, i - d.b2); }
-    else if (i < d.bh) { if ((int)(i - d.b3) < d.h3) p.b[i] = adam_element(s, p.gb3, p.b3, p.mb3, p.vb3, i - d.b3); }
+    if (i < d.b2) { if ((int)(i - d.b1) < d.h1) p.b[i] = adam_element(s, p.g.b1, p.p.b1, p.m.b1, p.v.b1, i - d.b1); }
+    else if (i < d.b3) { if ((int)(i - d.b2) < d.h2) p.b[i] = adam_element(s, p.g.b2, p.p.b2, p.m.b2, p.v.b2, i - d.b2); }
+    else if (i < d.bh) { if ((int)(i - d.b3) < d.h3) p.b[i] = adam_element(s, p.g.b3, p.p.b3, p.m.b3, p.v.b3, i - d.b3); }
     else {
       const int n = (int)(i - d.bh);
-      if (n < d.A) p.b[i] = adam_element(s, p.gba, p.ba, p.mba, p.vba, (size_t)n);
-      else if (n == kPolicyMaxActions) p.b[i] = adam_element(s, p.gbv, p.bv, p.mbv, p.vbv, 0);
+      if (n < d.A) p.b[i] = adam_element(s, p.g.ba, p.p.ba, p.m.ba, p.v.ba, (size_t)n);
+      else if (n == kPolicyMaxActions) p.b[i] = adam_element(s, p.g.bv, p.p.bv, p.m.bv, p.v.bv, 0);
     }
   }
 }

@@ -20,7 +20,8 @@ optimizer and reloads.
 
 What the kernels compute is `reference_forward`, `reference_loss_and_grad` (the numeric
 contracts, in torch on the CPU), `reference_adam_step` (in numpy) and `sample_reference` (the
-sampling rule, in numpy) below; the tests check the kernels against them.
+sampling rule, in numpy) of policy_reference.py, re-exported here; the tests check the kernels
+against them.
 The reference's `+ U(0, 1) / 100` input noise (actor_critic.py:189) is not reproduced.
 """
 from __future__ import annotations
@@ -32,6 +33,8 @@ import numpy as np
 from . import _lib
 
 LAYERS = ("affine1", "affine2", "affine3", "action_head", "value_head")
+# the ten tensors by name, in wab_policy_weights' order (the flat order of the optimizer's norm)
+ADAM_TENSORS = tuple("%s.%s" % (n, part) for n in LAYERS for part in ("weight", "bias"))
 SITE_POLICY = 11  # keyed-RNG site of the action draw (the first id free in oracle/keyed_rng.py)
 
 
@@ -40,13 +43,11 @@ def _state_dict(module_or_state_dict):
     if hasattr(sd, "state_dict"):
         sd = sd.state_dict()
     out = {}
-    for name in LAYERS:
-        for part in ("weight", "bias"):
-            key = "%s.%s" % (name, part)
-            if key not in sd:
-                raise ValueError("the policy needs %s (the five Linears of actor_critic.Policy: %s)"
-                                 % (key, ", ".join(LAYERS)))
-            out[key] = sd[key]
+    for key in ADAM_TENSORS:
+        if key not in sd:
+            raise ValueError("the policy needs %s (the five Linears of actor_critic.Policy: %s)"
+                             % (key, ", ".join(LAYERS)))
+        out[key] = sd[key]
     return out
 
 
@@ -66,230 +67,6 @@ def shape_of(state_dict):
         if tuple(sd[name + ".bias"].shape) != (n,):
             raise ValueError("%s.bias has shape %s, expected (%d,)" % (name, tuple(sd[name + ".bias"].shape), n))
     return int(F), int(h1), int(h2), int(h3), int(A)
-
-
-def reference_forward(state_dict, features, hidden=None):
-    """The kernel's numeric contract in torch on the CPU: every matmul operand (features, weights,
-    hidden activations after bias, leaky_relu and clamp) rounded to bf16 (nearest even), everything
-    else in float64 (the kernel: fp32 MFMA accumulation, fp32 bias / leaky_relu(0.01) / clamp(-4, 4)
-    / max-subtracted softmax / value).  Returns (probs [B, A], value [B]) as float64 tensors.
-    `hidden`, a list, receives each hidden layer's (pre-activation, bf16 output) pair."""
-    import torch
-
-    sd = {k: v.detach().to("cpu", torch.float32) for k, v in _state_dict(state_dict).items()}
-
-    def bf(x):  # round to bf16, carried on in float64
-        return x.to(torch.float32).to(torch.bfloat16).to(torch.float64)
-
-    def linear(x, name):
-        return x @ bf(sd[name + ".weight"]).T + sd[name + ".bias"].to(torch.float64)
-
-    x = bf(torch.as_tensor(features).detach().to("cpu", torch.float32))
-    for i, name in enumerate(LAYERS[:3]):
-        z = linear(x, name)
-        x = torch.where(z >= 0, z, z * float(np.float32(0.01)))
-        if i == 2:
-            x = x.clamp(-4.0, 4.0)
-        x = bf(x)
-        if hidden is not None:
-            hidden.append((z, x))
-    logits = linear(x, "action_head")
-    e = torch.exp(logits - logits.max(dim=-1, keepdim=True).values)
-    return e / e.sum(dim=-1, keepdim=True), linear(x, "value_head")[:, 0]
-
-
-def _value_loss(d, value_loss):
-    """(l(d), l'(d)) of the configured value loss, float64 tensors."""
-    import torch
-
-    if value_loss == "mse":
-        return 0.5 * d * d, d
-    return (torch.where(d.abs() < 1.0, 0.5 * d * d, d.abs() - 0.5), torch.where(d.abs() < 1.0, d, torch.sign(d)))
-
-
-def _reference_head_and_backward(state_dict, features, actions, head, entropy_coef, scale, round_grads):
-    """What reference_loss_and_grad and reference_ppo_loss_and_grad share: the forward, p, log p,
-    H, then head(logp, v, ok) -> (w rows, g_v rows, loss_policy, loss_value, extras), then G_4 and
-    the straight-through backward.  ok: the rows whose action is inside [0, A); the others are left
-    out of every sum and gradient and have logp 0 (the kernels' bad-action rule).  Returns (loss
-    parts, logp, v, H, grads, extras)."""
-    import torch
-
-    sd = {k: v.detach().to("cpu", torch.float32) for k, v in _state_dict(state_dict).items()}
-
-    def bf(x):
-        return x.to(torch.float32).to(torch.bfloat16).to(torch.float64)
-
-    def rd(g):
-        return bf(g) if round_grads else g
-
-    x0 = bf(torch.as_tensor(features).detach().to("cpu", torch.float32))
-    a = torch.as_tensor(actions).detach().to("cpu", torch.int64)
-    hidden = []
-    _, v = reference_forward(sd, features, hidden=hidden)
-    xs = [x0] + [h[1] for h in hidden]
-    wq = {n: bf(sd[n + ".weight"]) for n in LAYERS}
-    logits = xs[3] @ wq["action_head"].T + sd["action_head.bias"].to(torch.float64)
-    zc = logits - logits.max(dim=-1, keepdim=True).values
-    logp_all = zc - torch.log(torch.exp(zc).sum(dim=-1, keepdim=True))
-    p = torch.exp(logp_all)
-    H = -(p * logp_all).sum(dim=-1)
-    ok = (a >= 0) & (a < p.shape[1])
-    onehot = torch.zeros_like(p)
-    onehot[torch.arange(len(a)), torch.where(ok, a, torch.zeros_like(a))] = 1.0
-    zero = torch.zeros_like(H)
-    logp = torch.where(ok, (logp_all * onehot).sum(dim=-1), zero)
-    w, gv, loss_policy, loss_value, extras = head(logp, v, ok)
-    loss_entropy = torch.where(ok, H, zero).sum()
-
-    Da = rd(w[:, None] * (p - onehot) + entropy_coef * p * (logp_all + H[:, None]))
-    Da = torch.where(ok[:, None], Da, torch.zeros_like(Da))
-    Dv = rd(torch.where(ok, gv, zero))[:, None]
-    grads = {"action_head.weight": Da.T @ xs[3], "action_head.bias": Da.sum(dim=0),
-             "value_head.weight": Dv.T @ xs[3], "value_head.bias": Dv.sum(dim=0)}
-    dx = Da @ wq["action_head"] + Dv @ wq["value_head"]
-    slope = float(np.float32(0.01))
-    for i in (2, 1, 0):
-        z = hidden[i][0]
-        G = dx * torch.where(z >= 0, 1.0, slope)
-        if i == 2:
-            y = torch.where(z >= 0, z, z * slope)
-            G = G * ((y >= -4.0) & (y <= 4.0)).to(torch.float64)
-        D = rd(G)
-        grads[LAYERS[i] + ".weight"] = D.T @ xs[i]
-        grads[LAYERS[i] + ".bias"] = D.sum(dim=0)
-        dx = D @ wq[LAYERS[i]]
-    grads = {k: g * scale for k, g in grads.items()}
-    return (loss_policy, loss_value, loss_entropy), logp, v, H, grads, extras
-
-
-def _reference_gather(features, rows, actions, **per_row):
-    """The host side of `rows=`: (features, actions, per-row arrays) of call rows 0 .. N - 1, row i
-    from source row rows[i] of features [M, F] or [T, B, F] (M = T B).  An index outside [0, M) is
-    clamped into it and its row given action -1: the bad-row rule is the bad-action rule."""
-    import torch
-
-    r = torch.as_tensor(rows).detach().to("cpu", torch.int64).reshape(-1)
-    x = torch.as_tensor(features).detach().to("cpu")
-    x = x.reshape(-1, x.shape[-1])
-    M = x.shape[0]
-    if M < 1:
-        raise ValueError("rows= needs a source of at least one row")
-    bad = (r < 0) | (r >= M)
-    rc = r.clamp(0, M - 1)
-    a = torch.as_tensor(actions).detach().to("cpu", torch.int64).reshape(-1)[rc]
-    a = torch.where(bad, torch.full_like(a, -1), a)
-    out = {k: None if v is None else torch.as_tensor(v).detach().to("cpu").reshape(-1)[rc] for k, v in per_row.items()}
-    return x[rc], a, out
-
-
-def reference_loss_and_grad(state_dict, features, actions, weight, target, value_coef=1.0, entropy_coef=0.0,
-                            value_loss="smooth_l1", scale=1.0, round_grads=True, rows=None):
-    """wab_policy_grad's numeric contract in torch on the CPU, float64, written out by hand (no
-    autograd).  The forward is reference_forward.  Per row, p = softmax(logits), H = -sum p log p:
-
-        loss_policy = -sum_i weight_i log p_i[a_i];  loss_value = sum_i l(v_i - target_i), l
-        smooth_l1 (beta 1) or "mse" = d^2 / 2;  loss_entropy = sum_i H_i;
-        total = scale (loss_policy + value_coef loss_value - entropy_coef loss_entropy)
-
-    and the gradients of `total`, straight-through: every bf16 rounding has derivative 1.  With
-    G_4 = [weight (p - onehot) + entropy_coef p (log p + H) | value_coef l'] and D_l = bf16(G_l)
-    (G_l itself without round_grads): dW_l = D_l^T x_{l-1}, db_l = sum_i D_l[i], dx_{l-1} = D_l
-    bf16(W_l), G_{l-1} = dx_{l-1} * (z >= 0 ? 1 : float32(0.01)) * (layer 3: -4 <= leaky_relu(z) <= 4).
-    Returns {"loss": (policy, value, entropy, total), "logp", "value", "entropy": [N] rows,
-    "grads": the ten tensors in torch Linear layout}, all float64.
-    A row whose action is outside [0, A) takes no part in any sum or gradient and has logp 0.
-    rows (int [N]): the call's row i is source row rows[i] of features and of every per-row array
-    (wab_policy_grad_gather); an index outside the source is clamped into it and its row treated
-    as a bad-action row."""
-    import torch
-
-    if value_loss not in ("smooth_l1", "mse"):
-        raise ValueError("value_loss must be 'smooth_l1' or 'mse'")
-    if rows is not None:
-        features, actions, g = _reference_gather(features, rows, actions, weight=weight, target=target)
-        weight, target = g["weight"], g["target"]
-    w = torch.as_tensor(weight).detach().to("cpu", torch.float64)
-    tg = torch.as_tensor(target).detach().to("cpu", torch.float64)
-
-    def head(logp, v, ok):
-        lv, dv = _value_loss(v - tg, value_loss)
-        zero = torch.zeros_like(v)
-        return w, value_coef * dv, torch.where(ok, -(w * logp), zero).sum(), torch.where(ok, lv, zero).sum(), None
-
-    (lp, lvs, le), logp, v, H, grads, _ = _reference_head_and_backward(state_dict, features, actions, head,
-                                                                       entropy_coef, scale, round_grads)
-    total = scale * (lp + value_coef * lvs - entropy_coef * le)
-    return {"loss": (lp, lvs, le, total), "logp": logp, "value": v, "entropy": H, "grads": grads}
-
-
-def reference_ppo_loss_and_grad(state_dict, features, actions, advantage, target, old_logp, clip=0.2, old_value=None,
-                                value_clip=None, value_coef=1.0, entropy_coef=0.0, value_loss="smooth_l1", scale=1.0,
-                                round_grads=True, rows=None):
-    """wab_policy_grad_ppo's numeric contract (include/wab.h) in torch on the CPU, float64, by
-    hand: reference_loss_and_grad with the clipped surrogate's effective weight and the clipped
-    value loss.  Per row, A the advantage, lo = float32(1) - float32(clip), hi = float32(1) +
-    float32(clip) (the two float32 values the kernel forms):
-
-        d = clamp(logp - old_logp, -30, 30);  r = exp(d)
-        clipped = (A > 0 and r > hi) or (A < 0 and r < lo)
-        loss_policy_i = -(A (hi if A > 0 else lo)) if clipped else -(r A);  w_eff = 0 if clipped else r A
-        u = v - old_value;  |u| <= value_clip: the plain value loss and gradient;  otherwise
-        vc = old_value + sign(u) value_clip, loss_value_i = max(l(v - t), l(vc - t)), and g_v = 0
-        where l(vc - t) > l(v - t) (value_clipped)
-
-    value_clip None or <= 0: no value clipping.  Returns reference_loss_and_grad's dict plus
-    "ratio", "clipped", "value_clipped" rows and "ppo" = (clipped rows, sum of k3 = expm1(d) - d,
-    value-clipped rows, sum of r).  Bad-action rows and `rows` as reference_loss_and_grad's (a row
-    left out has ratio 0 and counts in none of the four)."""
-    import torch
-
-    if value_loss not in ("smooth_l1", "mse"):
-        raise ValueError("value_loss must be 'smooth_l1' or 'mse'")
-    if rows is not None:
-        features, actions, g = _reference_gather(features, rows, actions, advantage=advantage, target=target,
-                                                 old_logp=old_logp, old_value=old_value)
-        advantage, target, old_logp, old_value = g["advantage"], g["target"], g["old_logp"], g["old_value"]
-    A = torch.as_tensor(advantage).detach().to("cpu", torch.float64)
-    tg = torch.as_tensor(target).detach().to("cpu", torch.float64)
-    olp = torch.as_tensor(old_logp).detach().to("cpu", torch.float64)
-    one, cl = np.float32(1.0), np.float32(clip)
-    lo, hi = float(one - cl), float(one + cl)
-    vclip_on = value_clip is not None and float(value_clip) > 0
-    if vclip_on and old_value is None:
-        raise ValueError("value_clip > 0 needs old_value")
-    c = float(np.float32(value_clip)) if vclip_on else 0.0
-
-    def head(logp, v, ok):
-        zero = torch.zeros_like(v)
-        d = (logp - olp).clamp(-30.0, 30.0)
-        r = torch.where(ok, torch.exp(d), zero)
-        clipped = ok & (((A > 0) & (r > hi)) | ((A < 0) & (r < lo)))
-        bound = torch.where(A > 0, hi, lo)
-        lpol = torch.where(clipped, -(A * bound), -(r * A))
-        w_eff = torch.where(clipped, torch.zeros_like(A), r * A)
-        l1, dv = _value_loss(v - tg, value_loss)
-        lv, vcl = l1, torch.zeros_like(clipped)
-        if vclip_on:
-            ov = torch.as_tensor(old_value).detach().to("cpu", torch.float64)
-            u = v - ov
-            vc = ov + torch.where(u > 0, c, -c)
-            l2, _ = _value_loss(vc - tg, value_loss)
-            outside = ~(u.abs() <= c)
-            vcl = ok & outside & (l2 > l1)
-            lv = torch.where(vcl, l2, l1)
-        gv = torch.where(vcl, torch.zeros_like(dv), value_coef * dv)
-        ppo = (clipped.to(torch.float64).sum(), torch.where(ok, torch.expm1(d) - d, zero).sum(),
-               vcl.to(torch.float64).sum(), r.sum())
-        return (w_eff, gv, torch.where(ok, lpol, zero).sum(), torch.where(ok, lv, zero).sum(),
-                {"ratio": r, "clipped": clipped, "value_clipped": vcl, "ppo": ppo})
-
-    (lp, lvs, le), logp, v, H, grads, extra = _reference_head_and_backward(state_dict, features, actions, head,
-                                                                           entropy_coef, scale, round_grads)
-    total = scale * (lp + value_coef * lvs - entropy_coef * le)
-    out = {"loss": (lp, lvs, le, total), "logp": logp, "value": v, "entropy": H, "grads": grads}
-    out.update(extra)
-    return out
 
 
 def check_rows(shape, features, **rows):
@@ -369,25 +146,6 @@ def check_ppo_args(shape, features, actions, advantage, target, old_logp, clip=0
     return n
 
 
-ADAM_TENSORS = tuple("%s.%s" % (n, part) for n in LAYERS for part in ("weight", "bias"))  # the flat order
-
-
-def pair_tree_sum(q):
-    """The adjacent-pair tree sum of a 1-D float64 array, zero-padded to the next power of two:
-    x = x[0::2] + x[1::2] until one value is left (the order wab_policy_adam_step's norm is
-    summed in)."""
-    q = np.asarray(q, np.float64).ravel()
-    n = 1
-    while n < q.size:
-        n *= 2
-    x = np.zeros(n, np.float64)
-    x[:q.size] = q
-    with np.errstate(all="ignore"):
-        while x.size > 1:
-            x = x[0::2] + x[1::2]
-    return x[0]
-
-
 def check_adam_args(lr, betas, eps, weight_decay, max_grad_norm):
     """The argument checks of wab_policy_adam_step, on the host (ValueError)."""
     if not float(lr) >= 0.0:
@@ -412,66 +170,6 @@ def adam_beta_powers(step, betas):
             p = (1.0 if i == 0 else p) * float(b)
         out.append(p)
     return tuple(out)
-
-
-def adam_fresh_state():
-    """wab_adam_state of a fresh optimizer (all-zero bytes), as a dict."""
-    return {"step": 0, "skipped": 0, "beta1_pow": 0.0, "beta2_pow": 0.0, "grad_norm": np.float32(0.0),
-            "clip_scale": np.float32(0.0)}
-
-
-def reference_adam_step(params, grads, exp_avg, exp_avg_sq, state, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                        weight_decay=0.0, decoupled=False, max_grad_norm=0.0):
-    """wab_policy_adam_step's numeric contract (include/wab.h) in numpy: float32 arrays and
-    scalars, float64 where the contract says so, the norm's sum by pair_tree_sum.  params, grads,
-    exp_avg, exp_avg_sq: the ten arrays each in ADAM_TENSORS order; state: a dict as
-    adam_fresh_state().  Nothing is modified; returns (params, exp_avg, exp_avg_sq, state), new."""
-    check_adam_args(lr, betas, eps, weight_decay, max_grad_norm)
-    f32 = np.float32
-
-    def arrays(xs, what):
-        xs = [np.array(x.detach().cpu().numpy() if hasattr(x, "detach") else x, copy=True) for x in xs]
-        if len(xs) != len(ADAM_TENSORS) or any(x.dtype != np.float32 for x in xs):
-            raise ValueError("%s must be ten float32 arrays" % what)
-        return xs
-
-    p, g, m, v = (arrays(x, n) for x, n in ((params, "params"), (grads, "grads"), (exp_avg, "exp_avg"),
-                                            (exp_avg_sq, "exp_avg_sq")))
-    st = dict(state)
-    with np.errstate(all="ignore"):
-        flat = np.concatenate([x.ravel() for x in g]).astype(np.float64)
-        S = pair_tree_sum(flat * flat)
-        norm = np.sqrt(np.float64(S))
-        st["grad_norm"] = f32(norm)
-        c = f32(1.0)
-        if max_grad_norm > 0:
-            r = np.float64(max_grad_norm) / (norm + np.float64(1e-6))
-            c = f32(r if r < 1.0 else 1.0)
-        st["clip_scale"] = c
-        if not np.isfinite(S):
-            st["skipped"] = int(st["skipped"]) + 1
-            return p, m, v, st
-        beta1, beta2 = float(betas[0]), float(betas[1])
-        b1p = (1.0 if st["step"] == 0 else float(st["beta1_pow"])) * beta1
-        b2p = (1.0 if st["step"] == 0 else float(st["beta2_pow"])) * beta2
-        a = f32(float(lr) / (1.0 - b1p))
-        r2 = np.sqrt(f32(1.0 - b2p))
-        b1f, omb1, b2f, omb2 = f32(beta1), f32(1.0 - beta1), f32(beta2), f32(1.0 - beta2)
-        epsf, wdf, decayf = f32(eps), f32(weight_decay), f32(1.0 - float(lr) * float(weight_decay))
-        st["step"] = int(st["step"]) + 1
-        st["beta1_pow"], st["beta2_pow"] = b1p, b2p
-        for i in range(len(p)):
-            gi = g[i] * c
-            if weight_decay != 0 and not decoupled:
-                gi = gi + wdf * p[i]
-            if weight_decay != 0 and decoupled:
-                p[i] = p[i] * decayf
-            m[i] = b1f * m[i] + omb1 * gi
-            v[i] = b2f * v[i] + (omb2 * gi) * gi
-            den = np.sqrt(v[i]) / r2 + epsf
-            p[i] = p[i] - a * (m[i] / den)
-            assert p[i].dtype == np.float32 and m[i].dtype == np.float32 and v[i].dtype == np.float32
-    return p, m, v, st
 
 
 def adam_state_dict(step, exp_avg, exp_avg_sq, order, lr, betas, eps, weight_decay, decoupled, max_grad_norm):
@@ -539,49 +237,6 @@ def parse_adam_state_dict(sd, order, shapes):
     return int(step), m, v, hyper
 
 
-def keyed_u(seed, env_ids, episode, turn):
-    """The 53-bit keyed uniform of the action draw: (seed, global env id, episode, site 11, turn,
-    tile (0, 0), k = 0) under the definition of oracle/keyed_rng.py, restated here so that the
-    product does not import test infrastructure."""
-    M64 = (1 << 64) - 1
-
-    def mix64(z):
-        z &= M64
-        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-        return z ^ (z >> 31)
-
-    def fmix32(h):
-        h ^= h >> 16
-        h = (h * 0x85EBCA6B) & 0xFFFFFFFF
-        h ^= h >> 13
-        h = (h * 0xC2B2AE35) & 0xFFFFFFFF
-        return h ^ (h >> 16)
-
-    a = mix64((int(seed) + 0x9E3779B97F4A7C15) & M64)
-    out = np.zeros(len(env_ids), np.float64)
-    for i, (env, ep, t) in enumerate(zip(env_ids, episode, turn)):
-        ek = mix64(mix64(a ^ (int(env) & M64)) ^ (int(ep) & M64))
-        b0, b1 = ek & 0xFFFFFFFF, ek >> 32
-        ts = SITE_POLICY | ((int(t) & 0xFFFFF) << 12)
-        h1 = fmix32(b0)  # tile (0, 0)
-        hi = fmix32(h1 ^ ts ^ b1)
-        lo = fmix32(h1 ^ (((ts << 16) | (ts >> 16)) & 0xFFFFFFFF) ^ b0 ^ 0x9E3779B9)
-        out[i] = float((hi << 21) | (lo >> 11)) * 2.0 ** -53
-    return out
-
-
-def sample_reference(probs_f32, seed, env_ids, episode, turn):
-    """The sampling rule in numpy: action = #{k < A - 1 : c_k <= u}, c_k the running sum in double,
-    k = 0, 1, ..., of the float32 probabilities, u = keyed_u(...).  int8 [B]."""
-    p = np.asarray(probs_f32)
-    if p.dtype != np.float32:
-        raise ValueError("probs must be float32: the rule is defined on the values the kernel writes")
-    c = np.cumsum(p.astype(np.float64), axis=1)  # sequential, in order k = 0, 1, ...
-    u = keyed_u(seed, np.asarray(env_ids), np.asarray(episode), np.asarray(turn))
-    return (c[:, :-1] <= u[:, None]).sum(axis=1).astype(np.int8)
-
-
 class DevicePolicy:
     """The policy network on the env's device.  `module_or_state_dict` holds the five Linears by
     the reference's names (affine1, affine2, affine3, action_head, value_head); `env` is the
@@ -601,6 +256,8 @@ class DevicePolicy:
         if A != base.n_actions:
             raise ValueError("the policy has %d actions, the env's options %d" % (A, base.n_actions))
         self.in_features, self.n_actions = F, A
+        self._shapes = dict(zip(ADAM_TENSORS, ((h1, F), (h1,), (h2, h1), (h2,), (h3, h2), (h3,), (A, h3), (A,),
+                                                     (1, h3), (1,))))
         L = _lib.load()
         shp = _lib.WabPolicyShape(F, h1, h2, h3, A)
         p = ctypes.c_void_p()
@@ -621,8 +278,7 @@ class DevicePolicy:
         if shape_of(module_or_state_dict) != self.shape:
             raise ValueError("load(): the layers' shapes differ from the policy's %s" % (self.shape,))
         sd = _state_dict(module_or_state_dict)
-        keep = [sd["%s.%s" % (n, part)].detach().to(self.env.device, t.float32).contiguous()
-                for n in LAYERS for part in ("weight", "bias")]
+        keep = [sd[k].detach().to(self.env.device, t.float32).contiguous() for k in ADAM_TENSORS]
         w = _lib.WabPolicyWeights(*[x.data_ptr() for x in keep])
         _lib.check(_lib.load().wab_policy_load(self._p, ctypes.addressof(w), self.env._stream()),
                    "wab_policy_load")
@@ -654,16 +310,13 @@ class DevicePolicy:
         return dst
 
     def _grad_targets(self, into, accumulate):
-        """The ten gradient tensors in LAYERS order (weight, bias): `into`'s .grad fields
+        """The ten gradient tensors by name, in ADAM_TENSORS order: `into`'s .grad fields
         (allocated where missing), or fresh ones."""
         t = self._torch
-        F, h1, h2, h3, A = self.shape
-        shapes = [(h1, F), (h1,), (h2, h1), (h2,), (h3, h2), (h3,), (A, h3), (A,), (1, h3), (1,)]
-        names = ["%s.%s" % (n, part) for n in LAYERS for part in ("weight", "bias")]
         if into is None:
-            return {k: t.empty(shp, dtype=t.float32, device=self.env.device) for k, shp in zip(names, shapes)}
+            return {k: t.empty(shp, dtype=t.float32, device=self.env.device) for k, shp in self._shapes.items()}
         out = {}
-        for k, shp in zip(names, shapes):
+        for k, shp in self._shapes.items():
             layer, part = k.split(".")
             prm = getattr(getattr(into, layer, None), part, None)
             if not isinstance(prm, t.Tensor) or tuple(prm.shape) != shp:
@@ -699,34 +352,64 @@ class DevicePolicy:
         copy is made: the result is, bit for bit, that of the call on index_select copies.
         N = rows.numel() is what "mean" divides by, and the row outputs are [N].  An index outside
         [0, M) is never followed: its row is left out and counted, and check() raises for it."""
-        t = self._torch
-        n = check_loss_args(self.shape, features, actions, weight, target, value_loss, reduction, into, accumulate)
-        if features.device != self.env.device:
-            raise ValueError("features must be on %s" % (self.env.device,))
-        n, gather = self._row_index(rows, n)
-        grads = self._grad_targets(into, accumulate)
-        L = _lib.load()
-        cfg = _lib.WabPolicyLoss(float(value_coef), float(entropy_coef), _lib.VALUE_LOSS[value_loss],
-                                 float(scale) if scale is not None else (1.0 / n if reduction == "mean" and n > 0
-                                                                         else 1.0), 1 if accumulate else 0,
-                                 int(chunk_rows))
-        self._workspace(n, chunk_rows)
-        loss = t.zeros(4, dtype=t.float32, device=self.env.device)
-        rows = [t.empty(n, dtype=t.float32, device=self.env.device) for _ in range(3)] if return_rows else [None] * 3
-        gw = _lib.WabPolicyWeights(*[grads["%s.%s" % (nm, part)].data_ptr() for nm in LAYERS
-                                     for part in ("weight", "bias")])
-        call = L.wab_policy_grad_gather if gather else L.wab_policy_grad
-        _lib.check(call(self._p, features.data_ptr(), actions.data_ptr(), weight.data_ptr(),
-                        target.data_ptr(), n, ctypes.addressof(cfg), ctypes.addressof(gw),
-                        loss.data_ptr(), *[None if r is None else r.data_ptr() for r in rows],
-                        self._grad_ws.data_ptr(), self._grad_ws.numel(), self.env._stream(), *gather),
-                   "wab_policy_grad_gather" if gather else "wab_policy_grad")
-        out = {"loss": loss[3], "loss_policy": loss[0], "loss_value": loss[1], "entropy": loss[2]}
-        if into is None:
-            out["grads"] = grads
-        if return_rows:
-            lead = (n,) if gather else tuple(features.shape[:-1])
-            out["logp"], out["value"], out["entropy_rows"] = [r.view(lead) for r in rows]
+        m = check_loss_args(self.shape, features, actions, weight, target, value_loss, reduction, into, accumulate)
+        return self._run("grad", features, m, rows, [actions, weight, target],
+                         ("logp", "value", "entropy") if return_rows else (None,) * 3,
+                         loss=(value_coef, entropy_coef, value_loss, reduction, into, accumulate, chunk_rows, scale))
+
+    def _run(self, name, features, m, rows, per_row, row_names, loss=None, ppo=None):
+        """What loss_and_grad ("grad"), ppo_loss_and_grad ("grad_ppo") and evaluate ("evaluate") do
+        after their argument checks: one call of wab_policy_<name>, or with rows= of its _gather
+        form.  m: the checked source's rows; per_row: the input tensors after features, in the
+        call's order (None: not passed); row_names: the call's row outputs in its order, "logp",
+        "value", "entropy", "ratio" (None: not wanted); loss: the loss keywords (None: evaluate,
+        which keeps nothing in the workspace but the two counts); ppo: (clip, value_clip, old_logp,
+        old_value)."""
+        t, dev = self._torch, self.env.device
+        if features.device != dev:
+            raise ValueError("features must be on %s" % (dev,))
+        n, gather = self._row_index(rows, m)
+        if ppo is not None:
+            clip, value_clip, old_logp, old_value = ppo
+            # (no rows: nothing to clip, and an empty old_value has no address to pass)
+            vclip = float(value_clip) if value_clip is not None and float(value_clip) > 0 and n > 0 else 0.0
+            per_row = per_row + [old_logp, old_value if vclip > 0 else None]
+        mid, out = [], {}
+        if loss is None:
+            if self._grad_ws is None:
+                self._grad_ws = t.empty(256, dtype=t.uint8, device=dev)
+        else:
+            value_coef, entropy_coef, value_loss, reduction, into, accumulate, chunk_rows, scale = loss
+            grads = self._grad_targets(into, accumulate)
+            cfg = _lib.WabPolicyLoss(float(value_coef), float(entropy_coef), _lib.VALUE_LOSS[value_loss],
+                                     float(scale) if scale is not None else (1.0 / n if reduction == "mean" and n > 0
+                                                                             else 1.0), 1 if accumulate else 0,
+                                     int(chunk_rows))
+            pcfg = None if ppo is None else _lib.WabPpoConfig(float(clip), vclip)
+            self._workspace(n, chunk_rows)
+            sums = t.zeros(4 if ppo is None else 8, dtype=t.float32, device=dev)  # loss_out[4], ppo_out[4]
+            gw = _lib.WabPolicyWeights(*[grads[k].data_ptr() for k in ADAM_TENSORS])
+            mid = [ctypes.addressof(x) for x in (cfg, pcfg, gw) if x is not None] + [sums.data_ptr()]
+            if ppo is not None:
+                mid.append(sums[4:].data_ptr())
+        bufs = [None if k is None else t.empty(n, dtype=t.float32, device=dev) for k in row_names]
+        symbol = "wab_policy_%s%s" % (name, "_gather" if gather else "")
+        _lib.check(getattr(_lib.load(), symbol)(
+            self._p, features.data_ptr(), *[None if x is None else x.data_ptr() for x in per_row], n, *mid,
+            *[None if r is None else r.data_ptr() for r in bufs],
+            self._grad_ws.data_ptr(), self._grad_ws.numel(), self.env._stream(), *gather), symbol)
+        if loss is not None:
+            out = {"loss": sums[3], "loss_policy": sums[0], "loss_value": sums[1], "entropy": sums[2]}
+            if ppo is not None:
+                diag = sums[4:] / float(max(n, 1))
+                out["clip_fraction"], out["approx_kl"], out["value_clip_fraction"], out["ratio_mean"] = diag.unbind(0)
+                out["ppo_sums"] = sums[4:]
+            if into is None:
+                out["grads"] = grads
+        lead = (n,) if gather else tuple(features.shape[:-1])
+        for k, r in zip(row_names, bufs):  # (beside the loss's sums, the entropy rows are "entropy_rows")
+            if r is not None:
+                out["entropy_rows" if loss is not None and k == "entropy" else k] = r.view(lead)
         return out
 
     def _row_index(self, rows, m):
@@ -761,23 +444,9 @@ class DevicePolicy:
         this logp is exactly 1.  A row whose action is out of range has logp 0 and is counted:
         check() raises for it.  rows: as loss_and_grad's (wab_policy_evaluate_gather); the results
         are then [N], in the index's order."""
-        t = self._torch
-        n = check_rows(self.shape, features, **({} if actions is None else {"actions": actions}))
-        if features.device != self.env.device:
-            raise ValueError("features must be on %s" % (self.env.device,))
-        n, gather = self._row_index(rows, n)
-        if self._grad_ws is None:
-            self._grad_ws = t.empty(256, dtype=t.uint8, device=self.env.device)
-        names = (("logp",) if actions is not None else ()) + ("value", "entropy")
-        rows = {k: t.empty(n, dtype=t.float32, device=self.env.device) for k in names}
-        L = _lib.load()
-        _lib.check((L.wab_policy_evaluate_gather if gather else L.wab_policy_evaluate)(
-            self._p, features.data_ptr(), None if actions is None else actions.data_ptr(), n,
-            *[rows[k].data_ptr() if k in rows else None for k in ("logp", "value", "entropy")],
-            self._grad_ws.data_ptr(), self._grad_ws.numel(), self.env._stream(), *gather),
-            "wab_policy_evaluate_gather" if gather else "wab_policy_evaluate")
-        lead = (n,) if gather else tuple(features.shape[:-1])
-        return {k: r.view(lead) for k, r in rows.items()}
+        m = check_rows(self.shape, features, **({} if actions is None else {"actions": actions}))
+        return self._run("evaluate", features, m, rows, [actions],
+                         ("logp" if actions is not None else None, "value", "entropy"))
 
     def ppo_loss_and_grad(self, features, actions, advantage, target, old_logp, *, clip=0.2, old_value=None,
                           value_clip=None, value_coef=1.0, entropy_coef=0.0, value_loss="smooth_l1", reduction="sum",
@@ -792,42 +461,12 @@ class DevicePolicy:
         and 0-d device tensors "clip_fraction", "approx_kl" (Schulman's k3), "value_clip_fraction"
         and "ratio_mean", each a sum over the rows divided by N on the device ("ppo_sums": the
         four sums themselves); with return_rows also "ratio"."""
-        t = self._torch
-        n = check_ppo_args(self.shape, features, actions, advantage, target, old_logp, clip, old_value, value_clip,
+        m = check_ppo_args(self.shape, features, actions, advantage, target, old_logp, clip, old_value, value_clip,
                            value_loss, reduction, into, accumulate)
-        if features.device != self.env.device:
-            raise ValueError("features must be on %s" % (self.env.device,))
-        n, gather = self._row_index(rows, n)
-        # (no rows: nothing to clip, and an empty old_value has no address to pass)
-        vclip = float(value_clip) if value_clip is not None and float(value_clip) > 0 and n > 0 else 0.0
-        grads = self._grad_targets(into, accumulate)
-        cfg = _lib.WabPolicyLoss(float(value_coef), float(entropy_coef), _lib.VALUE_LOSS[value_loss],
-                                 float(scale) if scale is not None else (1.0 / n if reduction == "mean" and n > 0
-                                                                         else 1.0), 1 if accumulate else 0,
-                                 int(chunk_rows))
-        ppo = _lib.WabPpoConfig(float(clip), vclip)
-        ws = self._workspace(n, chunk_rows)
-        sums = t.zeros(8, dtype=t.float32, device=self.env.device)  # loss_out[4], ppo_out[4]
-        rows = [t.empty(n, dtype=t.float32, device=self.env.device) for _ in range(4)] if return_rows else [None] * 4
-        gw = _lib.WabPolicyWeights(*[grads["%s.%s" % (nm, part)].data_ptr() for nm in LAYERS
-                                     for part in ("weight", "bias")])
-        L = _lib.load()
-        _lib.check((L.wab_policy_grad_ppo_gather if gather else L.wab_policy_grad_ppo)(
-            self._p, features.data_ptr(), actions.data_ptr(), advantage.data_ptr(), target.data_ptr(),
-            old_logp.data_ptr(), old_value.data_ptr() if vclip > 0 else None, n, ctypes.addressof(cfg),
-            ctypes.addressof(ppo), ctypes.addressof(gw), sums.data_ptr(), sums[4:].data_ptr(),
-            *[None if r is None else r.data_ptr() for r in rows], ws.data_ptr(), ws.numel(), self.env._stream(),
-            *gather), "wab_policy_grad_ppo_gather" if gather else "wab_policy_grad_ppo")
-        out = {"loss": sums[3], "loss_policy": sums[0], "loss_value": sums[1], "entropy": sums[2]}
-        diag = sums[4:] / float(max(n, 1))
-        out["clip_fraction"], out["approx_kl"], out["value_clip_fraction"], out["ratio_mean"] = diag.unbind(0)
-        out["ppo_sums"] = sums[4:]
-        if into is None:
-            out["grads"] = grads
-        if return_rows:
-            lead = (n,) if gather else tuple(features.shape[:-1])
-            out["logp"], out["value"], out["entropy_rows"], out["ratio"] = [r.view(lead) for r in rows]
-        return out
+        return self._run("grad_ppo", features, m, rows, [actions, advantage, target],
+                         ("logp", "value", "entropy", "ratio") if return_rows else (None,) * 4,
+                         loss=(value_coef, entropy_coef, value_loss, reduction, into, accumulate, chunk_rows, scale),
+                         ppo=(clip, value_clip, old_logp, old_value))
 
     def check(self):
         """Synchronises; raises IndexError if the latest loss_and_grad left rows out because their
@@ -970,7 +609,7 @@ class DeviceAdam:
         torch.optim.Adam / AdamW over the same model; the beta powers are rebuilt by `step`
         sequential double multiplications.  The skipped count starts again at 0."""
         t = self._torch
-        step, m, v, hyper = parse_adam_state_dict(sd, self._order, [tuple(p.shape) for p in self.params])
+        step, m, v, hyper = parse_adam_state_dict(sd, self._order, list(self.policy._shapes.values()))
         self.lr, self.betas, self.eps = hyper["lr"], hyper["betas"], hyper["eps"]
         self.weight_decay, self.decoupled = hyper["weight_decay"], hyper["decoupled"]
         self.max_grad_norm = hyper.get("max_grad_norm", self.max_grad_norm)
@@ -984,3 +623,10 @@ class DeviceAdam:
         b1p, b2p = adam_beta_powers(step, self.betas)
         host = _lib.WabAdamState(step, 0, b1p, b2p, 0.0, 0.0, 0)
         self._state.copy_(t.from_numpy(np.frombuffer(bytes(host), dtype=np.int64).copy()))
+
+
+# The numeric contracts (policy_reference.py), by name: every policy.X of before the split resolves.
+# (At the end: policy_reference imports this module's names, and either can be imported first.)
+from .policy_reference import (adam_fresh_state, keyed_u, pair_tree_sum, reference_adam_step,  # noqa: E402,F401
+                               reference_forward, reference_loss_and_grad, reference_ppo_loss_and_grad,
+                               sample_reference, _reference_gather, _reference_head_and_backward, _value_loss)
