@@ -10,7 +10,8 @@ launches on one stream; the one host read per epoch (the printed loss, clip frac
 optional: --quiet leaves it out.
 
     python examples/train_ppo.py [--envs 4096] [--steps 64] [--updates 20] [--epochs 4]
-                                 [--minibatches 4] [--clip 0.2] [--value-clip 0.2] [--shuffle] [--quiet]
+                                 [--minibatches 4] [--clip 0.2] [--value-clip 0.2] [--shuffle] [--packed]
+                                 [--quiet]
 """
 import argparse
 import os
@@ -29,22 +30,27 @@ from train_actor_critic import Policy  # noqa: E402,F401
 
 
 def update(wrapper, policy, model, opt, T, epochs=4, minibatches=4, clip=0.2, value_clip=0.2, entropy_coef=0.0,
-           report=None, shuffle=False, perm=None):
+           report=None, shuffle=False, perm=None, packed=False):
     """One rollout segment and epochs x minibatches clipped steps (opt: a DeviceAdam, whose step()
     re-packs the policy's weights).  Minibatch m is the steps [m T / M, (m + 1) T / M) of the
     segment, a view; with shuffle, the rows perm[m n : (m + 1) n] of a permutation of the segment's
     T B rows drawn afresh each epoch into `perm` (an int32 [T B] device buffer, made here when not
     given), n = T B / M.  Returns the ppo_loss_and_grad results as a list of lists [epoch][minibatch]
-    (device tensors: nothing here reads them); report(epoch, results) is called after each epoch."""
+    (device tensors: nothing here reads them); report(epoch, results) is called after each epoch.
+    packed: the segment's feature rows are kept as 1 bit per feature (wab_rollout_policy_packed, 64
+    bytes per row of the reference net instead of 1796) for the evaluate pass and every minibatch;
+    the parameters after the update have the same bits."""
     if T % minibatches != 0:
         raise ValueError("the segment's %d steps do not split into %d minibatches" % (T, minibatches))
-    r = wrapper.rollout_policy(policy, T, bootstrap_value=True, gae_lambda=0.95, whiten=True)
-    old_logp = policy.evaluate(r["features"], r["actions"])["logp"]
+    r = wrapper.rollout_policy(policy, T, bootstrap_value=True, gae_lambda=0.95, whiten=True,
+                               store_features="packed" if packed else True)
+    feats = r["feature_bits"] if packed else r["features"]
+    old_logp = policy.evaluate(feats, r["actions"])["logp"]
     step = T // minibatches
     rows_all = r["actions"].numel()
     n = rows_all // minibatches
     if shuffle and perm is None:
-        perm = torch.empty(rows_all, dtype=torch.int32, device=r["features"].device)
+        perm = torch.empty(rows_all, dtype=torch.int32, device=feats.device)
     results = []
     for e in range(epochs):
         outs = []
@@ -52,14 +58,14 @@ def update(wrapper, policy, model, opt, T, epochs=4, minibatches=4, clip=0.2, va
             torch.randperm(rows_all, device=perm.device, dtype=torch.int32, out=perm)
         for m in range(minibatches):
             if shuffle:
-                outs.append(policy.ppo_loss_and_grad(r["features"], r["actions"], r["advantage"], r["target"],
+                outs.append(policy.ppo_loss_and_grad(feats, r["actions"], r["advantage"], r["target"],
                                                      old_logp, clip=clip, old_value=r["value"],
                                                      value_clip=value_clip, into=model, reduction="mean",
                                                      entropy_coef=entropy_coef, rows=perm[m * n:(m + 1) * n]))
                 opt.step()
                 continue
             s = slice(m * step, (m + 1) * step)
-            outs.append(policy.ppo_loss_and_grad(r["features"][s], r["actions"][s], r["advantage"][s], r["target"][s],
+            outs.append(policy.ppo_loss_and_grad(feats[s], r["actions"][s], r["advantage"][s], r["target"][s],
                                                  old_logp[s], clip=clip, old_value=r["value"][s],
                                                  value_clip=value_clip, into=model, reduction="mean",
                                                  entropy_coef=entropy_coef))
@@ -86,6 +92,7 @@ def main():
     ap.add_argument("--clip", type=float, default=0.2)
     ap.add_argument("--value-clip", type=float, default=0.2, help="0: no value clipping")
     ap.add_argument("--shuffle", action="store_true", help="minibatches from a fresh permutation of the rows per epoch")
+    ap.add_argument("--packed", action="store_true", help="keep the segment's feature rows as 1 bit per feature")
     ap.add_argument("--quiet", action="store_true", help="no host read per epoch")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -101,7 +108,7 @@ def main():
         if not args.quiet:
             print("update %d" % i)
         update(wrapper, policy, model, opt, args.steps, args.epochs, args.minibatches, args.clip, args.value_clip,
-               report=None if args.quiet else print_epoch, shuffle=args.shuffle, perm=perm)
+               report=None if args.quiet else print_epoch, shuffle=args.shuffle, perm=perm, packed=args.packed)
     policy.check()
     print("optimizer: %s" % (opt.stats(),))
 

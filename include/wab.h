@@ -658,6 +658,55 @@ int wab_policy_evaluate_gather(wab_policy* p, const float* features, const int8_
  * not 0. */
 int wab_policy_grad_bad_rows(const wab_policy* p, const void* workspace, void* stream, uint64_t* out);
 
+/* ---- packed feature rows: 1 bit per feature ------------------------------------------------ */
+
+/* Defined where the entry points below exist (added without a change of WAB_ABI_VERSION: nothing
+ * older changed).
+ * The format.  A PragmaticObsWrapper row is a one-hot layout: every float is 0.0 or 1.0.  A packed
+ * row of F features is P = 4 * ceil(F / 128) little-endian dwords (a multiple of 16 bytes):
+ * feature k is bit (k & 31) of dword (k >> 5).  Every producer writes bits F .. 32 P - 1 as 0;
+ * every consumer ignores them.  Arrays are [rows][P] uint32, 16-byte aligned.  The calls that read
+ * packed rows give, bit for bit, the results of their float counterparts on the unpacked rows:
+ * 0 and 1 are exact in bf16 and no sum changes its order. */
+#define WAB_HAS_PACKED_FEATURES 1
+
+/* P for rows of in_features features; WAB_E_INVALID outside wab_policy_create's range [1, 2^20]. */
+int wab_feature_bits_pitch(int32_t in_features);
+
+/* features [n_rows][F] float32 (4-byte aligned) -> bits [n_rows][P] (16-byte aligned): the bit is
+ * set iff the float's bit pattern is not 0x00000000.  nonbinary (device, 8-byte aligned, or NULL):
+ * the call adds the number of elements whose pattern is neither 0x00000000 nor 0x3F800000 (-0.0f
+ * and NaN count).  wab_features_unpack writes exactly 0.0f or 1.0f.  Each is one launch on
+ * `stream` (none when n_rows == 0), with no allocation and no synchronisation, safe to capture in
+ * a hipGraph.  WAB_E_INVALID for a NULL or misaligned pointer with n_rows > 0, n_rows < 0, or F
+ * outside [1, 2^20]. */
+int wab_features_pack(const float* features, int64_t n_rows, int32_t F, uint32_t* bits, uint64_t* nonbinary,
+                      void* stream);
+int wab_features_unpack(const uint32_t* bits, int64_t n_rows, int32_t F, float* features, void* stream);
+
+/* wab_policy_evaluate_gather, wab_policy_grad_gather and wab_policy_grad_ppo_gather with the
+ * source's feature rows packed: feature_bits [M][P] (rows == NULL: [N][P]) in place of features.
+ * rows == NULL means the contiguous rows 0 .. N - 1, and M is ignored; rows != NULL is the gather
+ * contract unchanged (clamping, bad rows, the index read on the device).  Workspace, launches,
+ * graph safety, bad-action counting and every refusal are the float calls'; feature_bits must be
+ * 16-byte aligned. */
+int wab_policy_evaluate_packed(wab_policy* p, const uint32_t* feature_bits, const int8_t* actions, int64_t N,
+                               float* logp, float* value, float* entropy,
+                               void* workspace, size_t workspace_bytes, void* stream,
+                               const int32_t* rows, int64_t M);
+int wab_policy_grad_packed(wab_policy* p, const uint32_t* feature_bits, const int8_t* actions, const float* weight,
+                           const float* target, int64_t N, const wab_policy_loss* loss,
+                           const wab_policy_weights* grads_out, float loss_out[4], float* logp, float* value,
+                           float* entropy, void* workspace, size_t workspace_bytes, void* stream,
+                           const int32_t* rows, int64_t M);
+int wab_policy_grad_ppo_packed(wab_policy* p, const uint32_t* feature_bits, const int8_t* actions, const float* advantage,
+                               const float* target, const float* old_logp, const float* old_value, int64_t N,
+                               const wab_policy_loss* loss, const wab_ppo_config* ppo,
+                               const wab_policy_weights* grads_out, float loss_out[4], float ppo_out[4],
+                               float* logp, float* value, float* entropy, float* ratio,
+                               void* workspace, size_t workspace_bytes, void* stream,
+                               const int32_t* rows, int64_t M);
+
 /* ---- device policy: the optimizer step (actor_critic.py:104, 165) ----------------------- */
 
 /* torch.optim.Adam's step (AdamW's with `decoupled`) over the ten parameter tensors, with a
@@ -773,6 +822,22 @@ int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int
                        const wab_obs* obs_seq, int8_t* actions, float* value, float* probs,
                        float* reward, uint8_t* done, float* features, float* features_last,
                        double gamma, const float* bootstrap, float* returns, void* stream);
+
+/* wab_rollout_policy with the [T][B][F] float `features` replaced by feature_bits [T][B][P]
+ * (WAB_HAS_PACKED_FEATURES; required, 16-byte aligned): slice t is wab_features_pack of what
+ * features[t] would have held, slice 0 that of features0.  Everything else is wab_rollout_policy's,
+ * bit for bit: features0 and features_last stay float32 [B][F]; actions, value, probs, reward,
+ * done, returns, the counters and the refusals are unchanged.  Slice 0 is written by a
+ * wab_features_pack launch queued in front on the same stream.  Where wab_rollout_policy_fused
+ * is 1 the steps are then one launch, whose rows-out phase writes the packed rows from the
+ * feature bits on chip (no float row reaches device memory but features_last); elsewhere each
+ * step of the 2 T calls goes through the handle-owned pair of float rows and is followed by one
+ * wab_features_pack launch into slice t + 1.  WAB_E_INVALID also for feature_bits == NULL or not
+ * 16-byte aligned. */
+int wab_rollout_policy_packed(wab_handle* h, wab_policy* p, const float* features0, int32_t T,
+                              const wab_obs* obs_seq, int8_t* actions, float* value, float* probs,
+                              float* reward, uint8_t* done, uint32_t* feature_bits, float* features_last,
+                              double gamma, const float* bootstrap, float* returns, void* stream);
 
 /* Test hook: the bush value (berries, generate_n_bush_values wab_env.py:631-635) the step
  * kernels give the 53-bit draws U[n] under h's threshold table, computed by the kernels' own

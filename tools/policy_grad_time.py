@@ -9,7 +9,10 @@ advantage and target that every variant works on:
     (a) torch_fp32   stock torch: fp32 forward over the T B rows, the same loss, backward(),
     (b) loss_and_grad, eager   DevicePolicy.loss_and_grad(into=model) (wab_policy_grad),
     (b) loss_and_grad, graph   the same call captured once and replayed,
-    (c) torch_bf16   (a) under torch.autocast(bfloat16): for information only.
+    (c) torch_bf16   (a) under torch.autocast(bfloat16): for information only,
+    (d) evaluate, loss_and_grad and ppo_loss_and_grad, eager, on the float rows and on the same
+        rows packed to 1 bit per feature (wab_gym_amd.features; the *_packed lines), each over the
+        contiguous rows and through rows= (a permutation of the T B rows; the *_rows lines).
 Each call is timed between two hipEvents on the stream and ends in a synchronise; the variants
 alternate once per batch after a warm-up batch; medians of `batches` with min and max.  (b) is
 also set against the bytes it must move (the features twice, the bf16 workspace once out and once
@@ -104,12 +107,40 @@ def main():
     with torch.cuda.graph(graph):
         device_update()
 
+    # (d): the float rows and the same rows packed, contiguous and through an index
+    from wab_gym_amd.features import pack_features
+
+    bits = pack_features(feats)
+    perm = torch.randperm(N, device=dev, dtype=torch.int32)
+    old_logp = pol.evaluate(feats, acts)["logp"]
+
+    def family(name, rows_of):
+        def ev(x, rows):
+            return lambda: pol.evaluate(x, acts, rows=rows)
+
+        def lg(x, rows):
+            return lambda: pol.loss_and_grad(x, acts, adv, tgt, into=model, reduction="mean", rows=rows)
+
+        def ppo(x, rows):
+            return lambda: pol.ppo_loss_and_grad(x, acts, adv, tgt, old_logp, clip=0.2, old_value=r["value"],
+                                                 value_clip=0.2, into=model, reduction="mean", rows=rows)
+
+        make = {"evaluate": ev, "loss_and_grad": lg, "ppo_loss_and_grad": ppo}[name]
+        return {name + sfx: make(x, rows_of(tag)) for sfx, x, tag in
+                (("", feats, 0), ("_packed", bits, 0), ("_rows", feats, 1), ("_rows_packed", bits, 1))}
+
+    extra = {}
+    for name in ("evaluate", "loss_and_grad", "ppo_loss_and_grad"):
+        extra.update(family(name, lambda tag: perm if tag else None))
+    extra.pop("loss_and_grad")  # (loss_and_grad_eager above)
+
     variants = {
         "torch_fp32": lambda: torch_update(False),
         "loss_and_grad_eager": device_update,
         "loss_and_grad_graph": graph.replay,
         "torch_bf16_autocast": lambda: torch_update(True),
     }
+    variants.update(extra)
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -132,6 +163,7 @@ def main():
     units = 2 * (128 + 160 + 128) + 16  # X_1..3, D_1..3 padded to the tile, D_4: bf16 per row
     must = 2 * N * F * 4 + 2 * N * units * 2
     floor_ms = must / 6.3e12 * 1e3
+    res["feature_bytes"] = {"float": N * F * 4, "packed": bits.numel() * 4}
     res["bytes_must_move"] = must
     res["floor_ms_at_6.3TBps"] = floor_ms
     res["eager_over_floor"] = res["loss_and_grad_eager_ms"]["median"] / floor_ms

@@ -3,7 +3,7 @@
     python tools/policy_rate.py [--envs 65536] [--reps 20] [--batches 7] [--steps 64]
 
 One env of B envs with the default options (449 features) and the reference's 449-128-150-128-5
-network.  Seven variants, each captured as a graph of `reps` calls and replayed, alternating, once
+network.  Eight variants, each captured as a graph of `reps` calls and replayed, alternating, once
 per batch between two hipEvents on the stream, after a warm-up replay of each:
     act     (a) wab_policy_act alone (probs and value written too),
     loop    (b) the closed-loop step: wab_policy_act, then wab_step_features without planes,
@@ -12,9 +12,12 @@ per batch between two hipEvents on the stream, after a warm-up replay of each:
     fusedS  (e) the fused closed loop, wab_rollout_policy as one launch of --steps steps with the
                 feature rows stored ([T, B, 449] float32),
     fusedN  (f) the same with features = NULL (no intermediate row leaves the chip),
+    fusedP  the same with the rows stored packed, 1 bit per feature (wab_rollout_policy_packed:
+            [T, B, 16] uint32, 64 bytes per row instead of 1796; the call's wab_features_pack
+            launch for slice 0 is part of the time),
     roll    the floor of (e): wab_rollout_features, the same launch with pre-chosen actions and no
             policy (the env steps and the feature stores that (e) contains).
-(e), (f) and roll are reported per step (a call's time / --steps), so they compare with (b).
+(e), (f), fusedP and roll are reported per step (a call's time / --steps), so they compare with (b).
 (a), (c) and (d) read a ring of four feature buffers (4 x 118 MB at B = 65536, more than the
 256 MB Infinity Cache), so that a call's features come from HBM as they do behind a step; (b)
 reads what its own step just wrote.  Prints every batch's per-call time, the median and the
@@ -113,15 +116,24 @@ def main():
     def fused_null(i):
         fused(None)
 
+    seq_bits = torch.empty((T, B, L.wab_feature_bits_pitch(F)), dtype=torch.int32, device=dev)
+
+    def fused_packed(i):
+        _lib.check(L.wab_rollout_policy_packed(env._h, pol._p, fused_feats.data_ptr(), T, ctypes.addressof(seq_obs),
+                                               pol_actions.data_ptr(), seq_value.data_ptr(), seq_probs.data_ptr(),
+                                               seq_reward.data_ptr(), seq_done.data_ptr(), seq_bits.data_ptr(),
+                                               fused_feats.data_ptr(), 0.99, None, None, env._stream()),
+                   "wab_rollout_policy_packed")
+
     def roll(i):
         _lib.check(L.wab_rollout_features(env._h, seq_actions.data_ptr(), T, ctypes.addressof(seq_obs),
                                           seq_reward.data_ptr(), seq_done.data_ptr(), seq.data_ptr(), 0.99, None, None,
                                           env._stream()), "wab_rollout_features")
 
-    per_call = {"fusedS": T, "fusedN": T, "roll": T}  # steps per call
+    per_call = {"fusedS": T, "fusedN": T, "fusedP": T, "roll": T}  # steps per call
     env.validate_actions = False  # (the policy's actions are in range; no per-step host check)
     variants = {"act": act, "loop": loop, "read": read, "torch": stock_act, "fusedS": fused_stored,
-                "fusedN": fused_null, "roll": roll}
+                "fusedN": fused_null, "fusedP": fused_packed, "roll": roll}
     stream = torch.cuda.current_stream(dev)
     graphs = {}
     for name, fn in variants.items():
@@ -159,7 +171,7 @@ def main():
 
     med = {k: statistics.median(v) for k, v in times.items()}
     for k, v in times.items():
-        print("%-6s us per call (fusedS, fusedN, roll: per step), by batch: %s   median %.1f  (min %.1f, max %.1f)"
+        print("%-6s us per call (fusedS, fusedN, fusedP, roll: per step), by batch: %s   median %.1f  (min %.1f, max %.1f)"
               % (k, " ".join("%.1f" % x for x in v), med[k], min(v), max(v)))
     nbytes = B * F * 4
     print("features: %d bytes per call; read %.0f GB/s, act %.0f GB/s" % (nbytes, nbytes / med["read"] / 1e3,
@@ -168,7 +180,7 @@ def main():
                       "act_us": round(med["act"], 2), "loop_us": round(med["loop"], 2),
                       "read_us": round(med["read"], 2), "torch_us": round(med["torch"], 2), "steps": T,
                       "fused_stored_us": round(med["fusedS"], 2), "fused_null_us": round(med["fusedN"], 2),
-                      "roll_features_us": round(med["roll"], 2),
+                      "fused_packed_us": round(med["fusedP"], 2), "roll_features_us": round(med["roll"], 2),
                       "spread_us": {k: [round(min(v), 2), round(max(v), 2)] for k, v in times.items()},
                       "act_over_read": round(med["act"] / med["read"], 2),
                       "torch_over_act": round(med["torch"] / med["act"], 2)}))

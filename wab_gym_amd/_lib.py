@@ -28,6 +28,9 @@ EXPORTED = [
     "wab_policy_grad_ppo", "wab_policy_evaluate",
     "wab_policy_grad_gather", "wab_policy_grad_ppo_gather", "wab_policy_evaluate_gather", "wab_policy_grad_bad_rows",
     "wab_policy_adam_workspace", "wab_policy_adam_step",
+    # WAB_HAS_PACKED_FEATURES: feature rows as 1 bit per feature
+    "wab_feature_bits_pitch", "wab_features_pack", "wab_features_unpack", "wab_policy_evaluate_packed",
+    "wab_policy_grad_packed", "wab_policy_grad_ppo_packed", "wab_rollout_policy_packed",
     # include/wab_torus.h: the Environment 2.0 torus world
     "wab2_abi_version", "wab2_last_error", "wab2_record_size", "wab2_create", "wab2_destroy",
     "wab2_batch", "wab2_reset", "wab2_step", "wab2_rollout", "wab2_get_state", "wab2_get_counters",
@@ -177,6 +180,14 @@ def load():
     L.wab_policy_grad_ppo_gather.argtypes = L.wab_policy_grad_ppo.argtypes + [P, I64]
     L.wab_policy_evaluate_gather.argtypes = L.wab_policy_evaluate.argtypes + [P, I64]
     L.wab_policy_grad_bad_rows.argtypes = [P, P, P, P]
+    # the _gather calls' arguments, feature_bits (uint32 [M][P]) in place of features; rows may be NULL
+    L.wab_policy_grad_packed.argtypes = L.wab_policy_grad_gather.argtypes
+    L.wab_policy_grad_ppo_packed.argtypes = L.wab_policy_grad_ppo_gather.argtypes
+    L.wab_policy_evaluate_packed.argtypes = L.wab_policy_evaluate_gather.argtypes
+    L.wab_feature_bits_pitch.argtypes = [I32]
+    L.wab_features_pack.argtypes = [P, I64, I32, P, P, P]
+    L.wab_features_unpack.argtypes = [P, I64, I32, P, P]
+    L.wab_rollout_policy_packed.argtypes = L.wab_rollout_policy.argtypes
     L.wab_debug_policy_grad_plan.argtypes = [P, I32, P]
     L.wab_policy_adam_workspace.argtypes = [P]
     L.wab_policy_adam_workspace.restype = ctypes.c_size_t

@@ -205,11 +205,14 @@ const void* wide_roll_kernel(const Params& p) {
 }
 
 // FEAT: the featurizer fused in (wab_step_features); ROLL: the multi-step build (Params::n_steps
-// steps per launch, wab_rollout); POLICY: the device policy between the steps (wab_rollout_policy)
+// steps per launch, wab_rollout); POLICY: the device policy between the steps (wab_rollout_policy);
+// PACKED: its rows go out as packed bits (wab_rollout_policy_packed)
 template <int SLOTS, int G, bool RULES>
-const void* small_instance(bool feat, bool roll, bool policy) {
-  if constexpr (SLOTS == 8 && G == 11)
+const void* small_instance(bool feat, bool roll, bool policy, bool packed) {
+  if constexpr (SLOTS == 8 && G == 11) {
+    if (policy && packed) return reinterpret_cast<const void*>(&wab::wab_step_small<8, 11, true, true, RULES, true, true>);
     if (policy) return reinterpret_cast<const void*>(&wab::wab_step_small<8, 11, true, true, RULES, true>);
+  }
   if (feat)
     return roll ? reinterpret_cast<const void*>(&wab::wab_step_small<SLOTS, G, true, true, RULES>)
                 : reinterpret_cast<const void*>(&wab::wab_step_small<SLOTS, G, true, false, RULES>);
@@ -219,14 +222,14 @@ const void* small_instance(bool feat, bool roll, bool policy) {
 
 }  // namespace
 
-const void* wab_host::small_kernel(int slots, bool g11, bool rules, bool feat, bool roll, bool policy) {
+const void* wab_host::small_kernel(int slots, bool g11, bool rules, bool feat, bool roll, bool policy, bool packed) {
 #if WAB_RULES_INSTANCE
-  if (g11 && slots == 8 && rules) return small_instance<8, 11, true>(feat, roll, policy);
+  if (g11 && slots == 8 && rules) return small_instance<8, 11, true>(feat, roll, policy, packed);
 #endif
   switch (slots) {
-    case 8: return g11 ? small_instance<8, 11, false>(feat, roll, policy) : small_instance<8, 0, false>(feat, roll, policy);
-    case 16: return g11 ? small_instance<16, 11, false>(feat, roll, policy) : small_instance<16, 0, false>(feat, roll, policy);
-    default: return g11 ? small_instance<32, 11, false>(feat, roll, policy) : small_instance<32, 0, false>(feat, roll, policy);
+    case 8: return g11 ? small_instance<8, 11, false>(feat, roll, policy, packed) : small_instance<8, 0, false>(feat, roll, policy, packed);
+    case 16: return g11 ? small_instance<16, 11, false>(feat, roll, policy, packed) : small_instance<16, 0, false>(feat, roll, policy, packed);
+    default: return g11 ? small_instance<32, 11, false>(feat, roll, policy, packed) : small_instance<32, 0, false>(feat, roll, policy, packed);
   }
 }
 

@@ -36,23 +36,28 @@ const void* policy_kernel(const wab::PolicyDims& d) {
   return policy_two_tiles(d) ? reinterpret_cast<const void*>(&wab::wab_policy_kernel<true>)
                              : reinterpret_cast<const void*>(&wab::wab_policy_kernel<false>);
 }
-template <int MODE, bool GATHER>
+template <int MODE, bool GATHER, bool PACKED>
 const void* policy_bwd_instance(bool two) {
-  return two ? reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<true, MODE, GATHER>)
-             : reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<false, MODE, GATHER>);
+  return two ? reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<true, MODE, GATHER, PACKED>)
+             : reinterpret_cast<const void*>(&wab::wab_policy_bwd_kernel<false, MODE, GATHER, PACKED>);
 }
-template <bool GATHER>
+template <bool GATHER, bool PACKED>
 const void* policy_bwd_mode(bool two, int mode) {
-  return mode == wab::kGradModePpo    ? policy_bwd_instance<wab::kGradModePpo, GATHER>(two)
-         : mode == wab::kGradModeEval ? policy_bwd_instance<wab::kGradModeEval, GATHER>(two)
-                                      : policy_bwd_instance<wab::kGradModeGrad, GATHER>(two);
+  return mode == wab::kGradModePpo    ? policy_bwd_instance<wab::kGradModePpo, GATHER, PACKED>(two)
+         : mode == wab::kGradModeEval ? policy_bwd_instance<wab::kGradModeEval, GATHER, PACKED>(two)
+                                      : policy_bwd_instance<wab::kGradModeGrad, GATHER, PACKED>(two);
 }
-// (gather: the rows come through an index, wab_policy_*_gather)
-const void* policy_bwd_kernel(const wab::PolicyDims& d, int mode, bool gather) {
+// (gather: the rows come through an index, wab_policy_*_gather; packed: the features are packed
+// bits, wab_policy_*_packed)
+const void* policy_bwd_kernel(const wab::PolicyDims& d, int mode, bool gather, bool packed) {
   const bool two = policy_two_tiles(d);
-  return gather ? policy_bwd_mode<true>(two, mode) : policy_bwd_mode<false>(two, mode);
+  if (packed) return gather ? policy_bwd_mode<true, true>(two, mode) : policy_bwd_mode<false, true>(two, mode);
+  return gather ? policy_bwd_mode<true, false>(two, mode) : policy_bwd_mode<false, false>(two, mode);
 }
-const void* policy_wgrad_kernel(bool gather) {
+const void* policy_wgrad_kernel(bool gather, bool packed) {
+  if (packed)
+    return gather ? reinterpret_cast<const void*>(&wab::wab_policy_wgrad_kernel<true, true>)
+                  : reinterpret_cast<const void*>(&wab::wab_policy_wgrad_kernel<false, true>);
   return gather ? reinterpret_cast<const void*>(&wab::wab_policy_wgrad_kernel<true>)
                 : reinterpret_cast<const void*>(&wab::wab_policy_wgrad_kernel<false>);
 }
@@ -176,7 +181,8 @@ int wab_policy_create(const wab_policy_shape* shape, int device, wab_policy** ou
   // the same for wab_rollout_policy's one-launch instances on this device (both: which one a
   // handle takes depends on its options)
   for (bool rules : {false, true})
-    if (e == hipSuccess) e = raise_lds(device, small_kernel(8, true, rules, true, true, true), p->lds_max);
+    for (bool packed : {false, true})
+      if (e == hipSuccess) e = raise_lds(device, small_kernel(8, true, rules, true, true, true, packed), p->lds_max);
   void *w = nullptr, *b = nullptr;
   if (e == hipSuccess) e = hipMalloc(&w, (size_t)p->dims.w_total * 2u);
   if (e == hipSuccess) e = hipMalloc(&b, (size_t)p->dims.b_total * 4u);
@@ -279,7 +285,8 @@ namespace {
 
 // What the calls on wab_policy_bwd_kernel differ in: wab_policy_grad leaves the ppo fields NULL,
 // wab_policy_evaluate loss and grads_out as well; the _gather calls set gather, rows and M
-// (features and the per-row inputs are then [M], read through rows [N]).
+// (features and the per-row inputs are then [M], read through rows [N]); the _packed calls set
+// packed and bits in place of features, and gather where they are given an index.
 struct GradCall {
   const char* name;
   int mode;  // wab::GradMode
@@ -289,6 +296,8 @@ struct GradCall {
   bool gather;
   const int32_t* rows;
   int64_t M;
+  bool packed;
+  const uint32_t* bits;
   const wab_policy_loss* loss;
   const wab_ppo_config* ppo;
   const wab_policy_weights* grads_out;
@@ -312,10 +321,15 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
     if (c.M < 1 || c.M > INT32_MAX) return fail(WAB_E_INVALID, w + "M outside [1, 2^31)");
     if ((reinterpret_cast<uintptr_t>(c.rows) & 3u) != 0) return fail(WAB_E_INVALID, w + "rows must be 4-byte aligned");
   }
+  if (c.packed) {
+    if (N > 0 && !c.bits) return fail(WAB_E_INVALID, w + "NULL argument (feature_bits is required)");
+    if (!aligned16(c.bits)) return fail(WAB_E_INVALID, w + "feature_bits must be 16-byte aligned");
+  }
+  const bool no_rows = N > 0 && !c.packed && !c.features;
   if (eval) {
-    if (N > 0 && (!c.features || (c.logp && !c.actions)))
+    if (no_rows || (N > 0 && c.logp && !c.actions))
       return fail(WAB_E_INVALID, w + "NULL argument (features are required, and actions with logp)");
-  } else if (N > 0 && (!c.features || !c.actions || !c.weight || !c.target)) {
+  } else if (no_rows || (N > 0 && (!c.actions || !c.weight || !c.target))) {
     return fail(WAB_E_INVALID, w + "NULL argument (features, actions, " + (ppo ? "advantage" : "weight") +
                                    " and target are required)");
   }
@@ -352,7 +366,7 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
   if (misaligned) return fail(WAB_E_INVALID, w + "float arrays must be 4-byte aligned");
   DeviceGuard guard(p->device);
   // wab_policy_bwd_kernel's dynamic LDS can exceed the 64 KB default: as wab_policy_create's
-  const void* const bwd = policy_bwd_kernel(p->dims, c.mode, c.gather);
+  const void* const bwd = policy_bwd_kernel(p->dims, c.mode, c.gather, c.packed);
   HIP_TRY(raise_lds(p->device, bwd, p->lds_max));
   unsigned char* const base = static_cast<unsigned char*>(c.workspace);
   uint32_t* const bad = reinterpret_cast<uint32_t*>(base + lay.bad);
@@ -391,6 +405,8 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
   bp.old_value = ppo && c.ppo->value_clip > 0.0f ? c.old_value : nullptr;
   bp.rows = c.gather ? c.rows : nullptr;
   bp.M = c.gather ? c.M : 0;
+  bp.bits = c.packed ? c.bits : nullptr;
+  bp.P = (int32_t)wab::feature_bits_pitch((uint32_t)p->dims.F);
   bp.clip = ppo ? c.ppo->clip : 0.0f;
   bp.value_clip = ppo ? c.ppo->value_clip : 0.0f;
   bp.w = p->w;
@@ -414,6 +430,8 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
   wp.features = c.features;
   wp.rows = bp.rows;
   wp.M = bp.M;
+  wp.bits = bp.bits;
+  wp.P = bp.P;
   wp.ws = ws;
   wp.part = part;
   wp.slab = slab;
@@ -429,7 +447,7 @@ int policy_grad_run(wab_policy* p, const GradCall& c) {
     wp.n_blocks = (int32_t)blocks;
     wp.first = row0 == 0 ? 1 : 0;
     void* wargs[] = {&wp};
-    (void)hipLaunchKernel(policy_wgrad_kernel(c.gather), dim3((unsigned)g.n_tasks + 1u, (unsigned)g.slabs), dim3(64),
+    (void)hipLaunchKernel(policy_wgrad_kernel(c.gather, c.packed), dim3((unsigned)g.n_tasks + 1u, (unsigned)g.slabs), dim3(64),
                           wargs, 0, st);
     HIP_TRY(hipGetLastError());
   }
@@ -551,6 +569,124 @@ int wab_policy_evaluate_gather(wab_policy* p, const float* features, const int8_
                          workspace, workspace_bytes, stream);
   c.gather = true; c.rows = rows; c.M = M;
   return policy_grad_run(p, c);
+}
+
+// ---- packed feature rows (include/wab.h, WAB_HAS_PACKED_FEATURES) --------------------------
+
+namespace {
+
+// a _packed call: its _gather twin's fill with the bits in place of the features; an index is optional
+void grad_call_packed(GradCall& c, const uint32_t* bits, const int32_t* rows, int64_t M) {
+  c.packed = true; c.bits = bits;
+  c.gather = rows != nullptr; c.rows = rows; c.M = rows ? M : 0;
+}
+
+}  // namespace
+
+int wab_policy_evaluate_packed(wab_policy* p, const uint32_t* feature_bits, const int8_t* actions, int64_t N,
+                               float* logp, float* value, float* entropy, void* workspace, size_t workspace_bytes,
+                               void* stream, const int32_t* rows, int64_t M) {
+  GradCall c = grad_call("wab_policy_evaluate_packed", wab::kGradModeEval, nullptr, actions, N, logp, value, entropy,
+                         workspace, workspace_bytes, stream);
+  grad_call_packed(c, feature_bits, rows, M);
+  return policy_grad_run(p, c);
+}
+
+int wab_policy_grad_packed(wab_policy* p, const uint32_t* feature_bits, const int8_t* actions, const float* weight,
+                           const float* target, int64_t N, const wab_policy_loss* loss,
+                           const wab_policy_weights* grads_out, float loss_out[4], float* logp, float* value,
+                           float* entropy, void* workspace, size_t workspace_bytes, void* stream, const int32_t* rows,
+                           int64_t M) {
+  GradCall c = grad_call("wab_policy_grad_packed", wab::kGradModeGrad, nullptr, actions, N, logp, value, entropy,
+                         workspace, workspace_bytes, stream);
+  c.weight = weight; c.target = target; c.loss = loss; c.grads_out = grads_out; c.loss_out = loss_out;
+  grad_call_packed(c, feature_bits, rows, M);
+  return policy_grad_run(p, c);
+}
+
+int wab_policy_grad_ppo_packed(wab_policy* p, const uint32_t* feature_bits, const int8_t* actions,
+                               const float* advantage, const float* target, const float* old_logp,
+                               const float* old_value, int64_t N, const wab_policy_loss* loss,
+                               const wab_ppo_config* ppo, const wab_policy_weights* grads_out, float loss_out[4],
+                               float ppo_out[4], float* logp, float* value, float* entropy, float* ratio,
+                               void* workspace, size_t workspace_bytes, void* stream, const int32_t* rows, int64_t M) {
+  GradCall c = grad_call("wab_policy_grad_ppo_packed", wab::kGradModePpo, nullptr, actions, N, logp, value, entropy,
+                         workspace, workspace_bytes, stream);
+  c.weight = advantage; c.target = target; c.loss = loss; c.grads_out = grads_out; c.loss_out = loss_out;
+  c.old_logp = old_logp; c.old_value = old_value; c.ppo = ppo; c.ppo_out = ppo_out; c.ratio = ratio;
+  grad_call_packed(c, feature_bits, rows, M);
+  return policy_grad_run(p, c);
+}
+
+int wab_feature_bits_pitch(int32_t in_features) {
+  g_err.clear();
+  if (in_features < 1 || in_features > (1 << 20))
+    return fail(WAB_E_INVALID, "wab_feature_bits_pitch: in_features outside [1, 2^20]");
+  return (int)wab::feature_bits_pitch((uint32_t)in_features);
+}
+
+namespace {
+
+constexpr int kPackMaxF = 4096;  // the LDS kernels: 64 rows of F bits, 32 KB
+
+int features_pack_args(const char* name, const void* features, const void* bits, const void* nonbinary,
+                       int64_t n_rows, int32_t F) {
+  const std::string w = std::string(name) + ": ";
+  if (n_rows < 0) return fail(WAB_E_INVALID, w + "n_rows must be >= 0");
+  if (F < 1 || F > (1 << 20)) return fail(WAB_E_INVALID, w + "F outside [1, 2^20]");
+  if (n_rows > 0 && (!features || !bits)) return fail(WAB_E_INVALID, w + "NULL argument");
+  if ((reinterpret_cast<uintptr_t>(features) & 3u) != 0) return fail(WAB_E_INVALID, w + "features must be 4-byte aligned");
+  if (!aligned16(bits)) return fail(WAB_E_INVALID, w + "bits must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(nonbinary) & 7u) != 0) return fail(WAB_E_INVALID, w + "nonbinary must be 8-byte aligned");
+  return WAB_OK;
+}
+
+}  // namespace
+
+int wab_features_pack(const float* features, int64_t n_rows, int32_t F, uint32_t* bits, uint64_t* nonbinary,
+                      void* stream) {
+  g_err.clear();
+  if (int rc = features_pack_args("wab_features_pack", features, bits, nonbinary, n_rows, F)) return rc;
+  if (n_rows == 0) return WAB_OK;
+  wab::PackParams pp = {};
+  pp.F = F;
+  pp.P = (int32_t)wab::feature_bits_pitch((uint32_t)F);
+  pp.n_rows = n_rows;
+  pp.features = features;
+  pp.bits = bits;
+  pp.nonbinary = reinterpret_cast<unsigned long long*>(nonbinary);
+  hipStream_t st = (hipStream_t)stream;
+  // (a group's 64 rows start 16-byte aligned where the array does: 64 F floats)
+  if (F <= kPackMaxF && aligned16(features)) {
+    const size_t lds = ((((size_t)64 * (size_t)F + 31u) >> 5) + 1u) * 4u;
+    hipLaunchKernelGGL(wab::wab_pack_rows_kernel, dim3((unsigned)((n_rows + 63) / 64)), dim3(256), lds, st, pp);
+  } else {
+    hipLaunchKernelGGL(wab::wab_pack_wave_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, pp);
+  }
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+int wab_features_unpack(const uint32_t* bits, int64_t n_rows, int32_t F, float* features, void* stream) {
+  g_err.clear();
+  if (int rc = features_pack_args("wab_features_unpack", features, bits, nullptr, n_rows, F)) return rc;
+  if (n_rows == 0) return WAB_OK;
+  wab::PackParams pp = {};
+  pp.F = F;
+  pp.P = (int32_t)wab::feature_bits_pitch((uint32_t)F);
+  pp.n_rows = n_rows;
+  pp.features_out = features;
+  pp.bits = const_cast<uint32_t*>(bits);
+  hipStream_t st = (hipStream_t)stream;
+  if (F <= kPackMaxF && aligned16(features)) {
+    hipLaunchKernelGGL(wab::wab_unpack_rows_kernel, dim3((unsigned)((n_rows + 63) / 64)), dim3(256),
+                       (size_t)64 * (size_t)pp.P * 4u, st, pp);
+  } else {
+    const int64_t blocks = std::min<int64_t>((n_rows * (int64_t)F + 255) / 256, 1 << 20);
+    hipLaunchKernelGGL(wab::wab_unpack_elem_kernel, dim3((unsigned)blocks), dim3(256), 0, st, pp);
+  }
+  HIP_TRY(hipGetLastError());
+  return WAB_OK;
 }
 
 int wab_policy_grad_bad_rows(const wab_policy* p, const void* workspace, void* stream, uint64_t* out) {
@@ -698,34 +834,50 @@ int wab_rollout_policy_fused(const wab_handle* h, const wab_policy* p) {
   return roll_policy_plan(h, p, 1, false, nullptr, &g_err) ? 1 : 0;
 }
 
-int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int32_t T, const wab_obs* obs_seq,
-                       int8_t* actions, float* value, float* probs, float* reward, uint8_t* done, float* features,
-                       float* features_last, double gamma, const float* bootstrap, float* returns, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// wab_rollout_policy (features: [T][B][F] or null) and wab_rollout_policy_packed (packed: bits
+// [T][B][P] in place of features, which is null)
+int rollout_policy_run(const char* name, bool packed, wab_handle* h, wab_policy* p, const float* features0, int32_t T,
+                       const wab_obs* obs_seq, int8_t* actions, float* value, float* probs, float* reward,
+                       uint8_t* done, float* features, uint32_t* bits, float* features_last, double gamma,
+                       const float* bootstrap, float* returns, void* stream) {
   g_err.clear();
-  if (!h || !p) return fail(WAB_E_INVALID, "wab_rollout_policy: NULL argument");
-  if (T < 0) return fail(WAB_E_INVALID, "wab_rollout_policy: T must be >= 0");
+  const std::string nm = std::string(name);
+  if (!h || !p) return fail(WAB_E_INVALID, nm + ": NULL argument");
+  if (packed && !bits) return fail(WAB_E_INVALID, nm + ": NULL argument (feature_bits is required)");
+  if (packed && !aligned16(bits)) return fail(WAB_E_INVALID, nm + ": feature_bits must be 16-byte aligned");
+  if (T < 0) return fail(WAB_E_INVALID, nm + ": T must be >= 0");
   if (!features0 || !actions || !reward || !done || !features_last || !obs_seq || !obs_seq->food_turns ||
       !obs_seq->role || !obs_seq->status)
-    return fail(WAB_E_INVALID, "wab_rollout_policy: NULL argument (features0, actions, reward, done, features_last "
+    return fail(WAB_E_INVALID, nm + ": NULL argument (features0, actions, reward, done, features_last "
                                "and the scalars of obs_seq are required)");
-  if (int rc = check_pair(h, p, "wab_rollout_policy", PAIR_RUNS | PAIR_FEATURES)) return rc;
+  if (int rc = check_pair(h, p, name, PAIR_RUNS | PAIR_FEATURES)) return rc;
   const int F = p->dims.F;
   const auto misaligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3u) != 0; };
   if (misaligned4(features0) || (probs && misaligned4(probs)) || (value && misaligned4(value)))
-    return fail(WAB_E_INVALID, "wab_rollout_policy: features0, probs and value must be 4-byte aligned");
+    return fail(WAB_E_INVALID, nm + ": features0, probs and value must be 4-byte aligned");
   if (!aligned16(features_last) || (features && !aligned16(features)))
-    return fail(WAB_E_INVALID, "wab_rollout_policy: features and features_last must be 16-byte aligned");
+    return fail(WAB_E_INVALID, nm + ": features and features_last must be 16-byte aligned");
   if (obs_seq->planes && !aligned16(obs_seq->planes))
-    return fail(WAB_E_INVALID, "wab_rollout_policy: planes must be 16-byte aligned");
+    return fail(WAB_E_INVALID, nm + ": planes must be 16-byte aligned");
   const int64_t B = h->p.B;
   const size_t OB = (size_t)h->p.OB, BF = (size_t)B * (size_t)F;
   if (T == 0 || B == 0) return WAB_OK;
+  // packed: slice 0 is the pack of features0, queued in front of everything else
+  const size_t BP = (size_t)B * (size_t)wab::feature_bits_pitch((uint32_t)F);
+  if (packed) {
+    DeviceGuard guard(h->device);
+    if (int rc = wab_features_pack(features0, B, F, bits, nullptr, stream)) return rc;
+  }
   const bool fused_returns = returns && T <= wab::kMaxFusedReturnSteps;
   wab::RollPolicy rp;
   bool fused = roll_policy_plan(h, p, T, fused_returns, &rp, nullptr);
   if (obs_seq->planes && ((size_t)B * OB) % 16u != 0) fused = false;  // (the launch's 16-byte obs stores)
   if (returns && !(fused && fused_returns) && h->rewards.n < 0)  // (checked before anything runs)
-    return fail(WAB_E_INVALID, "wab_rollout_policy: returns of this segment need the exact-reward scan, and two of "
+    return fail(WAB_E_INVALID, nm + ": returns of this segment need the exact-reward scan, and two of "
                                "the options' rewards round to the same float32 (pass returns = NULL)");
   if (fused) {
     // one launch: each workgroup runs its 64 envs through the T steps, the policy between them
@@ -742,6 +894,7 @@ int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int
     }
     rp.features0 = features0;
     rp.features = features;
+    rp.feature_bits = packed ? bits : nullptr;
     rp.features_last = features_last;
     rp.actions = actions;
     rp.probs = probs;
@@ -751,7 +904,7 @@ int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int
     q.pol = rp;
     DeviceGuard guard(h->device);
     ++h->rollout_launches;
-    launch_params(small_kernel(h, true, true, true), (unsigned)h->n_blocks, rp.reg_a + rp.lds.total, (hipStream_t)stream, q);
+    launch_params(small_kernel(h, true, true, true, packed), (unsigned)h->n_blocks, rp.reg_a + rp.lds.total, (hipStream_t)stream, q);
     HIP_TRY(hipGetLastError());
     if (fused_returns || !returns) return WAB_OK;
     return wab_discounted_returns_exact(h, reward, done, T, B, gamma, bootstrap, returns, stream);
@@ -763,7 +916,7 @@ int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int
   float* bounce = nullptr;
   if (!direct && T > 1) {
     bounce = bounce_rows(h, BF);
-    if (!bounce) return fail(WAB_E_NOMEM, "wab_rollout_policy: hipMalloc");
+    if (!bounce) return fail(WAB_E_NOMEM, nm + ": hipMalloc");
   }
   const size_t bounce_stride = (BF + 3u) & ~(size_t)3u;
   if (features && features != features0) {
@@ -777,7 +930,7 @@ int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int
                             value ? value + tb : nullptr, stream);
     if (rc != WAB_OK) return rc;
     ObsSlice s;
-    if ((rc = obs_slice(h, obs_seq, t, "wab_rollout_policy", &s)) != WAB_OK) return rc;
+    if ((rc = obs_slice(h, obs_seq, t, name, &s)) != WAB_OK) return rc;
     float* slice = features && t + 1 < T ? features + (size_t)(t + 1) * BF : nullptr;
     float* dst = t + 1 == T ? features_last : direct ? slice : bounce + (size_t)(t & 1) * bounce_stride;
     rc = wab_step_features(h, actions + tb, &s.o, reward + tb, done + tb, dst, stream);
@@ -787,10 +940,33 @@ int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int
       DeviceGuard guard(h->device);
       HIP_TRY(hipMemcpyAsync(slice, dst, BF * 4u, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
+    if (packed && t + 1 < T) {
+      DeviceGuard guard(h->device);
+      if ((rc = wab_features_pack(dst, B, F, bits + (size_t)(t + 1) * BP, nullptr, stream)) != WAB_OK) return rc;
+    }
     cur = dst;
   }
   if (!returns) return WAB_OK;
   return wab_discounted_returns_exact(h, reward, done, T, B, gamma, bootstrap, returns, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int wab_rollout_policy(wab_handle* h, wab_policy* p, const float* features0, int32_t T, const wab_obs* obs_seq,
+                       int8_t* actions, float* value, float* probs, float* reward, uint8_t* done, float* features,
+                       float* features_last, double gamma, const float* bootstrap, float* returns, void* stream) {
+  return rollout_policy_run("wab_rollout_policy", false, h, p, features0, T, obs_seq, actions, value, probs, reward,
+                            done, features, nullptr, features_last, gamma, bootstrap, returns, stream);
+}
+
+int wab_rollout_policy_packed(wab_handle* h, wab_policy* p, const float* features0, int32_t T, const wab_obs* obs_seq,
+                              int8_t* actions, float* value, float* probs, float* reward, uint8_t* done,
+                              uint32_t* feature_bits, float* features_last, double gamma, const float* bootstrap,
+                              float* returns, void* stream) {
+  return rollout_policy_run("wab_rollout_policy_packed", true, h, p, features0, T, obs_seq, actions, value, probs,
+                            reward, done, nullptr, feature_bits, features_last, gamma, bootstrap, returns, stream);
 }
 
 int wab_debug_policy_plan(const wab_policy* p, int32_t out[5]) {

@@ -299,4 +299,35 @@ __device__ __forceinline__ void store_rows_skip_views(const uint32_t* ob, float*
     out[q] = ((ob[q >> 5] >> (q & 31u)) & 1u) ? 1.0f : 0.0f;
 }
 
+// ---- packed rows (include/wab.h, WAB_HAS_PACKED_FEATURES).  The feature bits `ob` are an unpadded
+// stream (bit e F + k); a packed row is P dwords, feature k bit k & 31 of dword k >> 5, the bits
+// from F on zero.  Each dword of a row is a 64-bit funnel shift out of the stream (the word after
+// the stream's last is its slack: what is read of it is masked), 16 bytes per thread and store:
+// at F = 449 one uint4 per thread of a 256-thread group, 4 KB contiguous per 64 rows.
+template <bool NT = false>
+__device__ __forceinline__ void store_packed_rows(const uint32_t* ob, uint32_t* out, uint32_t n_rows, uint32_t F,
+                                                  uint32_t P, int tid, int nthreads) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const uint32_t P4 = P >> 2;
+  for (uint32_t u = (uint32_t)tid; u < n_rows * P4; u += (uint32_t)nthreads) {
+    const uint32_t e = u / P4, j0 = 4u * (u - e * P4);
+    uint32_t d[4];
+#pragma unroll
+    for (uint32_t c = 0; c < 4u; ++c) {
+      const uint32_t k = 32u * (j0 + c);
+      d[c] = 0u;
+      if (k < F) {
+        const uint32_t at = e * F + k;
+        const uint64_t ww = (uint64_t)ob[at >> 5] | ((uint64_t)ob[(at >> 5) + 1u] << 32);
+        d[c] = (uint32_t)(ww >> (at & 31u));
+        if (F - k < 32u) d[c] &= (1u << (F - k)) - 1u;
+      }
+    }
+    const u32x4 v = {d[0], d[1], d[2], d[3]};
+    u32x4* const dst = reinterpret_cast<u32x4*>(out) + u;
+    if (NT) __builtin_nontemporal_store(v, dst);
+    else *dst = v;
+  }
+}
+
 }  // namespace wab

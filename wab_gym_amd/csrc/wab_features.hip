@@ -413,4 +413,114 @@ template __global__ void wab_returns_kernel<4, 4>(const float* __restrict__, con
 template __global__ void wab_returns_kernel<4, 8>(const float* __restrict__, const uint8_t* __restrict__, int32_t,
     int64_t, double, const float* __restrict__, float* __restrict__, RewardTable);
 
+// ------------------------------------------------------------------ packed feature rows
+// wab_features_pack / wab_features_unpack (include/wab.h, WAB_HAS_PACKED_FEATURES).  A bit is set
+// iff the float's pattern is not 0; an element whose pattern is neither 0 nor 0x3F800000 is counted.
+//
+// wab_pack_rows_kernel (F <= kPackMaxF, 16-byte aligned float rows): one 256-thread workgroup per
+// 64 rows, whose floats are one contiguous 16-byte aligned run (64 F floats):
+//   phase 1  16-byte loads, 4 floats -> 4 bits; the eight lanes of a dword OR their nibbles lane to
+//            lane and one of them stores the dword of the unpadded LDS bit-stream (no atomics)
+//   phase 2  store_packed_rows (wab_feat.h): the padded rows, 16-byte stores
+// wab_pack_wave_kernel (any F, rows 4-byte aligned): one wave per row, 64 floats per ballot.
+__device__ __forceinline__ uint32_t pack_wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void wab_pack_rows_kernel(PackParams p) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t r0 = (int64_t)blockIdx.x * 64;
+  const uint32_t n = (uint32_t)min((int64_t)64, p.n_rows - r0);
+  const uint32_t F = (uint32_t)p.F, nf = n * F, nq = (nf + 3u) >> 2;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(p.features) + (size_t)r0 * F;
+  uint32_t nonbin = 0;
+  for (uint32_t u0 = 0; u0 < nq; u0 += 256u) {  // (uniform: every lane takes part in the exchange)
+    const uint32_t q = 4u * (u0 + (uint32_t)tid);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (q + 4u <= nf) {
+      const uint4 v = *reinterpret_cast<const uint4*>(src + q);
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+      for (uint32_t k = 0; k < 4u && q + k < nf; ++k) w[k] = src[q + k];
+    }
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      m |= (w[k] != 0u ? 1u : 0u) << k;
+      nonbin += (w[k] != 0u && w[k] != 0x3F800000u) ? 1u : 0u;
+    }
+    m <<= 4u * ((uint32_t)lane & 7u);
+    m |= __shfl_xor(m, 1, 64);
+    m |= __shfl_xor(m, 2, 64);
+    m |= __shfl_xor(m, 4, 64);
+    if ((lane & 7) == 0 && q < nf) lds[q >> 5] = m;
+  }
+  __syncthreads();
+  store_packed_rows(lds, p.bits + (size_t)r0 * (size_t)p.P, n, F, (uint32_t)p.P, tid, 256);
+  nonbin = pack_wave_sum(nonbin);
+  if (lane == 0 && p.nonbinary && nonbin) atomicAdd(p.nonbinary, (unsigned long long)nonbin);
+}
+
+__global__ __launch_bounds__(256) void wab_pack_wave_kernel(PackParams p) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t row = (int64_t)blockIdx.x * 4 + (int64_t)(threadIdx.x >> 6);
+  if (row >= p.n_rows) return;  // (the whole wave)
+  const uint32_t F = (uint32_t)p.F;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(p.features) + (size_t)row * F;
+  uint32_t* dst = p.bits + (size_t)row * (size_t)p.P;
+  uint32_t nonbin = 0;
+  for (uint32_t k0 = 0; k0 < 32u * (uint32_t)p.P; k0 += 64u) {
+    const uint32_t k = k0 + (uint32_t)lane;
+    const uint32_t w = k < F ? src[k] : 0u;
+    nonbin += (w != 0u && w != 0x3F800000u) ? 1u : 0u;
+    const unsigned long long b = __ballot(w != 0u);
+    if (lane == 0) *reinterpret_cast<uint2*>(dst + (k0 >> 5)) = make_uint2((uint32_t)b, (uint32_t)(b >> 32));
+  }
+  nonbin = pack_wave_sum(nonbin);
+  if (lane == 0 && p.nonbinary && nonbin) atomicAdd(p.nonbinary, (unsigned long long)nonbin);
+}
+
+// wab_unpack_rows_kernel (F <= kPackMaxF, 16-byte aligned float rows): 64 packed rows staged in LDS
+// by 16-byte loads, then 16-byte float stores over the group's contiguous floats.
+// wab_unpack_elem_kernel: one element per thread and pass.
+__global__ __launch_bounds__(256) void wab_unpack_rows_kernel(PackParams p) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  const int tid = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * 64;
+  const uint32_t n = (uint32_t)min((int64_t)64, p.n_rows - r0);
+  const uint32_t F = (uint32_t)p.F, P = (uint32_t)p.P, nf = n * F;
+  const uint4* src = reinterpret_cast<const uint4*>(p.bits + (size_t)r0 * P);
+  for (uint32_t u = (uint32_t)tid; u < n * (P >> 2); u += 256u) reinterpret_cast<uint4*>(lds)[u] = src[u];
+  __syncthreads();
+  float* dst = p.features_out + (size_t)r0 * F;
+  for (uint32_t q = 4u * (uint32_t)tid; q < nf; q += 1024u) {
+    uint32_t e = q / F, k = q - e * F;
+    float f[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      // (an element past the group's last reads row n - 1's pad or the next row staged: unused)
+      f[c] = ((lds[(e < n ? e : n - 1u) * P + (k >> 5)] >> (k & 31u)) & 1u) ? 1.0f : 0.0f;
+      if (++k == F) {
+        k = 0u;
+        ++e;
+      }
+    }
+    if (q + 4u <= nf) *reinterpret_cast<float4*>(dst + q) = make_float4(f[0], f[1], f[2], f[3]);
+    else
+      for (uint32_t c = 0; q + c < nf; ++c) dst[q + c] = f[c];
+  }
+}
+
+__global__ __launch_bounds__(256) void wab_unpack_elem_kernel(PackParams p) {
+  const int64_t total = p.n_rows * (int64_t)p.F;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t e = i / p.F;
+    const uint32_t k = (uint32_t)(i - e * p.F);
+    p.features_out[i] = ((p.bits[(size_t)e * (size_t)p.P + (k >> 5)] >> (k & 31u)) & 1u) ? 1.0f : 0.0f;
+  }
+}
+
 }  // namespace wab

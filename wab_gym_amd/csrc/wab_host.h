@@ -101,10 +101,11 @@ inline void launch_params(const void* kernel, unsigned blocks, size_t lds, hipSt
 enum { KERNEL_BLOCK = 0, KERNEL_SMALL = 1, KERNEL_WIDE = 2 };
 
 // The small-view kernel's instance wab_step_small<slots, g11 ? 11 : 0, feat, roll, rules, policy>
-// (wab_capi.hip): the one place that names them.  rules and policy exist for 8 slots at 11x11 only.
-const void* small_kernel(int slots, bool g11, bool rules, bool feat, bool roll, bool policy);
-inline const void* small_kernel(const wab_handle* h, bool feat, bool roll, bool policy = false) {
-  return small_kernel(h->slots, h->small_g11, h->small_rules, feat, roll, policy);
+// (wab_capi.hip): the one place that names them.  rules and policy (and with it packed, the policy
+// build that stores packed rows) exist for 8 slots at 11x11 only.
+const void* small_kernel(int slots, bool g11, bool rules, bool feat, bool roll, bool policy, bool packed = false);
+inline const void* small_kernel(const wab_handle* h, bool feat, bool roll, bool policy = false, bool packed = false) {
+  return small_kernel(h->slots, h->small_g11, h->small_rules, feat, roll, policy, packed);
 }
 
 // where a step's observation, and its actions and results, go

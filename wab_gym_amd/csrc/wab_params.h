@@ -68,6 +68,8 @@ struct RollPolicy {
   float* value;             // [T][B] or null
   const uint16_t* w;        // packed bf16 image (PolicyDims::w*)
   const float* b;           // packed biases (PolicyDims::b*)
+  uint32_t* feature_bits;   // [T][B][P] (wab_rollout_policy_packed, the PACKED instances; else null): the
+                            // rows go out packed, slices 1 .. T - 1 (slice 0 is the host's wab_features_pack)
 };
 
 // the policy phase's LDS for a step layout of `base` bytes
@@ -362,6 +364,19 @@ struct FeatParams {
   float* out;                // [B][F]
 };
 
+// Packed feature rows (include/wab.h, WAB_HAS_PACKED_FEATURES): P dwords per row of F features
+__host__ __device__ inline uint32_t feature_bits_pitch(uint32_t F) { return 4u * ((F + 127u) >> 7); }
+
+// wab_features_pack / wab_features_unpack (wab_features.hip)
+struct PackParams {
+  int32_t F, P;
+  int64_t n_rows;
+  const float* features;   // pack: in; unpack: null
+  float* features_out;     // unpack: out
+  uint32_t* bits;          // [n_rows][P]: pack out, unpack in
+  unsigned long long* nonbinary;  // pack: nullable device counter, added to
+};
+
 // Snapshot records (wab_snapshot.hip, wab_snapshot_save / wab_snapshot_restore): one env's
 // state as consecutive dwords, the same whichever step kernel runs the handle:
 //   [0,4) hdr  [4,6) food  [wolf, +slots) wolf tiles  [exy, +cap) eaten tiles
@@ -431,7 +446,7 @@ struct RenderParams {
 // launches them (wab_capi*.hip) see the same signature.  Their instances are in the defining files.
 template <int MODE, int SLOTS, bool SMALL>
 __global__ void wab_kernel(Params p);  // wab_step.hip
-template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES = false, bool POLICY = false>
+template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES = false, bool POLICY = false, bool PACKED = false>
 __global__ void wab_step_small(Params p0);  // wab_step_small.hip
 template <int MODE, int SLOTS>
 __global__ void wab_step_wide(Params p0);  // wab_step_wide.hip
@@ -439,6 +454,10 @@ template <int SLOTS, int FIXW>
 __global__ void wab_rollout_wide(Params p0);
 __global__ void wab_featurize_kernel(FeatParams p);  // wab_features.hip
 __global__ void wab_featurize_small_kernel(FeatParams p);
+__global__ void wab_pack_rows_kernel(PackParams p);    // 64 rows per workgroup through LDS
+__global__ void wab_pack_wave_kernel(PackParams p);    // one wave per row, by ballot
+__global__ void wab_unpack_rows_kernel(PackParams p);
+__global__ void wab_unpack_elem_kernel(PackParams p);
 template <int VEC, int NE>
 __global__ void wab_returns_kernel(const float* __restrict__ reward, const uint8_t* __restrict__ done, int32_t T,
                                    int64_t B, double gamma, const float* __restrict__ bootstrap,

@@ -155,6 +155,8 @@ struct GradBwdParams {
                            // rows whose index is outside [0, M), which are left out in the same way
   const int32_t* rows;     // GATHER: [N], the source row of each row (null otherwise)
   int64_t M;               // GATHER: the source's rows, in [1, 2^31)
+  const uint32_t* bits;    // PACKED: the rows' features as packed bits [N][P] (GATHER: [M][P]); features null
+  int32_t P;               // PACKED: dwords per packed row (feature_bits_pitch)
 };
 
 struct GradWgradParams {
@@ -171,6 +173,8 @@ struct GradWgradParams {
   double* loss;
   const int32_t* rows;     // GATHER: as GradBwdParams'
   int64_t M;
+  const uint32_t* bits;    // PACKED: as GradBwdParams'
+  int32_t P;
 };
 
 struct GradReduceParams {
@@ -188,9 +192,10 @@ struct GradReduceParams {
 // the kernels (wab_policy_grad.hip), launched from wab_capi_policy.hip
 __global__ void wab_policy_grad_pack(GradPackParams p);
 // (GATHER: the rows are taken through GradBwdParams::rows, wab_policy_*_gather)
-template <bool TWO, int MODE = kGradModeGrad, bool GATHER = false>
+// (PACKED: the features are GradBwdParams::bits, wab_policy_*_packed)
+template <bool TWO, int MODE = kGradModeGrad, bool GATHER = false, bool PACKED = false>
 __global__ void wab_policy_bwd_kernel(GradBwdParams p);
-template <bool GATHER = false>
+template <bool GATHER = false, bool PACKED = false>
 __global__ void wab_policy_wgrad_kernel(GradWgradParams p);
 __global__ void wab_policy_grad_reduce_kernel(GradReduceParams p);
 

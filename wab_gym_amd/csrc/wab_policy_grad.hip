@@ -152,7 +152,47 @@ __device__ __forceinline__ size_t grad_lane_u64(size_t v, int j) {
 // GATHER: row i of the call is row rows[i] of the source (features and the head's per-row inputs);
 // the blocks, the workspace, the sums and the row outputs are those of rows 0 .. N - 1 all the
 // same, so the results are the bits of the plain instance on gathered copies.
-template <bool TWO, int MODE, bool GATHER>
+// Columns [k0, k0 + kn) of the block's 128 rows as bf16 0x0000 / 0x3F80 into x[128][pitch] from
+// packed rows (include/wab.h, WAB_HAS_PACKED_FEATURES; PACKED instances).  k0 is a multiple of 16
+// and kn at most 256, 240 where k0 is in the middle of a dword, so the chunk lies within the eight
+// dwords from k0 >> 5: thread t takes four of them (half t & 1) of row t >> 1, one 16-byte load
+// where they start on a 16-byte boundary of the row, and expands each byte inside the chunk to one
+// 16-byte LDS store.  `row` is the thread's source row (null: past the batch, stored as zeros);
+// columns from F on are zero whatever the row's pad bits hold.
+__device__ __forceinline__ void grad_stage_packed(const uint32_t* __restrict__ row, int F, int P, int k0, int kn,
+                                                  uint16_t* x, int pitch, int tid) {
+  const int e = tid >> 1;
+  const int dw = (k0 >> 5) + 4 * (tid & 1);
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  if (row) {
+    if ((dw & 3) == 0 && dw + 4 <= P) {
+      const uint4 v = *reinterpret_cast<const uint4*>(row + dw);
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (dw + i < P) w[i] = row[dw + i];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int k = 32 * (dw + i) + 8 * b;
+      if (k < k0 || k >= k0 + kn) continue;
+      uint32_t bits = (w[i] >> (8 * b)) & 0xFFu;
+      bits = k >= F ? 0u : (F - k >= 8 ? bits : bits & ((1u << (F - k)) - 1u));
+      uint4 v;  // bf16 1.0 = 0x3F80
+      v.x = ((bits & 1u) ? 0x3F80u : 0u) | ((bits & 2u) ? 0x3F800000u : 0u);
+      v.y = ((bits & 4u) ? 0x3F80u : 0u) | ((bits & 8u) ? 0x3F800000u : 0u);
+      v.z = ((bits & 16u) ? 0x3F80u : 0u) | ((bits & 32u) ? 0x3F800000u : 0u);
+      v.w = ((bits & 64u) ? 0x3F80u : 0u) | ((bits & 128u) ? 0x3F800000u : 0u);
+      *reinterpret_cast<uint4*>(x + (size_t)e * (size_t)pitch + (size_t)(k - k0)) = v;
+    }
+  }
+}
+
+template <bool TWO, int MODE, bool GATHER, bool PACKED>
 __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBwdParams p) {
   constexpr bool PPO = MODE == kGradModePpo, EVAL = MODE == kGradModeEval;
   constexpr int TERMS = PPO ? kGradPpoTerms : kGradLossTerms;
@@ -178,16 +218,29 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_bwd_kernel(GradBw
   // batch, the batch's last) starts in the source, one index load per row and launch; the staging
   // reads it lane to scalar, once per 16 loads
   [[maybe_unused]] size_t src_off = 0;
-  if constexpr (GATHER) {
+  if constexpr (GATHER && !PACKED) {
     const int e = wave + 4 * r;
     src_off = (size_t)grad_src_row(p.rows[env0 + (e < n_env ? e : n_env - 1)], p.M) * (size_t)d.F;
+  }
+  // PACKED: thread t stages row t >> 1 of the block (grad_stage_packed): its packed source row, one
+  // index load per thread and launch
+  [[maybe_unused]] const uint32_t* bits_row = nullptr;
+  if constexpr (PACKED) {
+    const int e = (int)(threadIdx.x >> 1);
+    if (e < n_env) {
+      int64_t src = env0 + e;
+      if constexpr (GATHER) src = grad_src_row(p.rows[src], p.M);
+      bits_row = p.bits + (size_t)src * (size_t)p.P;
+    }
   }
 
   // ---- layer 1: chunks of KC input columns through region A -> X1 (region B)
   pol_layer1<4, TWO>(
       d, L, wimg, regA, wave, lane,
       [&](int k0, int kn) {
-        if constexpr (GATHER)
+        if constexpr (PACKED)
+          grad_stage_packed(bits_row, d.F, p.P, k0, kn, regA, L.pitch_in, (int)threadIdx.x);
+        else if constexpr (GATHER)
           pol_stage_rows<kGradRows>(p.features, d.F, n_env, k0, kn, regA, L.pitch_in, wave, lane,
                                     [&](int j, int) { return grad_lane_u64(src_off, j); },
                                     [](int, int, float, bool) {});
@@ -405,11 +458,27 @@ template __global__ void wab_policy_bwd_kernel<false, kGradModePpo, true>(GradBw
 template __global__ void wab_policy_bwd_kernel<true, kGradModePpo, true>(GradBwdParams p);
 template __global__ void wab_policy_bwd_kernel<false, kGradModeEval, true>(GradBwdParams p);
 template __global__ void wab_policy_bwd_kernel<true, kGradModeEval, true>(GradBwdParams p);
+// (PACKED: the rows' features are packed bits, wab_policy_*_packed)
+template __global__ void wab_policy_bwd_kernel<false, kGradModeGrad, false, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModeGrad, false, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModePpo, false, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModePpo, false, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModeEval, false, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModeEval, false, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModeGrad, true, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModeGrad, true, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModePpo, true, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModePpo, true, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<false, kGradModeEval, true, true>(GradBwdParams p);
+template __global__ void wab_policy_bwd_kernel<true, kGradModeEval, true, true>(GradBwdParams p);
 
 // ------------------------------------------------------------------------ dW, db
 // the slab's row blocks of this chunk, ascending: acc[i] += D_l[rows, tile i]^T . [X_{l-1} | 1][rows, tile kt]
 // (GATHER, on the FEAT path alone: a lane's eight feature rows are the source rows of its eight rows)
-template <bool FEAT, bool GATHER>
+// (PACKED, on the FEAT path alone: lane r of tile kt takes bit r of dword kt of each of its eight
+// packed rows, one dword load per row at the same address in the 32 lanes, and builds the operand
+// words the float loads round to: 0x3F80 where the bit is set)
+template <bool FEAT, bool GATHER, bool PACKED = false>
 __device__ __forceinline__ void grad_wgrad_blocks(const GradWgradParams& p, int K, int n_d, int u_d, int u_x, int grp,
                                                   int kt, int tiles, int slab, int lane,
                                                   pol_f32x16 (&acc)[kGradTiles]) {
@@ -451,7 +520,22 @@ __device__ __forceinline__ void grad_wgrad_blocks(const GradWgradParams& p, int 
     for (int ks = 0; ks < kGradRows / 16; ++ks) {
       const size_t rc = rb + (size_t)(16 * ks + 8 * h);
       uint4 bv;
-      if (FEAT) {
+      if constexpr (FEAT && PACKED) {
+        // (a tile past the row's dwords, the ones column's at F a multiple of 128, is masked below)
+        const uint32_t* const bcol = p.bits + (size_t)(kt < p.P ? kt : p.P - 1);
+        uint32_t o[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          int64_t row = p.row0 + (int64_t)rc + j;
+          row = row < p.N ? row : p.N - 1;  // (rows past N have D = 0)
+          if constexpr (GATHER) row = __shfl(ks < 4 ? src_lo : src_hi, (16 * ks + 8 * h + j) & 63, 64);
+          o[j] = ((bcol[(size_t)row * (size_t)p.P] >> r) & 1u) ? 0x3F80u : 0u;
+        }
+        bv.x = o[0] | (o[1] << 16);
+        bv.y = o[2] | (o[3] << 16);
+        bv.z = o[4] | (o[5] << 16);
+        bv.w = o[6] | (o[7] << 16);
+      } else if (FEAT) {
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -481,7 +565,7 @@ __device__ __forceinline__ void grad_wgrad_blocks(const GradWgradParams& p, int 
   }
 }
 
-template <bool GATHER>
+template <bool GATHER, bool PACKED>
 __global__ __launch_bounds__(64) void wab_policy_wgrad_kernel(GradWgradParams p) {
   const GradPlan& g = p.g;
   const int lane = (int)threadIdx.x, task = (int)blockIdx.x, slab = (int)blockIdx.y;
@@ -518,7 +602,7 @@ __global__ __launch_bounds__(64) void wab_policy_wgrad_kernel(GradWgradParams p)
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[i][q] = sl[(size_t)((i * 16 + q) * 64)];
   }
-  if (layer == 1) grad_wgrad_blocks<true, GATHER>(p, K, n_d, u_d, u_x, grp, kt, tiles, slab, lane, acc);
+  if (layer == 1) grad_wgrad_blocks<true, GATHER, PACKED>(p, K, n_d, u_d, u_x, grp, kt, tiles, slab, lane, acc);
   else grad_wgrad_blocks<false, false>(p, K, n_d, u_d, u_x, grp, kt, tiles, slab, lane, acc);
 #pragma unroll
   for (int i = 0; i < kGradTiles; ++i)
@@ -528,6 +612,8 @@ __global__ __launch_bounds__(64) void wab_policy_wgrad_kernel(GradWgradParams p)
 
 template __global__ void wab_policy_wgrad_kernel<false>(GradWgradParams p);
 template __global__ void wab_policy_wgrad_kernel<true>(GradWgradParams p);
+template __global__ void wab_policy_wgrad_kernel<false, true>(GradWgradParams p);
+template __global__ void wab_policy_wgrad_kernel<true, true>(GradWgradParams p);
 
 // ------------------------------------------------------------------------ slabs -> gradients
 __global__ __launch_bounds__(256) void wab_policy_grad_reduce_kernel(GradReduceParams p) {

@@ -1548,10 +1548,12 @@ __device__ __forceinline__ void store_obs(const Params& p, uint32_t* stream, int
 // from the rendered bit-stream (after B2, or B3) and the scalars each env's writer handed over:
 // W0 the wolf plane, W1 the bush plane, W2 the scalars and view mask, one more barrier, then
 // all 256 threads expand the feature bits to float32 (the featurizer's phases 2 and 3).
-// POLICY (wab_rollout_policy): the rows go to `rows` (that step's [B][F] slice), nowhere if null.
-template <bool ROLL = false, bool POLICY = false>
+// POLICY (wab_rollout_policy): the rows go to `rows` (that step's [B][F] slice), nowhere if null,
+// PACKED (wab_rollout_policy_packed, its own instances: the float build keeps its instruction text)
+// also as packed bits to `packed` (that step's [B][P] slice), if not null.
+template <bool ROLL = false, bool POLICY = false, bool PACKED = false>
 __device__ __forceinline__ void step_features(const Params& p, const SmallLayout& L, uint32_t* lds, int wave,
-                                              int lane, int t = 0, float* rows = nullptr) {
+                                              int lane, int t = 0, float* rows = nullptr, uint32_t* packed = nullptr) {
   const int md = p.W / 2 + p.H / 2 + 1;
   const uint32_t F = (uint32_t)pragmatic_dim(md, p.turns_empty), WH = (uint32_t)p.WH;
   const int64_t g0 = (int64_t)blockIdx.x * 64;
@@ -1611,6 +1613,12 @@ __device__ __forceinline__ void step_features(const Params& p, const SmallLayout
   constexpr bool NT = ROLL;
   if constexpr (POLICY) {
     if (rows) store_feature_bits<NT>(ob, rows + (size_t)g0 * F, n_active * F, (int)threadIdx.x, 256);
+    if constexpr (PACKED) {
+      if (packed) {  // (null at the last step alone)
+        const uint32_t P = feature_bits_pitch(F);
+        store_packed_rows<NT>(ob, packed + (size_t)g0 * P, n_active, F, P, (int)threadIdx.x, 256);
+      }
+    }
     return;
   }
   if (p.restrict_view || ROLL) store_feature_bits<NT>(ob, p.features + (size_t)g0 * F, n_active * F, (int)threadIdx.x, 256);
@@ -1816,7 +1824,7 @@ __device__ __forceinline__ void roll_apply(Params& p, const RollSlices& r) {
 // POLICY (wab_rollout_policy; with FEAT and ROLL): the device policy chooses each step's actions
 // inside the launch (roll_policy); its fragments and accumulators sit next to the carried state,
 // so these instances take two waves per SIMD's registers
-template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES, bool POLICY>
+template <int SLOTS, int G, bool FEAT, bool ROLL, bool RULES, bool POLICY, bool PACKED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(POLICY ? 2 : ROLL ? 4 : 1))) void wab_step_small(Params p0) {
   static_assert(!POLICY || (FEAT && ROLL), "the policy build is a build of wab_rollout_features' kernel");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -1913,10 +1921,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(POLICY ? 2 
         step_slice(p, t);                                                                    \
       }                                                                                      \
       float* rows = nullptr;  /* POLICY: where this step's feature rows go, if anywhere */    \
+      uint32_t* packed = nullptr;  /* ... and its packed rows (wab_rollout_policy_packed) */  \
       if constexpr (POLICY) {                                                                \
         p.features = p.pol.features_last;  /* (non-null: the featurizer is on) */            \
         rows = t == T - 1 ? p.pol.features_last                                              \
                : p.pol.features ? p.pol.features + (int64_t)(t + 1) * p.B * p.pol.d.F : nullptr; \
+        if constexpr (PACKED)                                                                \
+          if (t < T - 1)                                                                     \
+          packed = p.pol.feature_bits + (int64_t)(t + 1) * p.B * feature_bits_pitch((uint32_t)p.pol.d.F); \
       }                                                                                      \
       const SmallLayout L0 = small_layout(p);                                                \
       SmallLayout L = L0;                                                                    \
@@ -1932,7 +1944,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(POLICY ? 2 
       } else {                                                                               \
         __VA_ARGS__;                                                                         \
       }                                                                                      \
-      if (FEAT) step_features<true, POLICY>(p, L, lds, wave, lane, t, rows);  /* this step's rows */ \
+      if (FEAT) step_features<true, POLICY, PACKED>(p, L, lds, wave, lane, t, rows, packed);  /* this step's rows */ \
       if constexpr (POLICY) {  /* the next step's actions, keyed by the envs' state after this one */ \
         if (t < T - 1) {                                                                     \
           const uint4 ch = carry_hdr(c);                                                     \
@@ -1984,6 +1996,7 @@ template __global__ void wab_step_small<8, 11, true, false, true>(Params);
 template __global__ void wab_step_small<8, 11, false, true, true>(Params);
 template __global__ void wab_step_small<8, 11, true, true, true>(Params);
 template __global__ void wab_step_small<8, 11, true, true, true, true>(Params);  // wab_rollout_policy
+template __global__ void wab_step_small<8, 11, true, true, true, true, true>(Params);  // wab_rollout_policy_packed
 #endif
 #ifndef WAB_ONLY_WAVE  // (tools/isa_count.py reads the SLOTS = 8, G = 11 instances only)
 template __global__ void wab_step_small<8, 0, false, false, false>(Params);
@@ -1996,6 +2009,7 @@ template __global__ void wab_step_small<8, 11, true, false, false>(Params);
 template __global__ void wab_step_small<8, 11, false, true, false>(Params);
 template __global__ void wab_step_small<8, 11, true, true, false>(Params);
 template __global__ void wab_step_small<8, 11, true, true, false, true>(Params);  // wab_rollout_policy
+template __global__ void wab_step_small<8, 11, true, true, false, true, true>(Params);  // wab_rollout_policy_packed
 #ifndef WAB_ONLY_WAVE
 template __global__ void wab_step_small<16, 0, false, false, false>(Params);
 template __global__ void wab_step_small<16, 0, true, false, false>(Params);

@@ -70,14 +70,22 @@ def shape_of(state_dict):
 
 
 def check_rows(shape, features, **rows):
-    """features [N, F] or [T, B, F] float32 and the named per-row tensors (actions int8, every other
-    float32) of the leading shape, all contiguous and on the features' device: returns N."""
+    """features [N, F] or [T, B, F] float32, or packed (wab_gym_amd.features) int32 [N, P] or
+    [T, B, P], and the named per-row tensors (actions int8, every other float32) of the leading
+    shape, all contiguous and on the features' device: returns N."""
     import torch
 
     F = shape[0]
-    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() not in (2, 3) \
+    if isinstance(features, torch.Tensor) and features.dtype == torch.int32:
+        from .features import check_bits
+
+        check_bits(features, F)
+        if features.dim() not in (2, 3):
+            raise ValueError("packed features must have shape [N, P] or [T, B, P], not %s" % (tuple(features.shape),))
+    elif not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.dim() not in (2, 3) \
             or features.shape[-1] != F or not features.is_contiguous():
-        raise ValueError("features must be a contiguous float32 tensor of shape [N, %d] or [T, B, %d]" % (F, F))
+        raise ValueError("features must be a contiguous float32 tensor of shape [N, %d] or [T, B, %d] (or packed "
+                         "int32 rows)" % (F, F))
     lead = tuple(features.shape[:-1])
     for name, x in rows.items():
         dt = torch.int8 if name == "actions" else torch.float32
@@ -336,7 +344,9 @@ class DevicePolicy:
                       value_loss="smooth_l1", reduction="sum", into=None, accumulate=False, return_rows=False,
                       chunk_rows=0, scale=None, rows=None):
         """finish_episode()'s loss and loss.backward() (actor_critic.py:148-165) on the env's stream,
-        no host synchronisation: features [N, F] or [T, B, F] (viewed, not copied), actions int8,
+        no host synchronisation: features [N, F] or [T, B, F] (viewed, not copied; or packed rows,
+        int32 [N, P] or [T, B, P] of wab_gym_amd.features: the dtype selects wab_policy_grad_packed,
+        with the same bits in every result), actions int8,
         weight (the reference's R - value.item(), or an advantage; a constant) and target float32
         of the leading shape.  loss = scale (loss_policy + value_coef loss_value - entropy_coef
         entropy), scale 1 ("sum") or 1 / N ("mean") unless `scale` gives it; the three parts are
@@ -393,7 +403,11 @@ class DevicePolicy:
             if ppo is not None:
                 mid.append(sums[4:].data_ptr())
         bufs = [None if k is None else t.empty(n, dtype=t.float32, device=dev) for k in row_names]
-        symbol = "wab_policy_%s%s" % (name, "_gather" if gather else "")
+        # (int32 features are packed rows: the _packed calls, whose index is optional)
+        packed = features.dtype == t.int32
+        symbol = "wab_policy_%s%s" % (name, "_packed" if packed else "_gather" if gather else "")
+        if packed and not gather:
+            gather = (None, 0)
         _lib.check(getattr(_lib.load(), symbol)(
             self._p, features.data_ptr(), *[None if x is None else x.data_ptr() for x in per_row], n, *mid,
             *[None if r is None else r.data_ptr() for r in bufs],
@@ -406,7 +420,7 @@ class DevicePolicy:
                 out["ppo_sums"] = sums[4:]
             if into is None:
                 out["grads"] = grads
-        lead = (n,) if gather else tuple(features.shape[:-1])
+        lead = (n,) if rows is not None else tuple(features.shape[:-1])
         for k, r in zip(row_names, bufs):  # (beside the loss's sums, the entropy rows are "entropy_rows")
             if r is not None:
                 out["entropy_rows" if loss is not None and k == "entropy" else k] = r.view(lead)

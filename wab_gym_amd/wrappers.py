@@ -103,6 +103,10 @@ class PragmaticObsWrapper:
         discounted_returns after it, as in the loop).  fused=False forces the loop; fused=True
         raises NotImplementedError where the one launch does not apply.  store_features=False
         stores no intermediate feature rows (the loop then alternates between two rows).
+        store_features="packed" stores them as 1 bit per feature (wab_gym_amd.features): the result
+        holds feature_bits [T,B,P] int32, which DevicePolicy's evaluate and gradient calls take as
+        they take features, with the same bits in every result, and features is None
+        (wab_rollout_policy_packed in one launch; in the loop a wab_features_pack launch per step).
 
         bootstrap_value=True adds last_value [B] f32, the policy's value of the features the call
         leaves in the wrapper's `features` (one more wab_policy_act after the steps; its sampled
@@ -153,13 +157,23 @@ class PragmaticObsWrapper:
                 if fused:
                     raise NotImplementedError("rollout_policy(fused=True): " + why)
                 one_launch = False
-        feats = t.empty((T, B, F), dtype=t.float32, device=dev) if store_features else None
+        packed = isinstance(store_features, str)
+        if packed and store_features != "packed":
+            raise ValueError("store_features must be True, False or 'packed', not %r" % (store_features,))
+        feats = t.empty((T, B, F), dtype=t.float32, device=dev) if store_features and not packed else None
+        bits = None
+        if packed:
+            from .features import bits_pitch
+
+            bits = t.empty((T, B, bits_pitch(F)), dtype=t.int32, device=dev)
         actions = t.empty((T, B), dtype=t.int8, device=dev)
         value = t.empty((T, B), dtype=t.float32, device=dev)
         rew = t.empty((T, B), dtype=t.float32, device=dev)
         done = t.empty((T, B), dtype=t.uint8, device=dev)
         out = {"features": feats, "actions": actions, "reward": rew, "done": done, "value": value,
                "returns": t.empty((T, B), dtype=t.float32, device=dev)}
+        if packed:
+            out["feature_bits"] = bits
         probs = None
         if return_probs:
             probs = out["probs"] = t.empty((T, B, policy.n_actions), dtype=t.float32, device=dev)
@@ -208,13 +222,15 @@ class PragmaticObsWrapper:
             # last_value, which exists only after the launch: the kernel of the loop)
             in_launch = T <= 128 and not bootstrap_value
             first = self.features if feats is None else feats
-            _lib.check(L.wab_rollout_policy(env._h, policy._p, first.data_ptr(), T, ctypes.addressof(st),
-                                            actions.data_ptr(), value.data_ptr(),
-                                            None if probs is None else probs.data_ptr(), rew.data_ptr(),
-                                            done.data_ptr(), None if feats is None else feats.data_ptr(),
-                                            self.features.data_ptr(), float(gamma), None,
-                                            out["returns"].data_ptr() if in_launch else None, env._stream()),
-                       "wab_rollout_policy")
+            call, name = (L.wab_rollout_policy_packed, "wab_rollout_policy_packed") if packed else \
+                (L.wab_rollout_policy, "wab_rollout_policy")
+            rows_out = bits if packed else feats
+            _lib.check(call(env._h, policy._p, first.data_ptr(), T, ctypes.addressof(st),
+                            actions.data_ptr(), value.data_ptr(),
+                            None if probs is None else probs.data_ptr(), rew.data_ptr(),
+                            done.data_ptr(), None if rows_out is None else rows_out.data_ptr(),
+                            self.features.data_ptr(), float(gamma), None,
+                            out["returns"].data_ptr() if in_launch else None, env._stream()), name)
             env._sync_last_step(scal[:, T - 1], rew[T - 1], done[T - 1])
             env._planes_valid = False
             return finish(in_launch)
@@ -222,6 +238,12 @@ class PragmaticObsWrapper:
         direct = (B * F) % 4 == 0  # every step's feature slice is 16-byte aligned
         cur = self.features
         spare = None if feats is not None else t.empty_like(self.features)
+        def pack_step(k, rows):  # (the loop's packed rows: one launch per step)
+            if packed:
+                _lib.check(L.wab_features_pack(rows.data_ptr(), B, F, bits[k].data_ptr(), None, env._stream()),
+                           "wab_features_pack")
+
+        pack_step(0, self.features)
         for k in range(T):
             src = cur if feats is None else feats[k]
             policy.act(src, out=actions[k], value=value[k], probs=None if probs is None else probs[k])
@@ -234,6 +256,8 @@ class PragmaticObsWrapper:
                                            env._stream()), "wab_step_features")
             if feats is not None and not direct and k + 1 < T:
                 feats[k + 1].copy_(self.features)
+            if k + 1 < T:
+                pack_step(k + 1, nxt)
             cur = nxt
         if feats is None and cur is not self.features:
             self.features.copy_(cur)
