@@ -483,7 +483,22 @@ int wab_snapshot_restore(wab_handle* h, const wab_snapshot_info* info, const voi
  * episode, site 11, the env's current turn, tile (0, 0), k = 0), episode and turn read from the
  * handle's own state; action = #{k < n_actions - 1 : c_k <= u}, c_k the running sum in double,
  * k = 0, 1, ..., of the fp32 probabilities written to `probs`.  The action is an exact function
- * of probs and u, the same for any sharding of the batch. */
+ * of probs and u, the same for any sharding of the batch.
+ * Action rule (wab_policy_set_action_rule below; a fresh policy has {WAB_ACT_SAMPLE, 1.0f}, under
+ * which every bit is as described above).  Temperature t: inv = 1.0f / t, computed on the host in
+ * float32; in the head of wab_policy_act and wab_rollout_policy(_packed) logit_k is replaced by
+ * lg'_k = fl32((logit_k + bias_k) * inv), rounded once (never contracted into the subtraction
+ * that follows), and the softmax above is taken of lg': `probs` is the distribution the action is
+ * taken from, `value` is untouched, and inv = 1.0f changes no bit.
+ * WAB_ACT_SAMPLE: the keyed draw above on those probabilities.
+ * WAB_ACT_GREEDY: a = 0, best = p_0; for k = 1 .. n_actions - 1: if (p_k > best) { best = p_k;
+ * a = k; }, the p_k being the fp32 values written to `probs`: the first maximum of the
+ * probabilities, ties to the lowest index, a row of NaNs gives action 0 (as sampling does); no
+ * draw is made.  Like the sampled one, the action is an exact function of an output the caller
+ * can see, the same for any sharding of the batch.
+ * wab_policy_evaluate* and wab_policy_grad* (plain, _ppo, _gather, _packed) ignore the rule: they
+ * are t = 1, bit for bit.  A caller who trains on rollouts made under t != 1 owns the importance
+ * ratio: the behaviour log-probability of step's action a is log probs[a], not evaluate's logp. */
 typedef struct wab_policy wab_policy;
 typedef struct wab_policy_shape {
   int32_t in_features, h1, h2, h3, n_actions;
@@ -509,6 +524,28 @@ int wab_policy_load(wab_policy* p, const wab_policy_weights* weights, void* stre
  * is on another device; WAB_E_STATE before the first wab_policy_load or the first wab_reset. */
 int wab_policy_act(wab_handle* h, wab_policy* p, const float* features, int8_t* actions, float* probs,
                    float* value, void* stream);
+
+/* Defined where the two entry points below exist (added without a change of WAB_ABI_VERSION:
+ * nothing older changed). */
+#define WAB_HAS_ACTION_RULE 1
+enum { WAB_ACT_SAMPLE = 0, WAB_ACT_GREEDY = 1 };
+typedef struct wab_action_rule {
+  int32_t mode;      /* WAB_ACT_SAMPLE or WAB_ACT_GREEDY */
+  float temperature; /* finite, > 0, with a finite, normal float32 reciprocal */
+} wab_action_rule;
+
+/* How wab_policy_act and wab_rollout_policy(_packed) choose the action (the numeric contract is
+ * above).  Host state of the policy only: no device work, no stream, no allocation.  Every act
+ * and rollout enqueued afterwards reads the rule as kernel arguments (the one-launch path and
+ * the 2 T launches alike); work already enqueued, and a captured graph, keep the rule they were
+ * enqueued or captured with.  wab_policy_load and wab_policy_adam_step leave it alone.
+ * rule == NULL restores {WAB_ACT_SAMPLE, 1.0f}.  WAB_E_INVALID, the stored rule unchanged, for a
+ * NULL policy, a mode that is neither of the two, a temperature that is not finite and > 0, or
+ * one whose float32 reciprocal is zero, subnormal or infinite. */
+int wab_policy_set_action_rule(wab_policy* p, const wab_action_rule* rule);
+
+/* The rule as stored (the temperature as given).  WAB_E_INVALID for a NULL argument. */
+int wab_policy_get_action_rule(const wab_policy* p, wab_action_rule* out);
 
 /* Free the policy (synchronises its device). */
 int wab_policy_destroy(wab_policy* p);

@@ -31,6 +31,8 @@ EXPORTED = [
     # WAB_HAS_PACKED_FEATURES: feature rows as 1 bit per feature
     "wab_feature_bits_pitch", "wab_features_pack", "wab_features_unpack", "wab_policy_evaluate_packed",
     "wab_policy_grad_packed", "wab_policy_grad_ppo_packed", "wab_rollout_policy_packed",
+    # WAB_HAS_ACTION_RULE: greedy and temperature action selection
+    "wab_policy_set_action_rule", "wab_policy_get_action_rule",
     # include/wab_torus.h: the Environment 2.0 torus world
     "wab2_abi_version", "wab2_last_error", "wab2_record_size", "wab2_create", "wab2_destroy",
     "wab2_batch", "wab2_reset", "wab2_step", "wab2_rollout", "wab2_get_state", "wab2_get_counters",
@@ -73,6 +75,11 @@ class WabPolicyWeights(ctypes.Structure):
 
 
 VALUE_LOSS = {"smooth_l1": 0, "mse": 1}  # WAB_VALUE_LOSS_*
+ACTION_MODE = {"sample": 0, "greedy": 1}  # WAB_ACT_*
+
+
+class WabActionRule(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int32), ("temperature", ctypes.c_float)]
 
 
 class WabPpoConfig(ctypes.Structure):
@@ -156,6 +163,8 @@ def load():
     L.wab_policy_load.argtypes = [P, P, P]
     L.wab_policy_act.argtypes = [P, P, P, P, P, P, P]
     L.wab_policy_destroy.argtypes = [P]
+    L.wab_policy_set_action_rule.argtypes = [P, P]
+    L.wab_policy_get_action_rule.argtypes = [P, P]
     L.wab_rollout_policy_fused.argtypes = [P, P]
     L.wab_rollout_policy.argtypes = [P, P, P, I32, P, P, P, P, P, P, P, P, ctypes.c_double, P, P, P]
     L.wab_debug_returns_plan.argtypes = [P, P, P, P, I64, P]

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <new>
 
@@ -250,10 +251,41 @@ int wab_policy_act(wab_handle* h, wab_policy* p, const float* features, int8_t* 
   pp.value = value;
   pp.w = p->w;
   pp.b = p->b;
+  pp.inv_tau = p->inv_tau;
+  pp.act_mode = p->rule.mode;
   DeviceGuard guard(h->device);
   launch_params(policy_kernel(p->dims), (unsigned)((h->p.B + wab::kPolicyEnvs - 1) / wab::kPolicyEnvs), p->lds.total,
                 (hipStream_t)stream, pp);
   HIP_TRY(hipGetLastError());
+  return WAB_OK;
+}
+
+// ---- device policy: the action rule (host state; wab_policy_act and wab_rollout_policy read it) --
+
+int wab_policy_set_action_rule(wab_policy* p, const wab_action_rule* rule) {
+  g_err.clear();
+  if (!p) return fail(WAB_E_INVALID, "wab_policy_set_action_rule: NULL policy");
+  static_assert(sizeof(wab_action_rule) == 8, "wab_action_rule's layout is part of the ABI");
+  static_assert(WAB_ACT_SAMPLE == wab::kActSample && WAB_ACT_GREEDY == wab::kActGreedy, "the kernels' modes");
+  const wab_action_rule r = rule ? *rule : wab_action_rule{WAB_ACT_SAMPLE, 1.0f};
+  if (r.mode != WAB_ACT_SAMPLE && r.mode != WAB_ACT_GREEDY)
+    return fail(WAB_E_INVALID, "wab_policy_set_action_rule: mode " + std::to_string(r.mode) +
+                                   " is neither WAB_ACT_SAMPLE nor WAB_ACT_GREEDY");
+  if (!(std::isfinite(r.temperature) && r.temperature > 0.0f))
+    return fail(WAB_E_INVALID, "wab_policy_set_action_rule: temperature must be finite and > 0");
+  volatile float inv_v = 1.0f / r.temperature;  // (float32, rounded once: never kept wider)
+  const float inv = inv_v;
+  if (!std::isnormal(inv))
+    return fail(WAB_E_INVALID, "wab_policy_set_action_rule: 1 / temperature is not a normal float32");
+  p->rule = r;
+  p->inv_tau = inv;
+  return WAB_OK;
+}
+
+int wab_policy_get_action_rule(const wab_policy* p, wab_action_rule* out) {
+  g_err.clear();
+  if (!p || !out) return fail(WAB_E_INVALID, "wab_policy_get_action_rule: NULL argument");
+  *out = p->rule;
   return WAB_OK;
 }
 
@@ -901,6 +933,8 @@ int rollout_policy_run(const char* name, bool packed, wab_handle* h, wab_policy*
     rp.value = value;
     rp.w = p->w;
     rp.b = p->b;
+    rp.inv_tau = p->inv_tau;
+    rp.act_mode = p->rule.mode;
     q.pol = rp;
     DeviceGuard guard(h->device);
     ++h->rollout_launches;

@@ -49,6 +49,10 @@ struct wab_policy {
   uint16_t* w = nullptr;  // bf16 image, dims.w_total elements
   float* b = nullptr;     // padded biases, dims.b_total floats
   bool loaded = false;
+  // wab_policy_set_action_rule: host state only, read as kernel arguments by every act and
+  // rollout enqueued afterwards (inv_tau = 1.0f / rule.temperature in float32, checked there)
+  wab_action_rule rule = {WAB_ACT_SAMPLE, 1.0f};
+  float inv_tau = 1.0f;
 };
 
 namespace wab_host __attribute__((visibility("hidden"))) {

@@ -70,6 +70,8 @@ struct RollPolicy {
   const float* b;           // packed biases (PolicyDims::b*)
   uint32_t* feature_bits;   // [T][B][P] (wab_rollout_policy_packed, the PACKED instances; else null): the
                             // rows go out packed, slices 1 .. T - 1 (slice 0 is the host's wab_features_pack)
+  float inv_tau;            // the policy's action rule, as PolicyParams': 1 / temperature,
+  int32_t act_mode;         //   kActSample or kActGreedy
 };
 
 // the policy phase's LDS for a step layout of `base` bytes

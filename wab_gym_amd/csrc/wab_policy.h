@@ -13,6 +13,7 @@ constexpr int kPolicyMaxWidth = 256; // hidden widths h1, h2, h3
 constexpr int kPolicyMaxActions = 8;
 constexpr int kPolicyMaxChunk = 256; // input features staged per pass (columns of the LDS chunk)
 constexpr uint32_t SITE_POLICY = 11; // keyed-RNG site of the action draw (first id free in oracle/keyed_rng.py)
+constexpr int32_t kActSample = 0, kActGreedy = 1;  // WAB_ACT_* (include/wab.h): the action rule's modes
 
 // Packed weights: one layer is NT x KS fragments of 64 lanes x 8 bf16 (1 KB each), fragment
 // (nt, ks) at ((nt * KS + ks) * 64 + lane) * 8: lane l holds W[32 nt + (l & 31)][16 ks + 8 (l >> 5)
@@ -100,6 +101,8 @@ struct PolicyParams {
   float* value;              // [B] or null
   const uint16_t* w;         // packed bf16 image (PolicyDims::w*)
   const float* b;            // packed biases (PolicyDims::b*)
+  float inv_tau;             // the action rule (wab_policy_set_action_rule): 1 / temperature,
+  int32_t act_mode;          //   kActSample or kActGreedy
 };
 
 // A set of the policy's ten tensors (wab_policy_weights' fields, in its order): torch Linear

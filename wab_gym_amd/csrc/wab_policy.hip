@@ -19,6 +19,10 @@
 // episode, site 11, the env's current turn, x = 0, y = 0, k = 0), episode and turn read from the
 // handle's state; action = #{k < A - 1 : c_k <= u}, c_k the running sum in double, k = 0, 1, ...,
 // of the fp32 probabilities written out: an exact function of probs and u.
+// Action rule (wab_policy_set_action_rule; PolicyParams::inv_tau, act_mode): the logits, bias
+// included, are first multiplied by inv_tau = 1.0f / temperature, rounded once (1.0f: no bit
+// changes); kActGreedy takes the first maximum of the probabilities written out in place of the
+// draw (ties to the lowest index, a row of NaNs gives 0).
 //
 // Shape: a workgroup of four waves takes 128 envs.  The input features are staged in LDS as
 // bf16 in chunks of KC columns (PolicyLds), each wave loading rows with one dword per lane
@@ -128,8 +132,8 @@ __global__ __launch_bounds__(256, TWO ? 1 : 2) void wab_policy_kernel(PolicyPara
 
   // ---- heads: one tile (rows 0..7 action logits, row 8 the value), wave w on envs 32 w ..
   const pol_f32x16 acc = pol_head_mma(wf, d.KS4, regB + (size_t)(32 * wave + r) * (size_t)p.lds.pitch3 + 8 * h);
-  pol_sample(acc, lane, sampler, p.b + d.bh, d.A, p.seed, p.env_base, env0 + my_env, hdr.w, hdr.y, p.actions, p.probs,
-             p.value);
+  pol_sample(acc, lane, sampler, p.b + d.bh, d.A, p.inv_tau, p.act_mode, p.seed, p.env_base, env0 + my_env, hdr.w, hdr.y,
+             p.actions, p.probs, p.value);
 }
 
 template __global__ void wab_policy_kernel<false>(PolicyParams p);

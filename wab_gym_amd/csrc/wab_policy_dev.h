@@ -231,10 +231,15 @@ __device__ __forceinline__ pol_f32x16 pol_head_mma(const uint4 (&wf)[kPolicyMaxK
 // lane of the wave must call: lane (r, 0) takes rows 4..7 from lane (r, 1), and only lanes 0..31
 // hold a whole column): z_k = logit_k - max, e_k = expf(z_k) (0 for k >= A), s their sum over
 // k = 0, 1, ... in order, inv = 1 / s; p_k = e_k * inv.
+// SCALED (the act and rollout heads, under the policy's action rule): logit_k is first replaced by
+// fl32((logit_k + bias_k) * inv_tau), one rounding of its own, inv_tau = 1 / temperature from the
+// host (1.0f leaves every bit).  The gradient and evaluate kernels take the unscaled form.
 struct PolSoftmax {
   float val, z[kPolicyMaxActions], e[kPolicyMaxActions], s, inv;
 };
-__device__ __forceinline__ PolSoftmax pol_softmax(const pol_f32x16& acc, int lane, const float* __restrict__ bh, int A) {
+template <bool SCALED>
+__device__ __forceinline__ PolSoftmax pol_softmax_of(const pol_f32x16& acc, int lane, const float* __restrict__ bh, int A,
+                                                     float inv_tau) {
   // lane (r, h) holds rows 4 h + 0..3 in registers 0..3 and rows 8 + 4 h + 0..3 in registers 4..7
   // of env column r
   PolSoftmax q;
@@ -249,6 +254,7 @@ __device__ __forceinline__ PolSoftmax pol_softmax(const pol_f32x16& acc, int lan
 #pragma unroll
   for (int k = 0; k < kPolicyMaxActions; ++k) {
     lg[k] = lg[k] + bh[k];
+    if constexpr (SCALED) lg[k] = __fmul_rn(lg[k], inv_tau);
     if (k < A) m = fmaxf(m, lg[k]);
   }
   q.s = 0.0f;
@@ -261,30 +267,47 @@ __device__ __forceinline__ PolSoftmax pol_softmax(const pol_f32x16& acc, int lan
   q.inv = 1.0f / q.s;
   return q;
 }
+__device__ __forceinline__ PolSoftmax pol_softmax(const pol_f32x16& acc, int lane, const float* __restrict__ bh, int A) {
+  return pol_softmax_of<false>(acc, lane, bh, A, 1.0f);
+}
 
-// The tail on the head tile's accumulator: softmax, value and the keyed draw of env column
-// r = lane & 31, finished by the lanes 0..31 for which `sampler` holds (every lane of the wave
+// The tail on the head tile's accumulator: softmax (of the logits scaled by inv_tau), value and
+// the action of env column r = lane & 31 under the policy's action rule (`mode`, uniform: the
+// keyed draw, or kActGreedy, the first maximum of the probabilities as written, no draw made),
+// finished by the lanes 0..31 for which `sampler` holds (every lane of the wave
 // must call).  `env` is the env's index in the handle (the row of actions / value / probs),
 // env_base + env its global id; episode and turn are the env's current ones.  Returns the action
 // (of a sampler lane; -1 otherwise).
 __device__ __forceinline__ int pol_sample(const pol_f32x16& acc, int lane, bool sampler, const float* __restrict__ bh,
-                                          int A, uint64_t seed, int64_t env_base, int64_t env, uint32_t episode,
-                                          uint32_t turn, int8_t* actions, float* probs, float* value) {
-  const PolSoftmax q = pol_softmax(acc, lane, bh, A);
+                                          int A, float inv_tau, int mode, uint64_t seed, int64_t env_base, int64_t env,
+                                          uint32_t episode, uint32_t turn, int8_t* actions, float* probs,
+                                          float* value) {
+  const PolSoftmax q = pol_softmax_of<true>(acc, lane, bh, A, inv_tau);
   if (!sampler) return -1;
-  // the keyed draw (oracle/keyed_rng.py): site 11, the env's episode and turn, tile (0, 0), k = 0
-  const uint64_t ek = episode_key(seed, (uint64_t)(env_base + env), (uint64_t)episode);
-  const uint64_t U = draw_U(0u, make_ts(SITE_POLICY, 0u, (int32_t)turn), (uint32_t)ek, (uint32_t)(ek >> 32));
-  const double u = (double)U * 0x1p-53;
+  const bool greedy = mode == kActGreedy;
+  double u = 0.0;
+  if (!greedy) {
+    // the keyed draw (oracle/keyed_rng.py): site 11, the env's episode and turn, tile (0, 0), k = 0
+    const uint64_t ek = episode_key(seed, (uint64_t)(env_base + env), (uint64_t)episode);
+    const uint64_t U = draw_U(0u, make_ts(SITE_POLICY, 0u, (int32_t)turn), (uint32_t)ek, (uint32_t)(ek >> 32));
+    u = (double)U * 0x1p-53;
+  }
   double c = 0.0;
+  float best = 0.0f;
   int a = 0;
 #pragma unroll
   for (int k = 0; k < kPolicyMaxActions; ++k) {
     const float pk = q.e[k] * q.inv;
     if (k < A) {
       if (probs) probs[(size_t)env * (size_t)A + (size_t)k] = pk;
-      c = c + (double)pk;
-      if (k < A - 1 && c <= u) a += 1;
+      if (greedy) {
+        // ties to the lowest index; a NaN never compares greater, so a row of NaNs gives 0
+        if (k == 0) best = pk;
+        else if (pk > best) { best = pk; a = k; }
+      } else {
+        c = c + (double)pk;
+        if (k < A - 1 && c <= u) a += 1;
+      }
     }
   }
   actions[env] = (int8_t)a;

@@ -1731,8 +1731,8 @@ __device__ __forceinline__ void roll_policy(const Params& p, const SmallLayout& 
     const uint32_t ep = (uint32_t)__shfl((int)episode, my_env, 64), tu = (uint32_t)__shfl((int)turn, my_env, 64);
     const pol_f32x16 acc = pol_head_mma(wf, d.KS4, regB + (size_t)my_env * (size_t)q.lds.pitch3 + 8 * h);
     const int64_t o = (int64_t)t_out * p.B;
-    const int a = pol_sample(acc, lane, sampler, q.b + d.bh, d.A, p.seed, p.env_base, g0 + my_env, ep, tu, q.actions + o,
-                             q.probs ? q.probs + o * d.A : nullptr, q.value ? q.value + o : nullptr);
+    const int a = pol_sample(acc, lane, sampler, q.b + d.bh, d.A, q.inv_tau, q.act_mode, p.seed, p.env_base, g0 + my_env, ep,
+                             tu, q.actions + o, q.probs ? q.probs + o * d.A : nullptr, q.value ? q.value + o : nullptr);
     if (sampler) reinterpret_cast<int8_t*>(lds + L.act)[my_env] = (int8_t)a;
   }
 }

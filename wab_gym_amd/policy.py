@@ -11,6 +11,9 @@ action sampled in the same launch (wab_policy_act, wab_gym_amd/csrc/wab_policy.h
                                                  # PPO's clipped loss (wab_policy_grad_ppo)
     policy.ppo_loss_and_grad(..., rows=perm[a:b])  # the minibatch's rows picked from the whole segment
                                                  # by an int32 index, no copy (wab_policy_grad_ppo_gather)
+    with policy.acting(mode="greedy"):           # evaluation: the first maximum of probs in place of
+        monitor.rollout_policy(policy, T)        # the draw (wab_policy_set_action_rule); temperature=
+                                                 # scales the logits by 1 / temperature
 
     opt = DeviceAdam(policy, model, lr=3e-4)     # optimizer.step() and the re-pack in HIP
     opt.step()                                   # (wab_policy_adam_step): no policy.load after it
@@ -19,13 +22,14 @@ loss_and_grad fills each parameter's .grad; the caller steps with DeviceAdam, or
 optimizer and reloads.
 
 What the kernels compute is `reference_forward`, `reference_loss_and_grad` (the numeric
-contracts, in torch on the CPU), `reference_adam_step` (in numpy) and `sample_reference` (the
-sampling rule, in numpy) of policy_reference.py, re-exported here; the tests check the kernels
-against them.
+contracts, in torch on the CPU), `reference_adam_step` (in numpy), `sample_reference` (the
+sampling rule, in numpy) and `select_reference` (the action rule: that, or the greedy first
+maximum) of policy_reference.py, re-exported here; the tests check the kernels against them.
 The reference's `+ U(0, 1) / 100` input noise (actor_critic.py:189) is not reproduced.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -168,6 +172,24 @@ def check_adam_args(lr, betas, eps, weight_decay, max_grad_norm):
         raise ValueError("max_grad_norm is NaN")
 
 
+def check_action_rule(mode, temperature):
+    """The argument checks of wab_policy_set_action_rule, on the host (ValueError): mode "sample"
+    or "greedy"; temperature finite and > 0 as a float32, and its float32 reciprocal (what the
+    kernels multiply the logits by) finite and normal.  Returns (the mode's WAB_ACT_* number, the
+    temperature as float32, its reciprocal as float32)."""
+    if not isinstance(mode, str) or mode not in _lib.ACTION_MODE:
+        raise ValueError("mode must be 'sample' or 'greedy', not %r" % (mode,))
+    with np.errstate(all="ignore"):
+        tau = np.float32(temperature)
+        if not (np.isfinite(tau) and tau > 0):
+            raise ValueError("temperature must be finite and > 0, not %r" % (temperature,))
+        inv = np.float32(1.0) / tau
+    if not np.isfinite(inv) or inv < np.finfo(np.float32).tiny:
+        raise ValueError("1 / temperature must be a normal float32: temperature %r is outside what the kernels "
+                         "can scale by" % (temperature,))
+    return _lib.ACTION_MODE[mode], tau, inv
+
+
 def adam_beta_powers(step, betas):
     """beta1^step and beta2^step as the optimizer state keeps them: `step` sequential double
     multiplications each (0.0 for step 0, where they are not read)."""
@@ -249,7 +271,13 @@ class DevicePolicy:
     """The policy network on the env's device.  `module_or_state_dict` holds the five Linears by
     the reference's names (affine1, affine2, affine3, action_head, value_head); `env` is the
     BatchedWolvesAndBushesEnv (or a wrapper of it) whose envs it acts for: its episode and turn
-    counters key the draw."""
+    counters key the draw.
+
+    The action rule (set_action_rule, acting) reaches act() and the rollouts only.  evaluate(),
+    loss_and_grad() and ppo_loss_and_grad() ignore it: they are temperature 1, bit for bit.  A
+    caller who trains on rollouts made under temperature != 1 owns the importance ratio: the
+    behaviour log-probability of an action a is log probs[a] of the rollout's probs, not
+    evaluate()'s logp."""
 
     def __init__(self, module_or_state_dict, env):
         import torch
@@ -299,9 +327,42 @@ class DevicePolicy:
             raise ValueError("%s must be a contiguous %s tensor of shape %s on %s"
                              % (name, str(dtype).replace("torch.", ""), shape, self.env.device))
 
+    def set_action_rule(self, mode="sample", temperature=1.0):
+        """How act() and the rollouts choose the action (wab_policy_set_action_rule): "sample", the
+        keyed draw, or "greedy", the first maximum of the probabilities (ties to the lowest index),
+        on the softmax of the logits divided by `temperature`.  Host state only: every act() and
+        rollout_policy() enqueued afterwards follows it, a captured graph keeps the rule it was
+        captured with, load() and DeviceAdam.step() leave it alone.  ValueError from
+        check_action_rule."""
+        m, tau, _ = check_action_rule(mode, temperature)
+        rule = _lib.WabActionRule(m, float(tau))
+        _lib.check(_lib.load().wab_policy_set_action_rule(self._p, ctypes.addressof(rule)),
+                   "wab_policy_set_action_rule")
+
+    @property
+    def action_rule(self):
+        """(mode, temperature) as the library holds them (wab_policy_get_action_rule)."""
+        rule = _lib.WabActionRule()
+        _lib.check(_lib.load().wab_policy_get_action_rule(self._p, ctypes.addressof(rule)),
+                   "wab_policy_get_action_rule")
+        names = {v: k for k, v in _lib.ACTION_MODE.items()}
+        return names[int(rule.mode)], float(rule.temperature)
+
+    @contextlib.contextmanager
+    def acting(self, mode="sample", temperature=1.0):
+        """with policy.acting(mode="greedy"): ... sets the rule and restores the previous one on
+        exit (what was enqueued inside keeps the rule it was enqueued with)."""
+        before = self.action_rule
+        self.set_action_rule(mode, temperature)
+        try:
+            yield self
+        finally:
+            self.set_action_rule(*before)
+
     def act(self, features, out=None, probs=None, value=None):
-        """Sampled actions int8 [B] of features [B, F] float32 (one launch on the env's stream).
-        out, probs [B, A] float32 and value [B] float32 are written when given."""
+        """Actions int8 [B] of features [B, F] float32 under the policy's action rule (sampled by
+        default; one launch on the env's stream).  out, probs [B, A] float32 (the distribution the
+        action is taken from) and value [B] float32 are written when given."""
         t = self._torch
         B = self.env.num_envs
         self._check(features, (B, self.in_features), t.float32, "features")
@@ -643,4 +704,5 @@ class DeviceAdam:
 # (At the end: policy_reference imports this module's names, and either can be imported first.)
 from .policy_reference import (adam_fresh_state, keyed_u, pair_tree_sum, reference_adam_step,  # noqa: E402,F401
                                reference_forward, reference_loss_and_grad, reference_ppo_loss_and_grad,
-                               sample_reference, _reference_gather, _reference_head_and_backward, _value_loss)
+                               sample_reference, select_reference, _reference_gather, _reference_head_and_backward,
+                               _value_loss)

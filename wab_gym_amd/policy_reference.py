@@ -9,12 +9,15 @@ from __future__ import annotations
 import numpy as np
 
 
-def reference_forward(state_dict, features, hidden=None):
+def reference_forward(state_dict, features, hidden=None, temperature=1.0):
     """The kernel's numeric contract in torch on the CPU: every matmul operand (features, weights,
     hidden activations after bias, leaky_relu and clamp) rounded to bf16 (nearest even), everything
     else in float64 (the kernel: fp32 MFMA accumulation, fp32 bias / leaky_relu(0.01) / clamp(-4, 4)
     / max-subtracted softmax / value).  Returns (probs [B, A], value [B]) as float64 tensors.
-    `hidden`, a list, receives each hidden layer's (pre-activation, bf16 output) pair."""
+    `hidden`, a list, receives each hidden layer's (pre-activation, bf16 output) pair.
+    temperature (the action rule of act and rollout): the logits, bias included, are scaled by
+    float64(float32(1) / float32(temperature)), the factor the kernel multiplies by; the value is
+    not scaled, and 1.0 leaves every bit."""
     import torch
 
     sd = {k: v.detach().to("cpu", torch.float32) for k, v in _state_dict(state_dict).items()}
@@ -35,6 +38,8 @@ def reference_forward(state_dict, features, hidden=None):
         if hidden is not None:
             hidden.append((z, x))
     logits = linear(x, "action_head")
+    if temperature != 1.0:
+        logits = logits * float(np.float32(1.0) / np.float32(temperature))
     e = torch.exp(logits - logits.max(dim=-1, keepdim=True).values)
     return e / e.sum(dim=-1, keepdim=True), linear(x, "value_head")[:, 0]
 
@@ -350,6 +355,27 @@ def sample_reference(probs_f32, seed, env_ids, episode, turn):
     c = np.cumsum(p.astype(np.float64), axis=1)  # sequential, in order k = 0, 1, ...
     u = keyed_u(seed, np.asarray(env_ids), np.asarray(episode), np.asarray(turn))
     return (c[:, :-1] <= u[:, None]).sum(axis=1).astype(np.int8)
+
+
+def select_reference(probs_f32, seed, env_ids, episode, turn, mode="sample"):
+    """The action rule in numpy on the float32 probabilities the kernel writes: "sample" is
+    sample_reference; "greedy" is the first maximum, a = 0, best = p_0, then for k = 1 .. A - 1:
+    if p_k > best: best, a = p_k, k (ties to the lowest index, a row of NaNs gives 0; no draw is
+    made, and seed, env_ids, episode and turn are not read).  int8 [B]."""
+    if mode == "sample":
+        return sample_reference(probs_f32, seed, env_ids, episode, turn)
+    if mode != "greedy":
+        raise ValueError("mode must be 'sample' or 'greedy', not %r" % (mode,))
+    p = np.asarray(probs_f32)
+    if p.dtype != np.float32:
+        raise ValueError("probs must be float32: the rule is defined on the values the kernel writes")
+    a = np.zeros(p.shape[0], np.int8)
+    best = p[:, 0].copy()
+    for k in range(1, p.shape[1]):
+        up = p[:, k] > best
+        best = np.where(up, p[:, k], best)
+        a[up] = k
+    return a
 
 
 # At the end, as policy.py's re-export of this module is: either module can then be imported first.

@@ -83,7 +83,8 @@ class PragmaticObsWrapper:
     def rollout_policy(self, policy, T, gamma=0.99, store_planes=False, store_features=True, return_probs=False,
                        fused=None, normalize=False, bootstrap_value=False, gae_lambda=None, whiten=False):
         """T closed-loop steps of actor_critic.main's loop (actor_critic.py:185-200) on the env's
-        stream: step t's action is sampled by `policy` (a DevicePolicy) from step t's features, then
+        stream: step t's action is chosen by `policy` (a DevicePolicy) from step t's features under
+        its action rule (sampled by default; policy.acting(mode="greedy") for evaluation), then
         the env steps.  No host synchronisation, so the whole call can be captured in a graph.  It
         starts from the features of the current observation (recomputed from the env's obs planes
         when they are valid, else the wrapper's own `features` as its last reset()/step()/rollout
